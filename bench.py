@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark: end-to-end PPO-Clip env-steps/s at num_envs=4096, horizon=128 (BASELINE.json config C2:
 SynthBox(obs=17, act=6), ppo/mujoco.yaml hyper-parameters: n_epoch 16, n_minibatch 8, [256] nets,
-LeakyReLU, Adam eps=1e-5, LinearLR) plus the GAE kernel's HBM roofline.
+LeakyReLU, Adam eps=1e-5, LinearLR); with --full, plus the GAE kernel's HBM roofline and the other legs.
 
 A "step" is one PPO iteration on every rank: 128 env steps of the 4096-env device-resident rollout
 (obs-RMS + normalise, policy forward, action sample, env step, bootstrap critic, bookkeeping), the GAE
@@ -9,7 +9,10 @@ scan over [4096, 128], then 16 epochs x 8 minibatches of 65 536 (gather, heads f
 fwd+bwd kernel, MLP backward, [RCCL all-reduce], grad-clip, Adam, LinearLR).  Inputs start resident in
 HBM (the env lives on the GPU).  value = env-steps processed by all ranks / max-over-ranks wall time.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W]     the headline figure only: set up, warm up, time K steps
+    python bench.py --full ...                          plus every side measurement (roofline, C1 / C3 / C4 / C5,
+                                                        CPU baselines, sweeps, profiler child runs)
+    python bench.py --dump-outputs DIR ...              also write what the last timed step computed as DIR/<name>.npy
     torchrun --nproc-per-node N ... bench.py --gpus N ...     (one process per GPU, RCCL)
 """
 import argparse
@@ -42,6 +45,14 @@ def parse():
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--n-epoch", type=int, default=16)
     p.add_argument("--n-minibatch", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="also run every side measurement (GAE roofline and kernel timing, sweeps, C1 / C3 / C4 / C5 legs, "
+                        "CPU baselines, the data-parallel path and all-reduce probes, rocprofv3 child runs); the "
+                        "--no-* options below choose among them.  Without it: set-up, warm-up, the timed steps, the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last one computed (rollout buffer, GAE outputs, updated "
+                        "parameters, obs statistics, losses) as DIR/<name>.npy (float32 / float64); that step restarts from "
+                        "the state set-up left (restored outside the clock), so its inputs are the same in every run")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-updates", type=int, default=24, help="updates timed in the bounded CPU sample")
     p.add_argument("--no-sweep", action="store_true")
@@ -92,7 +103,13 @@ def parse():
     p.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc HBM-traffic passes")
     p.add_argument("--no-rocprof", action="store_true",
                    help="skip the child rocprofv3 --kernel-trace run that times the in-loop GAE launches")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:   # a plain run: nothing but the headline figure's own steps
+        for name in ("no_cpu_baseline", "no_sweep", "no_per", "no_c1", "no_c3", "no_c4", "no_kernel_timing", "no_pmc",
+                     "no_rocprof"):
+            setattr(args, name, True)
+        args.dp_path = "off"
+    return args
 
 
 def gae_bytes(n_envs, horizon, mid_truncations):
@@ -827,6 +844,103 @@ def dp_path_bench(device, args, steps=3, warmup=2):
             "hook_calls_per_minibatch": calls / (steps * args.n_epoch * args.n_minibatch)}
 
 
+DUMP_ARRAY_BYTES = 1 << 20    # per dumped array; a larger one is cut to a sample of its rows
+DUMP_TOTAL_BYTES = 60000000   # all arrays together stay under this (the per-array cap shrinks when there are many)
+
+
+def dump_outputs(agent, out_dir):
+    """--dump-outputs: what the last timed agent.train(T) left to its caller, one DIR/<name>.npy each (float32, or
+    float64 where the agent holds float64): the rollout buffer it filled (observations, actions, rewards, values,
+    terminals, closures, bootstraps, old log-probabilities), the GAE scan's advantages and returns, the observation
+    statistics, the parameters after the iteration's updates and the iteration's logged losses.  An array above
+    DUMP_ARRAY_BYTES is cut to a fixed sample of its rows (numpy default_rng(0), sorted: the same rows in every run),
+    so that all of them together stay under DUMP_TOTAL_BYTES.
+    The agent's seeds are fixed, so two runs with the same arguments dump the same inputs' outputs."""
+    import numpy as np
+    import torch
+    mem = agent.memory
+    arrays = {"mem_observations": mem.observations, "mem_actions": mem.actions, "mem_rewards": mem.rewards,
+              "mem_values": mem.values, "mem_terminals": mem.terminals, "mem_closed": mem.closed, "mem_boot": mem.boot,
+              "mem_advantages": mem.advantages, "mem_returns": mem.returns, "obs_mean": agent.obs_mean,
+              "obs_var": agent.obs_var, "obs_count": agent.obs_count}
+    for k, v in mem.auxiliary_infos.items():
+        arrays["mem_aux_" + k] = v
+    for k, v in agent.policy.state_dict().items():
+        arrays["param_" + k] = v
+    if agent.infos:
+        info = {k: v for k, v in agent.infos[-1].items() if isinstance(v, float)}
+        for k in sorted(info):
+            arrays["info_" + k.replace("/", "_")] = torch.tensor([info[k]], dtype=torch.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_ARRAY_BYTES, DUMP_TOTAL_BYTES // len(arrays))
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().to("cpu")
+        a = a.numpy().astype(np.float64 if a.dtype == torch.float64 else np.float32)
+        if a.nbytes > cap and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, cap // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        total += a.nbytes
+    return total
+
+
+_SCALARS = (int, float, bool, str, type(None))
+
+
+class AgentSnapshot:
+    """--dump-outputs: the agent's whole state right after set-up (every tensor reachable from it, cloned; every scalar
+    and list / tuple of scalars held by its objects and their dicts), put back in place before the last timed step, so
+    that the step whose outputs are dumped starts from the same inputs in every run whatever the steps before it left
+    (the update's split GEMMs do not repeat bit for bit from run to run, and training amplifies that from step to
+    step).  Tensors are restored with copy_ (captured graphs keep reading the same storage)."""
+
+    def __init__(self, root):
+        import torch
+        self.tensors, self.attrs, self.items = [], [], []
+        seen, stack = set(), [root]
+        while stack:
+            o = stack.pop()
+            if id(o) in seen:
+                continue
+            seen.add(id(o))
+            if isinstance(o, torch.Tensor):
+                self.tensors.append((o, o.detach().clone()))
+                g = getattr(o, "grad", None)
+                if g is not None:
+                    stack.append(g)
+            elif isinstance(o, dict):
+                self.items.append((o, {k: self._copy(v) for k, v in o.items() if self._plain(v)}))
+                stack.extend(o.values())
+            elif isinstance(o, (list, tuple, set)):
+                stack.extend(o)
+            elif hasattr(o, "__dict__") and type(o).__module__.split(".")[0] in ("xuanpolicy_amd", "torch", "types"):
+                d = vars(o)
+                self.attrs.append((o, {k: self._copy(v) for k, v in d.items() if self._plain(v)}))
+                stack.extend(d.values())
+
+    @staticmethod
+    def _plain(v):
+        return isinstance(v, _SCALARS) or (isinstance(v, (list, tuple)) and all(isinstance(x, _SCALARS) for x in v))
+
+    @staticmethod
+    def _copy(v):
+        return list(v) if isinstance(v, list) else v
+
+    def restore(self):
+        import torch
+        with torch.no_grad():
+            for t, c in self.tensors:
+                t.copy_(c)
+        for o, d in self.attrs:
+            for k, v in d.items():
+                setattr(o, k, self._copy(v))
+        for o, d in self.items:
+            for k, v in d.items():
+                o[k] = self._copy(v)
+        torch.cuda.synchronize()
+
+
 def _cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -1049,6 +1163,8 @@ def main():
     if world > 1:
         broadcast_parameters(agent.policy)
 
+    # --dump-outputs: the last timed step restarts from the state set-up left (outside the clock), see AgentSnapshot
+    snap = AgentSnapshot(agent) if args.dump_outputs and args.warmup + args.steps > 1 else None
     for _ in range(args.warmup):
         agent.train(T)
     torch.cuda.synchronize()
@@ -1063,9 +1179,15 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1 if snap else args.steps):
         agent.train(T)
     torch.cuda.synchronize()
+    if snap:   # the clock stops while the state is put back, then times the last step
+        paused = time.perf_counter()
+        snap.restore()
+        t0 += time.perf_counter() - paused
+        agent.train(T)
+        torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -1073,9 +1195,11 @@ def main():
         e = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(agent, args.dump_outputs)
     n_updates = args.steps * args.n_epoch * args.n_minibatch
     dp = None
-    if world > 1:
+    if world > 1 and args.full:
         probe = allreduce_probe(agent.learner, device)
         ms_step = elapsed / args.steps * 1e3
         dp = {"collectives_per_minibatch": (gs.collectives - coll0) / n_updates if gs is not None else None,

@@ -15,13 +15,13 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from tests.golden.parts import load_npz
 
     cache = {}
 
     def load(name):
         if name not in cache:
-            cache[name] = dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+            cache[name] = load_npz(os.path.join(GOLDEN, name))
         return cache[name]
     return load
 

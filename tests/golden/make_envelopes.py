@@ -24,10 +24,11 @@ sys.path.insert(0, REPO)
 from oracle import cpu_ref  # noqa: E402
 from oracle.synth_env import SynthAtariEnv  # noqa: E402
 from tests.golden.fixture_init import uniform_state  # noqa: E402
+from tests.golden.parts import load_npz  # noqa: E402
 
 
 def _load(name):
-    return dict(np.load(os.path.join(HERE, name), allow_pickle=False))
+    return load_npz(os.path.join(HERE, name))
 
 
 def _perdqn_batch(seed, k, B, A):   # make_golden.perdqn_batch

@@ -43,6 +43,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, REPO)
 
 import ref_loader  # noqa: E402
+from parts import save_npz  # noqa: E402  (fixtures above the 1 MiB file limit are stored in parts)
 
 xuance = ref_loader.import_reference()
 import torch  # noqa: E402
@@ -488,7 +489,7 @@ def capture_atari(N=4, T=16, iters=2, max_ep=20, n_actions=6, seed=5, net=ATARI_
     out["config"] = np.asarray([N, T, n_actions, cfg.n_epoch, cfg.n_minibatch, max_ep, seed], np.int64)
     out["net"] = np.asarray(net["filters"] + net["kernels"] + net["strides"] + net["fc_hidden_sizes"], np.int64)
     _sd_compact("sd1/", policy, out)
-    np.savez_compressed(os.path.join(HERE, fname), **out)
+    save_npz(os.path.join(HERE, fname), out)
     print(fname, len(out), "closures", int(out["closed"].sum()), "life-loss terminals", int(out["term"].sum()))
 
 
@@ -537,7 +538,7 @@ def capture_perdqn(B=32, A=18, n_updates=4, seed=9, sync=2, gamma=0.99, net=PERD
     out["config"] = np.asarray([B, A, n_updates, seed, sync], np.int64)
     out["gamma"] = np.asarray(gamma, np.float64)
     out["net"] = np.asarray(net["filters"] + net["kernels"] + net["strides"] + net["q_hidden"], np.int64)
-    np.savez_compressed(os.path.join(HERE, fname), **out)
+    save_npz(os.path.join(HERE, fname), out)
     print(fname, len(out))
 
 
@@ -648,7 +649,7 @@ def capture_perdqn_agent(N=4, n_size=128, batch=64, A=18, steps=48, seed=13, max
                               np.float64)
     out["net"] = np.asarray(net["filters"] + net["kernels"] + net["strides"] + net["q_hidden"], np.int64)
     _sd("sd1/", policy, out)
-    np.savez_compressed(os.path.join(HERE, fname), **out)
+    save_npz(os.path.join(HERE, fname), out)
     print(fname, len(out), "updates", n_up)
 
 
@@ -784,7 +785,7 @@ def capture_vecloop(name, seed=11):
     out["config"] = np.asarray([N, T, D or 0, A, max_ep, int(obsnorm), int(discrete), seed, cfg.n_epoch,
                                 cfg.n_minibatch], np.int64)
     fname = "vecloop_%s.npz" % name
-    np.savez_compressed(os.path.join(HERE, fname), **out)
+    save_npz(os.path.join(HERE, fname), out)
     mid = (out["closed"][:, :, :T - 1] != 0) & (out["it/term"][:, :, :T - 1] == 0)
     print(fname, len(out), "closures", int(out["closed"].sum()), "mid truncations", int(mid.sum()),
           "terminals", int(out["it/term"].sum()))

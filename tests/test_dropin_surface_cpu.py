@@ -1,29 +1,32 @@
 """CPU: the import-swap surface of INTEGRATION.md.  Every name the reference's on-policy examples import
-from `xuance` (examples/ppo/ppo_mujoco.py, ppo_atari.py; read as text when /root/reference is mounted)
-resolves under `xuanpolicy_amd`, and the agent / runner methods those examples call exist with the
-reference's signatures (agent.py:74-79, ppoclip_agent.py:59,113, runner_drl.py:77,100)."""
-import ast
+from `xuance` (examples/ppo/ppo_mujoco.py, ppo_atari.py) resolves under `xuanpolicy_amd`, and the agent / runner
+methods those examples call exist with the reference's signatures (agent.py:74-79, ppoclip_agent.py:59,113,
+runner_drl.py:77,100).  What the tests need of the reference is recorded as data in tests/golden/ref_surface.json
+(tests/golden/make_ref_surface.py writes it where the reference imports): the examples' import lists, the agents
+module's names, and the module trees of the reference's policy objects."""
 import inspect
+import json
 import os
+import sys
+import types
 from argparse import Namespace
 
 import pytest
 
 REF_EXAMPLES = [os.path.join("/root/reference/examples/ppo", f) for f in ("ppo_mujoco.py", "ppo_atari.py")]
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+with open(os.path.join(REPO, "tests", "golden", "ref_surface.json")) as _f:
+    REF_SURFACE = json.load(_f)
 
 
 def _imports(path):
-    tree = ast.parse(open(path).read())
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] == "xuance":
-            yield node.module, [a.name for a in node.names]
+    """The recorded `from xuance... import names` lines of that example."""
+    for module, names in REF_SURFACE["example_imports"][os.path.basename(path)]:
+        yield module, names
 
 
 @pytest.mark.parametrize("path", REF_EXAMPLES)
 def test_reference_example_imports_resolve(path):
-    if not os.path.exists(path):
-        pytest.skip("reference not mounted")
     import importlib
     seen = 0
     for module, names in _imports(path):
@@ -85,35 +88,49 @@ def _layer_sig(layers):
     return [(lin.in_features, lin.out_features, code, slope) for lin, code, slope in layers]
 
 
+def _rebuild(desc):
+    """A policy object with the recorded module tree of the reference's own (plain torch containers: the same
+    attribute names, Linear / LeakyReLU arguments, parameter names, shapes and order, and no `discrete` attribute)."""
+    import torch
+    from torch import nn
+    root = nn.Module()
+    made = {"": root}
+    for name, kind, args in desc["modules"]:
+        m = getattr(nn, kind)(**args)
+        parent, _, leaf = name.rpartition(".")
+        made[parent].add_module(leaf, m)
+        made[name] = m
+    for name, shape in desc["state_dict"]:
+        parent, _, leaf = name.rpartition(".")
+        if not hasattr(made[parent], leaf):   # a bare parameter: the Gaussian actor's logstd
+            made[parent].register_parameter(leaf, nn.Parameter(-torch.ones(shape)))
+    assert [[k, list(v.shape)] for k, v in root.state_dict().items()] == desc["state_dict"]
+    assert hasattr(root, "discrete") == desc["has_discrete"]
+    return root
+
+
 @pytest.mark.parametrize("discrete", [False, True])
 def test_reference_policy_objects_take_the_fast_path_plan(discrete):
     """examples/ppo/ppo_mujoco.py:43-58 builds the policy from the REFERENCE's classes (xuance.torch.representations
     .Basic_MLP + xuance.torch.policies.Gaussian_AC_Policy / Categorical_AC_Policy, which carry no `discrete`
     attribute).  The fast-path planner recognises networks by structure, so those objects get the same layer parse,
     the same fused-head / K13 / paired-hidden-layer plan and the same flat-buffer placement as the mirror classes —
-    the device agent's fused update, not the generic fallback.  Imports the reference in this container only."""
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference not mounted")
+    the device agent's fused update, not the generic fallback.  The reference's objects are rebuilt from their
+    recorded module trees (_rebuild)."""
     import torch
-    from tests.golden.ref_loader import import_reference
-    import_reference()
-    import gym
-    from xuance.torch.policies import Categorical_AC_Policy as RefCat, Gaussian_AC_Policy as RefGauss
-    from xuance.torch.representations import Basic_MLP as RefMLP
-    from xuance.torch.utils import ActivationFunctions as RefAct
     from xuanpolicy_amd.fused_mlp import FusedActorCritic, head_placement
     from xuanpolicy_amd.policies import (ActivationFunctions, Basic_MLP, Categorical_AC_Policy, Gaussian_AC_Policy,
                                          policy_discrete)
-    space = gym.spaces.Discrete(4) if discrete else gym.spaces.Box(-1, 1, (6,))
-    init = torch.nn.init.orthogonal_
 
-    def build(mlp, pol_cls, acts):
-        rep = mlp(input_shape=(17,), hidden_sizes=[256], normalize=None, initialize=init, activation=acts["LeakyReLU"],
-                  device="cpu")
-        return pol_cls(action_space=space, representation=rep, actor_hidden_size=[256], critic_hidden_size=[256],
-                       normalize=None, initialize=init, activation=acts["LeakyReLU"], device="cpu")
-    ref = build(RefMLP, RefCat if discrete else RefGauss, RefAct)
-    ours = build(Basic_MLP, Categorical_AC_Policy if discrete else Gaussian_AC_Policy, ActivationFunctions)
+    class _Space:
+        shape, n = (6,), 4
+    init = torch.nn.init.orthogonal_
+    rep = Basic_MLP(input_shape=(17,), hidden_sizes=[256], normalize=None, initialize=init,
+                    activation=ActivationFunctions["LeakyReLU"], device="cpu")
+    ours = (Categorical_AC_Policy if discrete else Gaussian_AC_Policy)(
+        action_space=_Space(), representation=rep, actor_hidden_size=[256], critic_hidden_size=[256], normalize=None,
+        initialize=init, activation=ActivationFunctions["LeakyReLU"], device="cpu")
+    ref = _rebuild(REF_SURFACE["policies"]["categorical" if discrete else "gaussian"])
     assert not hasattr(ref, "discrete") and policy_discrete(ref) == policy_discrete(ours) == discrete
     assert list(ref.state_dict().keys()) == list(ours.state_dict().keys())
     fr, fo = FusedActorCritic(ref), FusedActorCritic(ours)
@@ -129,15 +146,21 @@ def test_reference_policy_objects_take_the_fast_path_plan(discrete):
     assert hr[0][1] is ref.critic.model[0].weight
 
 
-def test_integration_patch_rebinds_the_example_imports():
+def test_integration_patch_rebinds_the_example_imports(monkeypatch):
     """INTEGRATION.md's patch for xuance/torch/agents/__init__.py rebinds the module attributes the example imports
     (`from xuance.torch.agents import PPOCLIP_Agent, get_total_iters`, ppo_mujoco.py:61) besides REGISTRY, so the
-    unmodified example reaches the device agent.  Applied here to the imported reference module (this container)."""
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference not mounted")
-    from tests.golden.ref_loader import import_reference
-    import_reference()
-    import xuance.torch.agents as ref_agents
+    unmodified example reaches the device agent.  Applied here to a module named xuance.torch.agents that holds the
+    recorded names of the reference's: its REGISTRY keys and the three names the patch rebinds, bound to placeholders."""
+    rec = REF_SURFACE["agents_module"]
+    ref_agents = types.ModuleType("xuance.torch.agents")
+    ref_agents.REGISTRY = {k: type(k, (), {}) for k in rec["registry_keys"]}
+    for n in rec["names"]:
+        setattr(ref_agents, n, type(n, (), {}))
+    for name in ("xuance", "xuance.torch"):
+        pkg = types.ModuleType(name)
+        pkg.__path__ = []
+        monkeypatch.setitem(sys.modules, name, pkg)
+    monkeypatch.setitem(sys.modules, "xuance.torch.agents", ref_agents)
     import xuanpolicy_amd.agents as amd
     src = open(os.path.join(REPO, "INTEGRATION.md")).read()
     block = src.split("```python\n# xuance/torch/agents/__init__.py", 1)[1].split("```", 1)[0].split("\n", 1)[1]

@@ -197,7 +197,7 @@ def test_bench_self_launch_two_ranks_one_gpu():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["XPA_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--n-envs", "512", "--horizon", "32", "--n-epoch", "2", "--n-minibatch", "2", "--no-sweep", "--no-per",
            "--no-c1", "--no-c3", "--no-cpu-baseline", "--no-kernel-timing", "--no-pmc", "--no-rocprof"]
     out = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=860)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import cpu_ref
+from tests.golden.parts import load_npz
 
 GAE_TAGS = ["plain_gae", "plain_nogae", "atari_gae", "atari_nogae"]
 
@@ -249,7 +250,7 @@ def test_fixture_init_regenerates_recorded_start():
     match the checksums recorded when the reference trained from them, and the generator is the PCG64 stream."""
     import numpy as np
     from tests.golden.fixture_init import checksum, uniform_state
-    g = dict(np.load(os.path.join(os.path.dirname(__file__), "golden", "atari_a2c_prod.npz"), allow_pickle=False))
+    g = load_npz(os.path.join(os.path.dirname(__file__), "golden", "atari_a2c_prod.npz"))
     shapes = [(k[len("sd0sum/"):], None) for k in g if k.startswith("sd0sum/")]
     assert len(shapes) == 12    # 3 conv + 1 fc (weight, bias) + actor / critic output layers
     from xuanpolicy_amd.policies import AC_CNN_Atari, Categorical_AC_Policy
@@ -270,7 +271,7 @@ def test_perdqn_agent_fixture_schedules():
     """G10 (PerDQN_Agent.train) on CPU: the recorded epsilon / beta schedules follow perdqn_agent.py:74-95 step by step,
     every update's uniforms lie in [0, 1), and the recorded trees are consistent (root = sum of leaves)."""
     import numpy as np
-    g = dict(np.load(os.path.join(os.path.dirname(__file__), "golden", "perdqn_agent.npz"), allow_pickle=False))
+    g = load_npz(os.path.join(os.path.dirname(__file__), "golden", "perdqn_agent.npz"))
     N, n_size, batch, A, steps, seed, max_ep, start, sync, decay = (int(x) for x in g["config"])
     eps0, eps1, beta0 = (float(x) for x in g["hyper"][:3])
     eps, beta = eps0, beta0

@@ -9,12 +9,13 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tests.test_gpu_atari as ta  # noqa: E402
 import tests.test_gpu_perdqn as tp  # noqa: E402
+from tests.golden.parts import load_npz  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
 
 def golden(name):
-    return dict(np.load(os.path.join(GOLD, name), allow_pickle=False))
+    return load_npz(os.path.join(GOLD, name))
 
 
 orig = np.testing.assert_allclose

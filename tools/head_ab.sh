@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 2
 T=${1:-hab}
 L=xuanpolicy_amd/libxuanpolicy_amd.so
 cp $L ab/lib_cur.so || exit 2
-ARGS="--steps 8 --warmup 2 --no-sweep --no-per --no-c1 --no-c3 --no-c4 --no-pmc --no-rocprof --no-cpu-baseline"
+ARGS="--full --steps 8 --warmup 2 --no-sweep --no-per --no-c1 --no-c3 --no-c4 --no-pmc --no-rocprof --no-cpu-baseline"
 for i in 1 2 3; do
   for arm in cur oldhead; do
     cp ab/lib_$arm.so $L || exit 2

@@ -9,7 +9,7 @@ if [ "$2" != "skip-tests" ]; then
   timeout -k 10 400 python -u -m pytest -x -v --timeout 120 --timeout-method thread tests/test_gpu_fused_mlp.py tests/test_gpu_fastpath_e2e.py -m gpu > $O/${T}_pytest.log 2>&1 || { tail -30 $O/${T}_pytest.log; exit 1; }
   tail -1 $O/${T}_pytest.log
 fi
-Q="--no-cpu-baseline --no-sweep --no-per --no-c1 --no-c3 --no-c4 --no-pmc --no-rocprof"
+Q="--full --no-cpu-baseline --no-sweep --no-per --no-c1 --no-c3 --no-c4 --no-pmc --no-rocprof"
 for F in on off on; do
   timeout -k 10 300 python -u bench.py --steps 6 --warmup 2 --trunk-heads $F $Q --out $O/${T}_bench_$F.json > $O/${T}_bench_$F.log 2>&1 || { tail -5 $O/${T}_bench_$F.log; exit 5; }
   python -c "import json;d=json.load(open('$O/${T}_bench_$F.json'));print('$F', d['value'], d['ms_per_step'], d['update_kernels']['heads']['avg_us'], d['phase_split_ms'])"

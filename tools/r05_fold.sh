@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_rollout_split.py \
   tests/test_gpu_rollout.py tests/test_gpu_fastpath_e2e.py tests/test_gpu_hostenv.py tests/test_gpu_kernels.py > gpurun_out/r05f_1.log 2>&1 || { tail -40 gpurun_out/r05f_1.log; exit 1; }
 tail -2 gpurun_out/r05f_1.log
-B="--no-c1 --no-c3 --no-c4 --no-per --no-cpu-baseline --no-sweep --no-pmc --no-rocprof"
+B="--full --no-c1 --no-c3 --no-c4 --no-per --no-cpu-baseline --no-sweep --no-pmc --no-rocprof"
 for cfg in on off on off; do
   timeout -k 10 300 python -u bench.py $B --fold-rms $cfg > gpurun_out/r05fold_$cfg.json 2>/dev/null || exit 1
   python -c "

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_rollout_split.py \
   tests/test_gpu_rollout.py tests/test_gpu_fastpath_e2e.py > gpurun_out/r05r_1.log 2>&1 || { tail -40 gpurun_out/r05r_1.log; exit 1; }
 tail -2 gpurun_out/r05r_1.log
-B="--no-c1 --no-c3 --no-c4 --no-per --no-cpu-baseline --no-sweep --no-pmc --no-rocprof"
+B="--full --no-c1 --no-c3 --no-c4 --no-per --no-cpu-baseline --no-sweep --no-pmc --no-rocprof"
 timeout -k 10 300 python -u bench.py $B > gpurun_out/r05r_on.json 2>/dev/null || exit 1
 timeout -k 10 300 python -u bench.py $B --rollout-split off > gpurun_out/r05r_off.json 2>/dev/null || exit 1
 timeout -k 10 300 python -u bench.py $B > gpurun_out/r05r_on2.json 2>/dev/null || exit 1

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 timeout -k 10 300 python -u -m pytest -x -q --timeout 200 tests/test_gpu_rollout_split.py tests/test_gpu_rollout.py > gpurun_out/r05r2_t.log 2>&1 || { tail -30 gpurun_out/r05r2_t.log; exit 1; }
 tail -1 gpurun_out/r05r2_t.log
-B="--no-c1 --no-c3 --no-c4 --no-per --no-cpu-baseline --no-sweep --no-pmc --no-rocprof"
+B="--full --no-c1 --no-c3 --no-c4 --no-per --no-cpu-baseline --no-sweep --no-pmc --no-rocprof"
 for rep in 1; do
 for cfg in "on nt" "off nt" "on plain" "off plain"; do
   set -- $cfg

@@ -17,7 +17,7 @@ for P in $PASSES; do
     *) echo "unknown pass $P"; exit 2;;
   esac
   timeout -s KILL 240 rocprofv3 --pmc $C --output-format csv -d $O/${T}_$P -o pmc -- \
-      python -u bench.py --steps 1 --warmup 1 --no-sweep --no-per --no-c1 --no-c3 --no-c4 --no-pmc --no-rocprof \
+      python -u bench.py --full --steps 1 --warmup 1 --no-sweep --no-per --no-c1 --no-c3 --no-c4 --no-pmc --no-rocprof \
       --no-cpu-baseline --no-kernel-timing --dp-path off > $O/${T}_$P.log 2>&1 || { tail -5 $O/${T}_$P.log; exit 3; }
   python tools/pmc_update_summary.py $O/${T}_$P $O/${T}_$P.json > /dev/null || exit 4
   echo "pmc $P ok"
