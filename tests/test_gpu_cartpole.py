@@ -253,6 +253,32 @@ def test_small_mlp_epoch_graphs_match_eager(n_steps, n_mb):
         np.testing.assert_array_equal(b, a)
 
 
+def test_graphs_capture_records_with_collector_off():
+    """graphs.capture (every capture of the package goes through it): the body is recorded, not executed, with the
+    cyclic collector off; two replays add twice, and the collector is on again afterwards."""
+    import gc
+    from xuanpolicy_amd import graphs
+    y = torch.zeros(64, dtype=torch.float32, device=DEV)
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        y.add_(1)                                  # warm-up, not part of the graph
+    torch.cuda.current_stream(DEV).wait_stream(side)
+    y.zero_()
+    assert gc.isenabled()
+
+    def body():
+        assert not gc.isenabled()
+        y.add_(1)
+        return "recorded"
+    g, result = graphs.capture(body)
+    assert result == "recorded" and gc.isenabled()
+    g.replay()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(y, torch.full_like(y, 2.0))
+
+
 @pytest.mark.parametrize("agent_name,hidden,obsnorm,n_envs", [("PPO_Clip", 64, True, 8), ("A2C", 64, True, 8),
                                                                ("PPO_Clip", 32, True, 8), ("PPO_Clip", 64, False, 8),
                                                                ("PPO_Clip", 64, True, 100), ("A2C", 64, True, 256)])

@@ -34,7 +34,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, graphs, ops
 from .buffer import DummyOnPolicyBuffer, DummyOnPolicyBuffer_Atari
 from .fused_mlp import Rows
 from .learners import A2C_Learner, PerDQN_Learner, PPOCLIP_Learner
@@ -559,10 +559,7 @@ class _OnPolicyAgent:
             with torch.cuda.stream(side):
                 self._rollout_step_device()        # a real step (also warms up BLAS handles)
             torch.cuda.current_stream(self.device).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._graph_pool):
-                self._rollout_step_device()        # recorded, not executed
-            self._graph = g
+            self._graph, _ = graphs.capture(self._rollout_step_device, self._graph_pool)   # recorded, not executed
             return
         self._graph.replay()
 
@@ -582,11 +579,8 @@ class _OnPolicyAgent:
                 self._rollout_step_graph()   # a real first step + the single-step graph (warm-up, BLAS handles)
                 return 1
             self._chunk_key = key
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._graph_pool):
-                for _ in range(k):
-                    self._rollout_step_device()   # recorded, not executed
-            self._chunk_graph = g
+            self._chunk_graph, _ = graphs.capture(lambda: [self._rollout_step_device() for _ in range(k)],
+                                                  self._graph_pool)   # k steps recorded, not executed
         self._chunk_graph.replay()
         return k
 

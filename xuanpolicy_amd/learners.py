@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, graphs, ops
 from .policies import policy_discrete, policy_heads
 
 
@@ -34,6 +34,8 @@ class Learner:
         self.model_dir = model_dir
         self.iterations = 0
         self.grad_sync = None  # set by xuanpolicy_amd.distributed for data-parallel training
+        self.fused_cnn_enabled = True
+        self._fc = None        # fused_cnn.FusedCNNActorCritic once built (False: the policy does not take it)
 
     def save_model(self, model_path):
         torch.save(self.policy.state_dict(), model_path)
@@ -47,12 +49,15 @@ class Learner:
         names = sorted(n for n in os.listdir(path) if n != "obs_rms.npy")
         dev = self.device if self.device is not None else "cpu"
         self.policy.load_state_dict(torch.load(os.path.join(path, names[-1]), map_location=dev, weights_only=True))
-        fc = getattr(self, "_fc", None)
-        if fc:
-            fc.stale = True
+        if self._fc:
+            self._fc.stale = True
 
     def update(self, *args):
         raise NotImplementedError
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else 0
 
 
 def _dist_of(policy):
@@ -70,11 +75,21 @@ class _FusedPolicyGradient(Learner):
         self.dist = _dist_of(policy)
         self._ws = None
         self._params = [p for p in policy.parameters()]
+        # everything set or built later, at its default
+        self.flat_grads = self.fused_opt = None         # distributed.attach_flat_grads (enable_fast_path)
+        self.fused_mlp_enabled = True
+        self.graph_updates = False                      # minibatch updates as captured graphs: the agent's loop sets it
+        self.graph_k9 = self.graph_epochs = True        # K9 inside the slot graphs; a whole epoch of them as one graph
+        self.small_updates = self.small_split = True    # K30; as one workgroup per 32 rows + a finalize launch
+        self.small_stamps = None                        # diagnostics: int64 [16] phase timestamps (tools/k30_stamps.py)
+        self._fm = self._small_scalars = self._graph_pool = None   # built on first use (_fm False: not for this policy)
+        self._small_split_ws = {}                       # workgroup count -> (gradient parts, loss parts)
+        self._slot_graphs, self._small_graphs, self._epoch_graphs = {}, {}, {}   # key -> "warm" | (graph, scalars, ...)
+        self._graph_failed = False                      # a slot / small-epoch capture failed: stay eager
 
     def _backward_and_step(self, head, logstd, v, d_head, d_logstd, d_v):
-        fg = getattr(self, "flat_grads", None)
-        if fg is not None:
-            fg.zero_()  # grads are views into one flat buffer (xuanpolicy_amd.distributed.FlatGrads)
+        if self.flat_grads is not None:
+            self.flat_grads.zero_()  # grads are views into one flat buffer (xuanpolicy_amd.distributed.FlatGrads)
         else:
             self.optimizer.zero_grad(set_to_none=True)
         tensors, grads = [head, v], [d_head, d_v]
@@ -86,8 +101,8 @@ class _FusedPolicyGradient(Learner):
 
     def _fused_mlp(self):
         """Explicit actor-critic backward (fused_mlp.FusedActorCritic) once gradients live in flat views."""
-        fm = getattr(self, "_fm", None)
-        if fm is None and getattr(self, "flat_grads", None) is not None and getattr(self, "fused_mlp_enabled", True):
+        fm = self._fm
+        if fm is None and self.flat_grads is not None and self.fused_mlp_enabled:
             from .fused_mlp import FusedActorCritic
             try:
                 fm = FusedActorCritic(self.policy, flat=self.flat_grads)
@@ -98,10 +113,10 @@ class _FusedPolicyGradient(Learner):
 
     def _fused_cnn(self):
         """Explicit CNN actor-critic forward/backward (fused_cnn.FusedCNNActorCritic) for AC_CNN_Atari policies."""
-        fc = getattr(self, "_fc", None)
+        fc = self._fc
         if fc is None:
             fc = False
-            if getattr(self, "fused_cnn_enabled", True) and self._device().type == "cuda":
+            if self.fused_cnn_enabled and self._device().type == "cuda":
                 from .fused_cnn import FusedCNNActorCritic
                 try:
                     fc = FusedCNNActorCritic(self.policy)
@@ -116,7 +131,7 @@ class _FusedPolicyGradient(Learner):
         if self.grad_sync is not None:
             self.grad_sync(self._params)
             sq = None
-        fused = getattr(self, "fused_opt", None)
+        fused = self.fused_opt
         if fused is not None and fused.sched_enabled and self.grad_sync is None:
             fused.ensure_window(self.scheduler)
             fused.launch_sched(self._max_norm if self._use_clip else None)   # K9 from the device schedule
@@ -158,8 +173,7 @@ class _FusedPolicyGradient(Learner):
             head, logstd, v, ctx = fc.forward(obs)
             if self._ws is None or self._ws.batch != head.shape[0]:
                 self._ws = ops.LossWorkspace(head.shape[0], head.shape[1], head.device, self.dist)
-            fg = getattr(self, "flat_grads", None)
-            if fg is None:
+            if self.flat_grads is None:
                 for p in self._params:
                     if p.grad is None:
                         p.grad = torch.zeros_like(p)
@@ -172,18 +186,14 @@ class _FusedPolicyGradient(Learner):
             self._sync_clip_step()
             return scalars
         if fm is not None and self._graph_ok(obs):
-            fused = getattr(self, "fused_opt", None)
-            if fused is not None and getattr(self, "graph_k9", True):
+            fused = self.fused_opt
+            if fused is not None and self.graph_k9:
                 # K9 inside the slot graph: it reads lr / Adam step from the device schedule and advances its cursor
                 if not fused.sched_enabled:
                     fused.enable_sched()
                 fused.ensure_window(self.scheduler)
-                scalars = self._graphed_mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, pre,
-                                                   k9=lambda: fused.launch_sched(self._max_norm if self._use_clip
-                                                                                 else None))
-                fused.host_step()
-                if self.scheduler is not None:
-                    self.scheduler.step()
+                scalars = self._graphed_mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, pre, k9=True)
+                self._host_steps(1)
                 return scalars
             scalars = self._graphed_mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, pre)
             self._sync_clip_step()
@@ -214,77 +224,78 @@ class _FusedPolicyGradient(Learner):
 
     def _graph_ok(self, obs):
         # not while ops.TIMER records events: a captured record would be replayed without re-appending its event
-        return (getattr(self, "graph_updates", False) and self.grad_sync is None and isinstance(obs, torch.Tensor)
-                and obs.is_cuda and obs.shape[0] <= self.graph_max_rows and not getattr(self, "_graph_failed", False)
-                and not ops.TIMER.enabled
-                and len(self.__dict__.get("_slot_graphs", ())) < self.graph_max_slots)
+        return (self.graph_updates and self.grad_sync is None and isinstance(obs, torch.Tensor)
+                and obs.is_cuda and obs.shape[0] <= self.graph_max_rows and not self._graph_failed
+                and not ops.TIMER.enabled and len(self._slot_graphs) < self.graph_max_slots)
 
     def _step_key(self):
         """What a captured update bakes in besides its inputs: the parameter / gradient pointers, the fused optimizer's
         buffers (flat params and grads, Adam moments, schedule table + cursor, norm output) and the K9 constants
         (max_norm, clipping, betas, eps).  Re-homed parameters or a changed hyper-parameter give a new key, so a stale
         graph is never replayed against freed memory or old constants."""
-        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-        fused = getattr(self, "fused_opt", None)
-        fk = ()
+        fused, fk = self.fused_opt, ()
         if fused is not None:
-            fk = (ptr(fused.fs.param), ptr(fused.fs.flat), ptr(fused.exp_avg), ptr(fused.exp_avg_sq),
-                  ptr(getattr(fused, "_sched", None)), ptr(getattr(fused, "_cursor", None)),
-                  ptr(getattr(fused, "total_norm", None)))
+            fk = (_ptr(fused.fs.param), _ptr(fused.fs.flat), _ptr(fused.exp_avg), _ptr(fused.exp_avg_sq),
+                  _ptr(getattr(fused, "_sched", None)), _ptr(getattr(fused, "_cursor", None)),
+                  _ptr(getattr(fused, "total_norm", None)))
         g = self.optimizer.param_groups[0]
         b1, b2 = g.get("betas", (0.9, 0.999))
-        return (tuple(p.data_ptr() for p in self._params) + tuple(ptr(p.grad) for p in self._params) + fk
+        return (tuple(p.data_ptr() for p in self._params) + tuple(_ptr(p.grad) for p in self._params) + fk
                 + (float(self._max_norm) if self._max_norm is not None else None, bool(self._use_clip), float(b1),
                    float(b2), float(g.get("eps", 0.0))))
 
     def _slot_key(self, obs, idx, act, adv, ret, old_logp, adv_partials):
-        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
         # the loss coefficients are kernel arguments baked into a capture: part of the key
-        return (ptr(obs), tuple(obs.shape), ptr(idx), -1 if idx is None else idx.shape[0], ptr(act), ptr(adv),
-                ptr(ret), ptr(old_logp), ptr(adv_partials), float(self.clip_range), float(self.vf_coef),
+        return (_ptr(obs), tuple(obs.shape), _ptr(idx), -1 if idx is None else idx.shape[0], _ptr(act), _ptr(adv),
+                _ptr(ret), _ptr(old_logp), _ptr(adv_partials), float(self.clip_range), float(self.vf_coef),
                 float(self.ent_coef)) + self._step_key()
 
-    def _graphed_mlp_update(self, fm, obs, idx, act, adv, ret, old_logp, adv_partials, pre=None, k9=None):
-        """k9: the device part of the clip + Adam step (xpa_clip_adam_step_sched), run after the backward and captured
-        with it; the caller does the host bookkeeping."""
-        key = self._slot_key(obs, idx, act, adv, ret, old_logp, adv_partials)
-        graphs = self.__dict__.setdefault("_slot_graphs", {})
-        ent = graphs.get(key)
-        if ent is None:                     # first use of this slot: eager (warm-up)
-            graphs[key] = "warm"
+    def _host_steps(self, n):
+        """The host's part of n updates whose K9 read (lr, Adam step) from the device schedule."""
+        for _ in range(n):
+            self.fused_opt.host_step()
+            if self.scheduler is not None:
+                self.scheduler.step()
+
+    def _try_capture(self, body, fm=None):
+        """graphs.capture(body) in the learner's pool: (graph, body's result), or None when a launch cannot be captured.
+        Nothing of an aborted capture ran; the host-side state it could have left half-built or pointing into its pool
+        (a ragged last minibatch reallocates the workspace inside it) is put back for the caller's eager fallback."""
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        saved = (self._ws, dict(fm._partials), fm._hws) if fm is not None else None   # K30 (no fm) touches none of it
+        try:
+            return graphs.capture(body, self._graph_pool)
+        except Exception:
+            torch.cuda.synchronize()
+            if fm is not None:
+                self._ws, fm._partials, fm._hws = saved
+                fm._cq.reset()              # queued finalizes of the aborted capture (capture-pool partials)
+                fm._cq_early.reset()
+            return None
+
+    def _graphed_mlp_update(self, fm, obs, idx, act, adv, ret, old_logp, adv_partials, pre=None, k9=False):
+        """k9: with the device part of the clip + Adam step (xpa_clip_adam_step_sched), run after the backward and
+        captured with it; the caller does the host bookkeeping."""
+        def body():
             if pre is not None:
                 pre()
             out = self._mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, step=False)
-            if k9 is not None:
-                k9()
+            if k9:
+                self.fused_opt.launch_sched(self._max_norm if self._use_clip else None)
             return out
+        key = self._slot_key(obs, idx, act, adv, ret, old_logp, adv_partials)
+        slots, ent = self._slot_graphs, self._slot_graphs.get(key)
+        if ent is None:                     # first use of this slot: eager (warm-up)
+            slots[key] = "warm"
+            return body()
         if ent == "warm":
-            if self.__dict__.get("_graph_pool") is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            # host-side state a failed capture could leave half-built: restored before the eager retry
-            saved = (self._ws, dict(fm._partials), fm._hws)
-            try:
-                with torch.cuda.graph(g, pool=self._graph_pool):
-                    if pre is not None:
-                        pre()
-                    out = self._mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, step=False)
-                    if k9 is not None:
-                        k9()
-            except Exception:               # a launch that cannot be captured: stay eager from here on
+            cap = self._try_capture(body, fm)
+            if cap is None:                 # stay eager from here on
                 self._graph_failed = True
-                torch.cuda.synchronize()
-                self._ws, fm._partials, fm._hws = saved[0], saved[1], saved[2]
-                fm._cq.reset()              # queued finalizes of the aborted capture (capture-pool partials)
-                fm._cq_early.reset()
-                del graphs[key]
-                if pre is not None:
-                    pre()
-                out = self._mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, step=False)
-                if k9 is not None:
-                    k9()
-                return out
-            graphs[key] = ent = (g, out, self._ws)   # the graph writes into this workspace: keep it alive
+                del slots[key]
+                return body()
+            slots[key] = ent = cap + (self._ws,)   # the graph writes into this workspace: keep it alive
         ent[0].replay()
         return ent[1]
 
@@ -308,9 +319,9 @@ class _FusedPolicyGradient(Learner):
         """True when a minibatch of `batch` rows of obs_flat [n_rows, d] can take K30 (xpa_small_mlp_update): the
         small_policy_layers shape, flat parameters with the fused Adam, no data-parallel gradient sync, and the LDS
         budget."""
-        if not getattr(self, "small_updates", True) or self.grad_sync is not None:
+        if not self.small_updates or self.grad_sync is not None:
             return False
-        fused = getattr(self, "fused_opt", None)
+        fused = self.fused_opt
         layers = self.small_policy_layers()
         if layers is None or fused is None or fused.fs.numel % 4:
             return False
@@ -322,7 +333,7 @@ class _FusedPolicyGradient(Learner):
         if any(h % 32 or h > 256 for h in (h0, h1, h2)) or not 2 <= k <= 16 or l0.in_features != obs_flat.shape[1] \
                 or l0.in_features > 32:
             return False
-        rows = 32 if getattr(self, "small_split", True) and 32 < batch <= 512 else batch   # per workgroup
+        rows = 32 if self.small_split and 32 < batch <= 512 else batch   # per workgroup
         return int(ops.lib().xpa_small_mlp_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704
 
     def _small_launch(self, obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars=None):
@@ -331,7 +342,7 @@ class _FusedPolicyGradient(Learner):
         fm, fused = self._fused_mlp(), self.fused_opt
         (l0, code, slope), (l1, _, _), (la, _, _), (l2, _, _), (lc, _, _) = (fm.rep[0], fm.actor[0], fm.actor[1],
                                                                              fm.critic[0], fm.critic[1])
-        if getattr(self, "_small_scalars", None) is None:
+        if self._small_scalars is None:
             self._small_scalars = torch.zeros(8, dtype=torch.float32, device=obs_flat.device)
         g = self.optimizer.param_groups[0]
         b1, b2 = g["betas"]
@@ -360,14 +371,13 @@ class _FusedPolicyGradient(Learner):
         a.sched, a.cursor = fused._sched.data_ptr(), fused._cursor.data_ptr()
         out = self._small_scalars if scalars is None else scalars
         a.scalars, a.total_norm_out = out.data_ptr(), fused.total_norm.data_ptr()
-        st = getattr(self, "small_stamps", None)   # diagnostics: int64 [16] of phase timestamps (tools/k30_stamps.py)
-        a.stamps = st.data_ptr() if st is not None else None
+        a.stamps = self.small_stamps.data_ptr() if self.small_stamps is not None else None
         # split form: one workgroup per 32 minibatch rows + a finalize launch (small_split = False: one workgroup)
         B = idx.shape[0]
-        G = (B + 31) // 32 if getattr(self, "small_split", True) and 32 < B <= 512 else 1
+        G = (B + 31) // 32 if self.small_split and 32 < B <= 512 else 1
         a.n_groups = G
         if G > 1:
-            ws = self.__dict__.setdefault("_small_split_ws", {})
+            ws = self._small_split_ws
             if G not in ws:   # zero-filled once: elements no gradient view covers stay 0
                 ws[G] = (torch.zeros((G, fused.fs.numel), dtype=torch.float32, device=obs_flat.device),
                          torch.zeros((G, 8), dtype=torch.float64, device=obs_flat.device))
@@ -384,9 +394,7 @@ class _FusedPolicyGradient(Learner):
         fused.ensure_window(self.scheduler)
         self.iterations += 1
         out = self._small_launch(obs_flat, idx, act, adv, ret, old_logp, use_advnorm)
-        fused.host_step()
-        if self.scheduler is not None:
-            self.scheduler.step()
+        self._host_steps(1)
         return out
 
     def small_epoch(self, obs_flat, batches, use_advnorm, keep_all=False):
@@ -396,47 +404,37 @@ class _FusedPolicyGradient(Learner):
         fused = self.fused_opt
         if not fused.sched_enabled:
             fused.enable_sched()
-        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-        key = (ptr(obs_flat), tuple(obs_flat.shape), bool(use_advnorm), float(self.clip_range), float(self.vf_coef),
-               float(self.ent_coef), bool(getattr(self, "small_split", True))) + \
-            tuple((ptr(b[0]), b[0].shape[0], ptr(b[1]), ptr(b[2]), ptr(b[3]), ptr(b[4])) for b in batches) + \
+        key = (_ptr(obs_flat), tuple(obs_flat.shape), bool(use_advnorm), float(self.clip_range), float(self.vf_coef),
+               float(self.ent_coef), bool(self.small_split)) + \
+            tuple((_ptr(b[0]), b[0].shape[0], _ptr(b[1]), _ptr(b[2]), _ptr(b[3]), _ptr(b[4])) for b in batches) + \
             self._step_key()
-        graphs = self.__dict__.setdefault("_small_graphs", {})
-        ent = graphs.get(key)
+        cache = self._small_graphs
+        ent = cache.get(key)
         # bounded like the slot graphs: a caller whose pointers never repeat stays eager instead of growing the cache
-        graphed = getattr(self, "graph_updates", False) and not getattr(self, "_graph_failed", False) \
-            and len(batches) <= fused.SCHED_WINDOW and (ent is not None or len(graphs) < self.graph_max_slots)
+        graphed = self.graph_updates and not self._graph_failed \
+            and len(batches) <= fused.SCHED_WINDOW and (ent is not None or len(cache) < self.graph_max_slots)
         if ent is None or not graphed:
             outs = []
             for b in batches:
                 out = self.small_update(obs_flat, *b, use_advnorm=use_advnorm)
                 outs.append(out.clone() if keep_all else out)
             if graphed:
-                graphs[key] = "warm"
+                cache[key] = "warm"
             return outs
         fused.ensure_window(self.scheduler, need=len(batches))
         if ent == "warm":
-            if self.__dict__.get("_graph_pool") is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
             # every update writes its loss scalars into its own row (no per-update copy inside the graph)
             rows = torch.zeros((len(batches), 8), dtype=torch.float32, device=obs_flat.device)
-            try:
-                with torch.cuda.graph(g, pool=self._graph_pool):
-                    outs = [self._small_launch(obs_flat, *b, use_advnorm=use_advnorm, scalars=rows[i])
-                            for i, b in enumerate(batches)]
-            except Exception:
+            ent = self._try_capture(lambda: [self._small_launch(obs_flat, *b, use_advnorm=use_advnorm, scalars=rows[i])
+                                             for i, b in enumerate(batches)])
+            if ent is None:                 # stay eager from here on
                 self._graph_failed = True
-                torch.cuda.synchronize()
-                del graphs[key]
+                del cache[key]
                 return self.small_epoch(obs_flat, batches, use_advnorm, keep_all)
-            graphs[key] = ent = (g, outs)
+            cache[key] = ent
         ent[0].replay()
-        for _ in batches:
-            self.iterations += 1
-            fused.host_step()
-            if self.scheduler is not None:
-                self.scheduler.step()
+        self.iterations += len(batches)
+        self._host_steps(len(batches))
         return [o.clone() for o in ent[1]] if keep_all else list(ent[1])
 
     def update_epoch(self, batches, keep_all=False):
@@ -447,49 +445,35 @@ class _FusedPolicyGradient(Learner):
         through update_fused.  Returns the per-update loss-scalar tensors (keep_all False: only the last is guaranteed
         to hold its own update's values — the eager updates share their workspace's scalars)."""
         fm = self._fused_mlp()
-        fused = getattr(self, "fused_opt", None)
-        slots = self.__dict__.get("_slot_graphs", {})
-        keys = [self._slot_key(b[0], b[1], b[2], b[3], b[4], b[5], b[6]) for b in batches] \
+        fused, slots = self.fused_opt, self._slot_graphs
+        keys = tuple(self._slot_key(*b[:7]) for b in batches) \
             if fm is not None and not fm.fused_heads else None
-        ready = (keys is not None and fused is not None and fused.sched_enabled and getattr(self, "graph_k9", True)
-                 and getattr(self, "graph_epochs", True) and all(self._graph_ok(b[0]) for b in batches)
+        ready = (keys is not None and fused is not None and fused.sched_enabled and self.graph_k9
+                 and self.graph_epochs and all(self._graph_ok(b[0]) for b in batches)
                  and all(isinstance(slots.get(k), tuple) for k in keys) and len(batches) <= fused.SCHED_WINDOW)
         if not ready:
             return self._eager_epoch(batches, keep_all)
-        epochs = self.__dict__.setdefault("_epoch_graphs", {})
-        ekey = tuple(keys)
         fused.ensure_window(self.scheduler, need=len(batches))
-        ent = epochs.get(ekey)
+        ent = self._epoch_graphs.get(keys)
         if ent is None:
-            g = torch.cuda.CUDAGraph()
-            # host-side state a failed capture could leave pointing into the aborted capture's pool (a ragged last
-            # minibatch reallocates the workspace inside it): restored before the eager fallback
-            saved = (self._ws, dict(fm._partials), fm._hws)
-            try:
-                with torch.cuda.graph(g, pool=self._graph_pool):
-                    outs = []
-                    for (obs, idx, act, adv, ret, old_logp, adv_partials, pre) in batches:
-                        if pre is not None:
-                            pre()
-                        out = self._mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, step=False)
-                        # every update of the epoch writes the same workspace: each one's scalars copied out in-graph
-                        outs.append(out.clone())
-                        fused.launch_sched(self._max_norm if self._use_clip else None)
-            except Exception:
-                # nothing of the aborted capture ran: stay with the slot graphs from here on
+            def body():
+                outs = []
+                for (obs, idx, act, adv, ret, old_logp, adv_partials, pre) in batches:
+                    if pre is not None:
+                        pre()
+                    out = self._mlp_update(fm, obs, idx, act, adv, ret, old_logp, adv_partials, step=False)
+                    # every update of the epoch writes the same workspace: each one's scalars copied out in-graph
+                    outs.append(out.clone())
+                    fused.launch_sched(self._max_norm if self._use_clip else None)
+                return outs
+            ent = self._try_capture(body, fm)
+            if ent is None:                 # stay with the slot graphs from here on
                 self.graph_epochs = False
-                torch.cuda.synchronize()
-                self._ws, fm._partials, fm._hws = saved
-                fm._cq.reset()
-                fm._cq_early.reset()
                 return self._eager_epoch(batches, keep_all)
-            epochs[ekey] = ent = (g, outs)
+            self._epoch_graphs[keys] = ent
         ent[0].replay()
-        for _ in batches:
-            self.iterations += 1
-            fused.host_step()
-            if self.scheduler is not None:
-                self.scheduler.step()
+        self.iterations += len(batches)
+        self._host_steps(len(batches))
         # the graph's scalar buffers are rewritten by the next replay: copies when every update's values are kept
         return [o.clone() for o in ent[1]] if keep_all else list(ent[1])
 
@@ -518,7 +502,7 @@ class _FusedPolicyGradient(Learner):
     def enable_fast_path(self, fused_optimizer=True):
         """Flat parameters/gradients and the fused clip+Adam kernel (xuanpolicy_amd.flat)."""
         from .distributed import attach_flat_grads
-        if getattr(self, "flat_grads", None) is None:
+        if self.flat_grads is None:
             attach_flat_grads(self, allreduce=True, fused_optimizer=fused_optimizer)
         return self
 
@@ -616,6 +600,7 @@ class PerDQN_Learner(Learner):
         self.sync_frequency = sync_frequency
         super().__init__(policy, optimizer, scheduler, device, model_dir)
         self._err = None
+        self._fq = None        # fused_cnn.FusedQNetwork once built (False: the policy does not take it)
 
     def _f32(self, x, dev):
         if isinstance(x, torch.Tensor):
@@ -624,11 +609,11 @@ class PerDQN_Learner(Learner):
 
     def _fused_q(self):
         """Explicit Q-network forward / backward (fused_cnn.FusedQNetwork) for CNN Q-networks on uint8 frames."""
-        fq = getattr(self, "_fq", None)
+        fq = self._fq
         if fq is None:
             fq = False
             dev = next(self.policy.parameters()).device
-            if getattr(self, "fused_cnn_enabled", True) and dev.type == "cuda" and hasattr(self.policy, "eval_Qhead"):
+            if self.fused_cnn_enabled and dev.type == "cuda" and hasattr(self.policy, "eval_Qhead"):
                 from .fused_cnn import FusedQNetwork
                 try:
                     fq = FusedQNetwork(self.policy)
