@@ -74,6 +74,83 @@ def test_invalid_arguments_rejected_before_launch(lib):
                                               None) == 1
 
 
+def test_bindings_literal_pins():
+    """The header-derived bindings of entry points that between them use every type spelling and declaration shape
+    the parser handles, written out (as the hand-kept table had them)."""
+    from ctypes import c_double, c_float as f32, c_int, c_int32 as i32, c_int64 as i64, c_uint32 as u32, c_void_p as p
+    pins = {
+        "xpa_abi_version": (c_int, []),                                                     # (void)
+        "xpa_gae_scan": (c_int, [p, p, p, p, p, i64, i64, f32, f32, c_int, p, p, p]),       # multi-line, const T *, stream
+        "xpa_gather_num_partials": (i64, [i64]),                                            # int64_t return
+        "xpa_adam_sched_entry": (None, [f32, f32, f32, i64, p]),                            # void return
+        "xpa_conv_wgrad_force_stream": (None, [c_int]),
+        "xpa_per_store": (c_int, [p, p, p, i64, i64, i64, c_double, p]),                    # double
+        "xpa_synthbox_step": (c_int, [i64, i64, p, u32, i32, f32, f32, f32, p, i64] + [p] * 10),   # uint32_t, int32_t
+        "xpa_small_mlp_update": (c_int, [p, p]),                                            # struct pointer
+        "xpa_rollout_step_workspace": (i64, [i64, i64, c_int, p]),                          # int64_t * out-parameter
+        "xpa_colsum_finalize_batch": (c_int, [c_int, p, p, p, p, p]),                       # T *const *
+    }
+    for name, want in pins.items():
+        assert _lib.SIGNATURES[name] == want, name
+    assert len(_lib.SIGNATURES) == len(_header_functions())
+
+
+def _bundled_clang():
+    """The clang beside the hipcc build_library uses (host compiles only here)."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    out = subprocess.run([hipcc, "--version"], capture_output=True, text=True, check=True).stdout
+    return os.path.join(re.search(r"InstalledDir:\s*(\S+)", out).group(1), "clang")
+
+
+def test_struct_layout_matches_compiler(lib, tmp_path):
+    """sizeof and every offsetof of the two argument structs, as the C compiler lays the header out, against the
+    ctypes classes derived from the same header."""
+    import ctypes
+    classes = (_lib.XpaSmallMlpArgs, _lib.XpaSmallRolloutArgs)
+    assert [len(c._fields_) for c in classes] == [59, 69]
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "xuanpolicy_amd.h"', "int main(void) {"]
+    for c in classes:
+        lines.append('    printf("%%zu\\n", sizeof(%s));' % c.__name__)
+        lines += ['    printf("%%zu\\n", offsetof(%s, %s));' % (c.__name__, n) for n, _ in c._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    exe = str(tmp_path / "layout")
+    subprocess.run([_bundled_clang(), "-I", os.path.dirname(_lib.HEADER), "-o", exe, str(src)], check=True)
+    got = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    want = []
+    for c in classes:
+        want += [ctypes.sizeof(c)] + [getattr(c, n).offset for n, _ in c._fields_]
+    assert got == want
+    assert (got[0], got[60]) == (400, 472)
+
+
+def test_parser_refuses_what_it_does_not_know():
+    with pytest.raises(_lib.XpaError, match="xpa_x"):
+        _lib.parse_header("int xpa_x(long double y);")
+    with pytest.raises(_lib.XpaError, match="xpa_y"):
+        _lib.parse_header("int xpa_y(int (*callback)(int));")
+    with pytest.raises(_lib.XpaError, match="xpa_z"):
+        _lib.parse_header("size_t xpa_z(void);")
+    with pytest.raises(_lib.XpaError, match="XpaThing"):
+        _lib.parse_header("typedef struct XpaThing { int a, b; size_t n; } XpaThing;")
+    sig, structs, consts = _lib.parse_header("#define XPA_N 7\ntypedef struct XpaOk { int a, b; const float *p, *q; } XpaOk;\n"
+                                             "void xpa_ok(const XpaOk *a, /* c */ unsigned n); // d\n")
+    import ctypes
+    assert sig == {"xpa_ok": (None, [ctypes.c_void_p, ctypes.c_uint])} and consts == {"XPA_N": 7}
+    assert structs["XpaOk"]._fields_ == [("a", ctypes.c_int), ("b", ctypes.c_int), ("p", ctypes.c_void_p),
+                                         ("q", ctypes.c_void_p)]
+
+
+def test_call_names_the_entry_point_that_failed(lib):
+    with pytest.raises(_lib.XpaError, match=r"xpa_gae_scan failed.*invalid argument"):
+        _lib.call(lib.xpa_gae_scan, None, None, None, None, None, -1, 4, 0.99, 0.95, 1, None, None, None)
+
+
+def test_constants_come_from_the_header(lib):
+    assert _lib.ABI_VERSION == lib.xpa_abi_version() == 4
+    assert _lib.COLSUM_TICKET_INTS == 4096
+
+
 def test_ops_refuse_cpu_tensors():
     from xuanpolicy_amd import ops
     x = torch.zeros(4, 8)

@@ -564,6 +564,42 @@ def test_rollout_post_deferred_slot_rows(slot_src):
         np.testing.assert_allclose(so[k * N + n], row, rtol=1e-6, atol=1e-6)
 
 
+def test_rollout_post_deferred_equals_norm_form_with_identity_statistics():
+    """ops.rollout_post's 4-element deferred form (xpa_rollout_post_deferred: the kept rows arrive normalised) against
+    its 8-element form (xpa_rollout_post_deferred_norm, the same kernel with the normalisation folded in) under
+    obs_mean = 0, obs_var = 1 and a clip no row reaches: (x - 0) / (sqrt(1) + 1e-8f) = x / 1.0f = x exactly in f32, so
+    every buffer, slot, statistic and the cursor must agree bit for bit.  A few envs, two slots, row-strided sources,
+    truncations before the last step and terminals."""
+    from xuanpolicy_amd import ops
+    rng = np.random.default_rng(9)
+    N, T, D, S = 5, 4, 3, 2
+    steps = [(rng.normal(0, 1, N).astype(np.float32), rng.random(N) < 0.2, (rng.random(N) < 0.4) & (t < T - 1),
+              rng.normal(0, 1, (N, D + 2)).astype(np.float32)) for t in range(T)]
+    runs = []
+    for form in ("plain", "norm"):
+        st = {"ret_mean": torch.zeros(1, device=DEV), "ret_var": torch.ones(1, device=DEV),
+              "ret_count": torch.full((1,), 1e-4, dtype=torch.float64, device=DEV), "returns": torch.zeros(N, device=DEV),
+              "buf_rew": torch.zeros(N, T, device=DEV), "buf_term": torch.zeros(N, T, device=DEV),
+              "buf_closed": torch.zeros(N, T, dtype=torch.uint8, device=DEV), "buf_boot": torch.zeros(N, T, device=DEV),
+              "cursor": ops.new_cursor(DEV), "slot_obs": torch.zeros(S * N, D, device=DEV),
+              "slot_t": torch.full((S * N,), -1, dtype=torch.int32, device=DEV),
+              "overflow": torch.zeros(1, dtype=torch.int32, device=DEV)}
+        boot_norm = torch.zeros(N, D, device=DEV)
+        for rew, term, trunc, fin in steps:
+            deferred = (_d(fin)[:, :D], st["slot_obs"], st["slot_t"], st["overflow"])
+            if form == "norm":
+                deferred += (torch.zeros(D, device=DEV), torch.ones(D, device=DEV), 1e30, boot_norm)
+            ops.rollout_post(_d(rew), _d(term.astype(np.uint8)), _d(trunc.astype(np.uint8)), None, st["cursor"],
+                             st["ret_mean"], st["ret_var"], st["ret_count"], st["returns"], st["buf_rew"],
+                             st["buf_term"], st["buf_closed"], st["buf_boot"], 0.99, deferred=deferred)
+        runs.append({k: _h(v) for k, v in st.items()})
+        if form == "norm":
+            np.testing.assert_array_equal(_h(boot_norm), steps[-1][3][:, :D])
+    assert (runs[0]["slot_t"] >= 0).sum() >= 2 and runs[0]["buf_closed"].any()
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
+
+
 # ---------------------------------------------------------------------------------------------- K9
 @pytest.mark.parametrize("max_norm", [0.5, None, 0.0, 1e9])
 def test_fused_clip_adam_matches_torch(max_norm):

@@ -8,6 +8,7 @@ There is no CPU fallback: every entry point raises if the library is missing or 
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch  # noqa: F401  (must be loaded first: see module docstring)
@@ -20,302 +21,69 @@ SOURCES = ["gae.hip", "loss.hip", "rollout.hip", "optim.hip", "mlp.hip", "head.h
            "classic.hip", "dqn.hip", "conv.hip", "igemm.hip", "smallmlp.hip", "sgemm3.hip"]
 HEADER = os.path.join(REPO_DIR, "include", "xuanpolicy_amd.h")
 
-ABI_VERSION = 4
-COLSUM_TICKET_INTS = 4096   # include/xuanpolicy_amd.h XPA_COLSUM_TICKET_INTS (ABI 4)
 
-c_i32, c_i64, c_u32, c_f32, c_p = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p
-
-class XpaSmallMlpArgs(ctypes.Structure):
-    """include/xuanpolicy_amd.h XpaSmallMlpArgs (K30), field for field."""
-    _fields_ = ([(n, ctypes.c_int) for n in ("batch", "d_in", "h0", "h1", "h2", "k", "act_code", "algo", "use_advnorm",
-                                             "n_sched")]
-                + [(n, ctypes.c_float) for n in ("slope", "clip_range", "vf_coef", "ent_coef", "max_norm", "beta1",
-                                                 "beta2", "eps")]
-                + [("obs", ctypes.c_void_p), ("obs_ld", ctypes.c_int64), ("idx", ctypes.c_void_p),
-                   ("n_rows", ctypes.c_int64)]
-                + [(n, ctypes.c_void_p) for n in ("actions", "old_logp", "adv", "ret", "W0", "b0", "W1", "b1", "W2",
-                                                  "b2", "Wa", "ba", "Wc", "bc", "gW0", "gb0", "gW1", "gb1", "gW2",
-                                                  "gb2", "gWa", "gba", "gWc", "gbc", "param", "grad", "exp_avg",
-                                                  "exp_avg_sq")]
-                + [("n", ctypes.c_int64), ("sched", ctypes.c_void_p), ("cursor", ctypes.c_void_p),
-                   ("scalars", ctypes.c_void_p), ("total_norm_out", ctypes.c_void_p), ("stamps", ctypes.c_void_p),
-                   ("n_groups", ctypes.c_int), ("grad_part", ctypes.c_void_p), ("loss_part", ctypes.c_void_p)])
+class XpaError(RuntimeError):
+    pass
 
 
-class XpaSmallRolloutArgs(ctypes.Structure):
-    """include/xuanpolicy_amd.h XpaSmallRolloutArgs (K32), field for field."""
-    _fields_ = ([(n, ctypes.c_int) for n in ("n_envs", "horizon", "steps", "d_in", "h0", "h1", "h2", "k", "act_code",
-                                             "use_obsnorm", "n_slots", "mask_returns", "use_rewnorm",
-                                             "max_episode_steps", "slot_reset_obs")]
-                + [(n, ctypes.c_float) for n in ("slope", "obs_clip", "gamma", "rew_range")]
-                + [("seed", ctypes.c_uint32), ("env_seed", ctypes.c_uint32)]
-                + [(n, ctypes.c_void_p) for n in ("W0", "b0", "W1", "b1", "W2", "b2", "Wa", "ba", "Wc", "bc",
-                                                  "obs_mean", "obs_var", "obs_count", "obs_norm")]
-                + [("ld_norm", ctypes.c_int64)]
-                + [(n, ctypes.c_void_p) for n in ("buf_obs", "buf_act", "buf_logp", "buf_val", "buf_rew", "buf_term",
-                                                  "buf_closed", "buf_boot", "act_in")]
-                + [("ld_act", ctypes.c_int64), ("env_state", ctypes.c_void_p), ("env_obs", ctypes.c_void_p),
-                   ("ld_obs", ctypes.c_int64)]
-                + [(n, ctypes.c_void_p) for n in ("final_obs", "env_rew", "env_term", "env_trunc", "ep_step",
-                                                  "ep_index", "ep_score", "ep_last_score", "ep_last_len", "returns",
-                                                  "ret_mean", "ret_var", "ret_count", "slot_obs", "slot_t", "overflow",
-                                                  "boot_norm")]
-                + [("ld_boot", ctypes.c_int64), ("cursor", ctypes.c_void_p), ("stamps", ctypes.c_void_p)])
+# The type spellings include/xuanpolicy_amd.h may use for scalars; any declarator with a `*` is a c_void_p.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "unsigned": ctypes.c_uint, "uint8_t": ctypes.c_uint8, "float": ctypes.c_float, "double": ctypes.c_double,
+            "xpa_stream_t": ctypes.c_void_p}
 
 
-# name -> (restype, argtypes); mirrors include/xuanpolicy_amd.h one-for-one.
-SIGNATURES = {
-    "xpa_abi_version": (ctypes.c_int, []),
-    "xpa_gae_scan": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_f32, ctypes.c_int, c_p, c_p, c_p]),
-    "xpa_gae_scan_compact": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_f32, ctypes.c_int, c_p, c_p,
-                                            c_p, c_p, c_p, c_p]),
-    "xpa_gae_scan_value": (ctypes.c_int, [c_p, c_p, c_p, c_p, ctypes.c_int, c_p, c_i64, c_f32, c_p, c_p, c_i64, c_i64,
-                                          c_i64, c_f32, c_f32, ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_stream_copy_timed": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p]),
-    "xpa_gae_scan_timed": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_f32, c_f32, ctypes.c_int, c_p, c_p,
-                                          c_p, c_p, c_p]),
-    "xpa_dispatch_floor_timed": (ctypes.c_int, [c_p, c_p, c_p]),
-    "xpa_random_permutation": (ctypes.c_int, [c_i64, c_u32, c_u32, c_p, c_p]),
-    "xpa_gather_num_partials": (c_i64, [c_i64]),
-    "xpa_gather_minibatch": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_loss_num_partials": (c_i64, [c_i64]),
-    "xpa_loss_partial_width": (c_i64, [c_i64]),
-    "xpa_policy_loss_fwd_bwd": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p,
-                                               c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_f32, c_p, c_p, c_p, c_p]),
-    "xpa_policy_loss_finalize": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_f32, c_f32,
-                                                c_p, c_p, c_p]),
-    "xpa_rms_num_partials": (c_i64, [c_i64]),
-    "xpa_rms_partials": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "xpa_rms_update": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_rms_merge": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
-    "xpa_obs_normalize": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "xpa_rollout_sample": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_u32, c_f32, c_p, c_p,
-                                          c_p, c_p, c_i64, c_p]),
-    "xpa_synthbox_step": (ctypes.c_int, [c_i64, c_i64, c_p, c_u32, c_i32, c_f32, c_f32, c_f32, c_p, c_i64, c_p, c_p,
-                                         c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_cartpole_step": (ctypes.c_int, [c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                         c_p, c_u32, c_i32, c_p]),
-    "xpa_dqn_td_loss": (ctypes.c_int, [c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_f32, c_p, c_i64, c_p, c_p,
-                                       c_p, c_p]),
-    "xpa_rollout_post_num_blocks": (c_i64, [c_i64]),
-    "xpa_rollout_post": (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                        c_f32, ctypes.c_int, ctypes.c_int, c_f32, ctypes.c_int, c_p, c_p, c_p]),
-    "xpa_act_bwd_num_partials": (c_i64, [c_i64]),
-    "xpa_act_bwd_colsum": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p, c_p]),
-    "xpa_colsum_finalize": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_p]),
-    "xpa_frames_to_f32": (ctypes.c_int, [c_p, c_i64, c_p, c_p]),
-    "xpa_conv_dgrad_s2k": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64,
-                                           c_i64, c_p, c_p]),
-    "xpa_conv1_u8_wgrad_num_partials": (c_i64, []),
-    "xpa_conv1_u8_wgrad_act": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_f32, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                                               c_i64, c_i64, c_p, c_p, c_p]),
-    "xpa_conv1_u8_wgrad": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "xpa_conv1_form": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_conv_igemm_form": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_conv1_u8_fwd": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p,
-                                         c_i64, c_f32, c_p, c_p]),
-    "xpa_bias_act": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_p, c_f32, c_p]),
-    "xpa_act_bwd_bias_num_partials": (c_i64, [c_i64, c_i64]),
-    "xpa_act_bwd_bias": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p, c_p]),
-    "xpa_global_maxpool": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
-    "xpa_maxpool_act_bwd_bias": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f32, c_p, c_p,
-                                                c_p, c_p]),
-    "xpa_head_bwd_num_partials": (c_i64, [c_i64]),
-    "xpa_head_backward": (ctypes.c_int, [ctypes.c_int, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_f32, c_p, c_p, c_p,
-                                         c_p, c_p]),
-    "xpa_head_fused_num_partials": (c_i64, [c_i64]),
-    "xpa_head_fused_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_i64, c_p, c_p,
-                                            c_p,
-                                            c_f32, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_p, c_p,
-                                            c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_fused_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_f32, c_p, c_i64, c_p, c_f32,
-                                             c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_rollout_policy_head": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p,
-                                               c_f32, c_p, c_p, c_p, c_p, c_p, c_p, c_u32, c_f32, c_p, c_p, c_p, c_p,
-                                               c_i64, c_p]),
-    "xpa_rollout_policy_head_synthbox": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_f32,
-                                                        c_p, c_p, c_p, c_p, c_p, c_p, c_u32, c_f32, c_p, c_p, c_p,
-                                                        c_i64, c_p, c_u32, ctypes.c_int32, c_f32, c_f32, c_f32, c_p,
-                                                        c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_value_head": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p]),
-    "xpa_colsum_batch_tiles": (c_i64, [ctypes.c_int, c_p, c_p]),
-    "xpa_colsum_finalize_batch_sq": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_colsum_finalize_batch_sq_loss": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int,
-                                                         ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_f32, c_f32, c_p,
-                                                         c_p, c_p]),
-    "xpa_policy_loss_finalize_sq": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_f32, c_f32,
-                                                   c_p, c_p, c_p, c_p]),
-    "xpa_clip_adam_step_partials": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_f32, c_f32, c_f32, c_f32,
-                                                   c_f32, c_i64, c_p, c_p]),
-    "xpa_clip_adam_step_sched": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f32, c_f32, c_f32, c_f32, c_p, c_i64,
-                                                c_p, c_p, c_p]),
-    "xpa_adam_sched_entry": (None, [c_f32, c_f32, c_f32, c_i64, c_p]),
-    "xpa_small_mlp_lds_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
-    "xpa_small_mlp_update": (ctypes.c_int, [c_p, c_p]),
-    "xpa_small_rollout_lds_floats": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
-    "xpa_small_rollout_cartpole": (ctypes.c_int, [c_p, c_p]),
-    "xpa_colsum_finalize_batch": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_per_store": (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, ctypes.c_double, c_p]),
-    "xpa_per_update_priorities": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, ctypes.c_double,
-                                                 c_p, c_p]),
-    "xpa_per_sample": (ctypes.c_int, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_u32, c_u32, ctypes.c_double,
-                                      ctypes.c_int, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_store_column": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
-    "xpa_synthatari_step": (ctypes.c_int, [c_i64, c_i64, c_p, c_i64, c_u32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                           c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_synthatari_reset": (ctypes.c_int, [c_i64, c_u32, c_p, c_p, c_p]),
-    "xpa_rollout_post_deferred_norm": (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p,
-                                                      c_p, c_f32,
-                                                      c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                                      c_p, c_p, c_p, c_f32, ctypes.c_int, ctypes.c_int, c_f32,
-                                                      ctypes.c_int, c_p, c_p, c_p]),
-    "xpa_rollout_post_deferred": (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p,
-                                                 c_p, c_p,
-                                                 c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, ctypes.c_int, ctypes.c_int,
-                                                 c_f32, ctypes.c_int, c_p, c_p, c_p]),
-    "xpa_conv_igemm_ok": (ctypes.c_int, [c_i64, c_i64, c_i64]),
-    "xpa_conv_fwd": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64,
-                                    c_f32, c_p, c_p]),
-    "xpa_conv_dgrad_num_partials": (c_i64, [c_i64, c_i64, c_i64]),
-    "xpa_conv_dgrad": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                                      ctypes.c_int, c_p, c_f32, c_p, c_p, c_p]),
-    "xpa_conv_wgrad_num_partials": (c_i64, []),
-    "xpa_conv_wgrad_force_stream": (None, [ctypes.c_int]),
-    "xpa_conv_wgrad": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_f32, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                                      c_i64, c_p, c_p, c_p]),
-    "xpa_rollout_bootstrap_fixup": (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p]),
-    "xpa_thin_bwd_num_partials": (c_i64, [c_i64]),
-    "xpa_thin_linear_act_fwd_gather": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_p,
-                                                       c_f32, c_p, c_i64, c_p, c_p, c_p, c_p]),
-    "xpa_thin_linear_act_bwd_gather": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p,
-                                                       c_i64, c_i64, c_f32, c_p, c_p, c_p]),
-    "xpa_thin_linear_act_fwd_norm": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_f32,
-                                                    c_p, c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "xpa_thin_linear_act_fwd": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_f32, c_p, c_i64,
-                                               c_p]),
-    "xpa_thin_linear_act_bwd": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_f32,
-                                               c_p, c_p, c_p]),
-    "xpa_head_gemm_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64, c_p,
-                                           c_p, c_i64, c_p, c_p, c_f32, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_f32,
-                                           c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32, c_p,
-                                            c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_ws_grid": (c_i64, [c_i64]),
-    "xpa_head_gemm_ws_probe": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_lds_poison": (ctypes.c_int, [c_p]),
-    "xpa_head_gemm_ws_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64,
-                                              c_p, c_p, c_i64, c_p, c_p, c_f32, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                              c_f32, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_ws_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32,
-                                               c_p, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64,
-                                              c_p, c_p, c_i64, c_p, c_p, c_f32, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                              c_f32, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32,
-                                               c_p, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3p_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64,
-                                              c_p, c_p, c_i64, c_p, c_p, c_f32, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                              c_f32, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3p_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32,
-                                               c_p, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3q_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64,
-                                              c_p, c_p, c_i64, c_p, c_p, c_f32, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                              c_f32, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3q_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32,
-                                               c_p, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_trunk_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64,
-                                                 c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32, c_p,
-                                                 c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_p, c_p, c_p, c_p,
-                                                 c_p, c_i64, c_p]),
-    "xpa_head_gemm_trunk_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_f32, c_p,
-                                                  c_i64, c_p, c_p, c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_f32, c_p,
-                                                  c_p, c_p, c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3r_actor": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64, c_i64, c_p, c_i64,
-                                               c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_f32,
-                                               c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_f32, c_f32, c_p, c_p, c_p,
-                                               c_p, c_p, c_i64, c_p]),
-    "xpa_head_gemm_s3r_critic": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_f32, c_p, c_p,
-                                                c_i64, c_p, c_p, c_f32, c_p, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p,
-                                                c_i64, c_p]),
-    "xpa_s3_gemm_trunk_bwd_sign": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, ctypes.c_int,
-                                                  c_f32, c_p, c_p, c_p]),
-    "xpa_thin_linear_act_fwd_gather_sign": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p,
-                                                           c_p, c_f32, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_thin_probe": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_head_store_probe": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_head_stagger": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_s3_probe": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_head_gemm_s3q_critic_mask": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p,
-                                                     c_f32, c_p, c_i64, c_p, c_f32, c_p, c_p, c_p, c_p, c_p, c_i64, c_p,
-                                                     c_p, c_p]),
-    "xpa_s3_split_batch_scaled": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32,
-                                                 c_p]),
-    "xpa_s3_gemm_trunk_bwd_crit": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64,
-                                                  c_i64, ctypes.c_int, c_f32, c_p, c_p, c_p]),
-    "xpa_rollout_post_deferred_norm_rms": (ctypes.c_int, [c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i64,
-                                                          c_p, c_p, c_p, c_f32, c_p, c_i64, c_p, c_p, c_i64, c_p, c_p,
-                                                          c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, ctypes.c_int,
-                                                          ctypes.c_int, c_f32, ctypes.c_int, c_p, c_p, c_p, c_i64, c_p,
-                                                          c_p]),
-    "xpa_s3_gemm_bias_act_rows": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, ctypes.c_int,
-                                                 c_f32, c_p, c_p]),
-    "xpa_s3_wgrad_rows": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "xpa_s3_gemm_rows_pair": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_p]),
-    "xpa_s3_split_batch_padded": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_s3_gemm_bias_act": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_p, ctypes.c_int, c_f32, c_p,
-                                            c_p]),
-    "xpa_s3_gemm_trunk_bwd_dz": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, ctypes.c_int, c_f32, c_p, c_i64,
-                                                c_p, c_p]),
-    "xpa_s3_gemm_trunk_bwd_crit_dz": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_i64,
-                                                     ctypes.c_int, c_f32, c_p, c_i64, c_p, c_p]),
-    "xpa_gather_minibatch_pitched": (ctypes.c_int, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
-    "xpa_colsum_finalize_batch_map": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_int,
-                                                     ctypes.c_int, c_i64, c_i64, c_p, c_i64, c_f32, c_f32, c_p, c_p,
-                                                     c_p]),
-    "xpa_s3_wgrad_pair_slices": (ctypes.c_int, [c_i64, c_p, c_p, c_p, c_p]),
-    "xpa_s3_wgrad_pair_tune": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_s3_wgrad_pair": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p, c_f32, c_i64, c_i64, c_i64,
-                                         c_i64, c_p, c_p, c_p]),
-    "xpa_s3_split_bytes": (c_i64, [c_i64, c_i64]),
-    "xpa_s3_split_b": (ctypes.c_int, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "xpa_s3_split_batch": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "xpa_s3_gemm": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p]),
-    "xpa_s3_gemm_group": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p]),
-    "xpa_s3_gemm_group_act_num_partials": (c_i64, [ctypes.c_int, c_i64]),
-    "xpa_s3_gemm_group_act": (ctypes.c_int, [ctypes.c_int, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, ctypes.c_int,
-                                             c_f32, c_i64, c_p, c_p]),
-    "xpa_s3_wgrad_num_slices": (c_i64, [c_i64, c_i64]),
-    "xpa_s3_gemm_trunk_bwd_num_partials": (c_i64, [c_i64]),
-    "xpa_s3_gemm_trunk_bwd": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, ctypes.c_int,
-                                             c_f32, c_p, c_p, c_p]),
-    "xpa_s3_wgrad": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "xpa_s3_wgrad_padded": (ctypes.c_int, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p]),
-    "xpa_rollout_step_workspace": (c_i64, [c_i64, c_i64, ctypes.c_int, c_p]),
-    "xpa_k14f_probe": (ctypes.c_int, [ctypes.c_int]),
-    "xpa_s3_gemm_value": (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, ctypes.c_int, c_f32, c_p, c_p, c_p]),
-    "xpa_s3_gemm_rows_pair_trunk": (ctypes.c_int, [ctypes.c_int, c_p, c_i64, c_i64, c_p, c_p, c_f32, c_p, c_p, c_f32,
-                                                   c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64,
-                                                   c_p]),
-    "xpa_rollout_step_synthbox": (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_f32,
-                                                 c_p, c_p, c_p, c_p, c_p, c_p, c_u32, c_f32, c_p, c_p, c_p,
-                                                 c_i64, c_p, c_u32, ctypes.c_int32, c_f32, c_f32, c_f32, c_p,
-                                                 c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                                                 c_p, c_p, c_i64, c_p, ctypes.c_int, c_p, c_p, c_p, c_f32, c_p, c_i64,
-                                                 c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, ctypes.c_int,
-                                                 ctypes.c_int, c_f32, ctypes.c_int, c_p, c_p, c_p]),
-    "xpa_grad_norm_num_partials": (c_i64, [c_i64]),
-    "xpa_clip_adam_step": (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_p, c_f32, c_f32, c_f32, c_f32, c_f32, c_i64, c_p,
-                                          c_p]),
-}
+def _ctype(type_name, declarator, where):
+    """ctypes type of `type_name declarator` (declarator: `name`, `*name`, `**name`); raises rather than guess."""
+    name = declarator.replace("*", " ").strip()
+    if not name.isidentifier() or ("*" not in declarator and type_name not in _SCALARS):
+        raise XpaError("cannot bind '%s %s' in %s" % (type_name, declarator, where))
+    return name, (ctypes.c_void_p if "*" in declarator else _SCALARS[type_name])
+
+
+def parse_header(text):
+    """Parse a C header in the subset include/xuanpolicy_amd.h is written in.
+
+    Returns (signatures, structs, constants): name -> (restype, argtypes) for every `ret xpa_name(args);`, a
+    ctypes.Structure subclass for every `typedef struct Name { ... } Name;` and the integer `#define XPA_*`s."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(XPA_\w+)[ \t]+(\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$|\bconst\b", " ", text, flags=re.M)   # const does not change a binding
+    structs = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text):
+        fields = []
+        for line in filter(None, (ln.strip() for ln in body.split(";"))):
+            m = re.fullmatch(r"(\w+)\s+(.+)", line, re.S)
+            if not m:
+                raise XpaError("cannot bind '%s' in struct %s" % (line, name))
+            fields += [_ctype(m[1], d.strip(), "struct " + name) for d in m[2].split(",")]
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    signatures = {}
+    for ret, name, args in re.findall(r"(\w+)\s+(xpa_\w+)\s*\(([^()]*)\)\s*;", text):
+        if ret != "void" and ret not in _SCALARS:
+            raise XpaError("cannot bind return type '%s' of %s" % (ret, name))
+        argtypes = []
+        for arg in ([] if args.strip() == "void" else args.split(",")):
+            m = re.fullmatch(r"\s*(\w+)\s+([*\s]*\w+)\s*", arg)
+            if not m:
+                raise XpaError("cannot bind '%s' in %s" % (" ".join(arg.split()), name))
+            argtypes.append(_ctype(m[1], m[2], name)[1])
+        signatures[name] = (None if ret == "void" else _SCALARS[ret], argtypes)
+    missed = set(re.findall(r"\b(xpa_\w+)\s*\(", text)) - set(signatures)
+    if missed:
+        raise XpaError("cannot parse the declaration of %s" % ", ".join(sorted(missed)))
+    return signatures, structs, constants
+
+
+# The header is the only statement of the ABI: name -> (restype, argtypes), the argument structs and the constants.
+with open(HEADER) as _f:
+    SIGNATURES, _structs, _constants = parse_header(_f.read())
+XpaSmallMlpArgs, XpaSmallRolloutArgs = _structs["XpaSmallMlpArgs"], _structs["XpaSmallRolloutArgs"]
+ABI_VERSION, COLSUM_TICKET_INTS = _constants["XPA_ABI_VERSION"], _constants["XPA_COLSUM_TICKET_INTS"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall"]
 OBJ_DIR = os.path.join(PKG_DIR, "_obj")
 
 _lib = None
-
-
-class XpaError(RuntimeError):
-    pass
 
 
 def _digest(paths, extra=""):
@@ -403,3 +171,8 @@ def load(path=None):
 def check(rc, what):
     if rc != 0:
         raise XpaError("%s failed: hipError %d%s" % (what, rc, " (invalid argument)" if rc == 1 else ""))
+
+
+def call(fn, *args):
+    """Call a status-returning entry point; a non-zero status raises, named after the symbol that ran."""
+    check(fn(*args), fn.__name__)

@@ -504,8 +504,7 @@ class _OnPolicyAgent:
 
     def _small_rollout_launch(self, a, steps):
         a.steps = int(steps)
-        _lib.check(ops.lib().xpa_small_rollout_cartpole(ctypes.byref(a), ops._stream(self.device)),
-                   "xpa_small_rollout_cartpole")
+        _lib.call(ops.lib().xpa_small_rollout_cartpole, ctypes.byref(a), ops._stream(self.device))
 
     def _rollout_step_device(self):
         env = self.envs

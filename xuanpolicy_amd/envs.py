@@ -134,13 +134,11 @@ class SynthBoxVecEnv:
     def step_device(self):
         """One env step for all envs from the action already written into act_in."""
         torch.mm(self.X, self.Wcat_t, out=self.pre)
-        rc = ops.lib().xpa_synthbox_step(self.num_envs, self.D, ops._p(self.pre), self.noise_seed,
-                                         self.max_episode_steps, NOISE, TERM_THRESH, RESET_SCALE, ops._p(self.X),
-                                         self.X.stride(0), ops._p(self.final_obs), ops._p(self.rew),
-                                         ops._p(self.term), ops._p(self.trunc), ops._p(self.ep_step),
-                                         ops._p(self.ep_index), ops._p(self.ep_score), ops._p(self.ep_last_score),
-                                         ops._p(self.ep_last_len), ops._stream(self.device))
-        _lib.check(rc, "xpa_synthbox_step")
+        _lib.call(ops.lib().xpa_synthbox_step, self.num_envs, self.D, ops._p(self.pre), self.noise_seed,
+                  self.max_episode_steps, NOISE, TERM_THRESH, RESET_SCALE, ops._p(self.X), self.X.stride(0),
+                  ops._p(self.final_obs), ops._p(self.rew), ops._p(self.term), ops._p(self.trunc), ops._p(self.ep_step),
+                  ops._p(self.ep_index), ops._p(self.ep_score), ops._p(self.ep_last_score), ops._p(self.ep_last_len),
+                  ops._stream(self.device))
 
     def step(self, actions):
         """VecEnv contract (gym_vec_env.py:201-212): returns host copies of (obs, rew, term, trunc, infos)
@@ -239,20 +237,16 @@ class SynthAtariVecEnv:
             t.zero_()
         self.lives.fill_(5)
         self.paddle.fill_(38)
-        _lib.check(ops.lib().xpa_synthatari_reset(self.num_envs, self.noise_seed, ops._p(self.stack),
-                                                  ops._p(self.ep_index), ops._stream(self.device)),
-                   "xpa_synthatari_reset")
+        _lib.call(ops.lib().xpa_synthatari_reset, self.num_envs, self.noise_seed, ops._p(self.stack),
+                  ops._p(self.ep_index), ops._stream(self.device))
         return self.stack.clone(), [{} for _ in range(self.num_envs)]
 
     def step_device(self):
-        rc = ops.lib().xpa_synthatari_step(self.num_envs, self.n_actions, ops._p(self._act), self._act.stride(0),
-                                           self.noise_seed, self.max_episode_steps, ops._p(self.stack),
-                                           ops._p(self.final_obs), ops._p(self.rew), ops._p(self.term),
-                                           ops._p(self.trunc), ops._p(self.ep_step), ops._p(self.ep_index),
-                                           ops._p(self.lives), ops._p(self.paddle), ops._p(self.ep_score),
-                                           ops._p(self.ep_last_score), ops._p(self.ep_last_len),
-                                           ops._p(self.err), ops._stream(self.device))
-        _lib.check(rc, "xpa_synthatari_step")
+        _lib.call(ops.lib().xpa_synthatari_step, self.num_envs, self.n_actions, ops._p(self._act), self._act.stride(0),
+                  self.noise_seed, self.max_episode_steps, ops._p(self.stack), ops._p(self.final_obs), ops._p(self.rew),
+                  ops._p(self.term), ops._p(self.trunc), ops._p(self.ep_step), ops._p(self.ep_index),
+                  ops._p(self.lives), ops._p(self.paddle), ops._p(self.ep_score), ops._p(self.ep_last_score),
+                  ops._p(self.ep_last_len), ops._p(self.err), ops._stream(self.device))
 
     def step(self, actions):
         """DummyVecEnv_Atari contract (gym_vec_env.py:201-212): host copies of (obs, rew, term, trunc, infos);
@@ -353,13 +347,11 @@ class CartPoleVecEnv:
         return False
 
     def step_device(self):
-        rc = ops.lib().xpa_cartpole_step(self.num_envs, ops._p(self._act), self._act.stride(0), ops._p(self.state),
-                                         ops._p(self._obs), self._obs.stride(0), ops._p(self.final_obs),
-                                         ops._p(self.rew), ops._p(self.term), ops._p(self.trunc),
-                                         ops._p(self.ep_step), ops._p(self.ep_index), ops._p(self.ep_score),
-                                         ops._p(self.ep_last_score), ops._p(self.ep_last_len), self.noise_seed,
-                                         self.max_episode_steps, ops._stream(self.device))
-        _lib.check(rc, "xpa_cartpole_step")
+        _lib.call(ops.lib().xpa_cartpole_step, self.num_envs, ops._p(self._act), self._act.stride(0),
+                  ops._p(self.state), ops._p(self._obs), self._obs.stride(0), ops._p(self.final_obs), ops._p(self.rew),
+                  ops._p(self.term), ops._p(self.trunc), ops._p(self.ep_step), ops._p(self.ep_index),
+                  ops._p(self.ep_score), ops._p(self.ep_last_score), ops._p(self.ep_last_len), self.noise_seed,
+                  self.max_episode_steps, ops._stream(self.device))
 
     def step(self, actions):
         """VecEnv contract (gym_vec_env.py:201-212): host copies of (obs, rew, term, trunc, infos)."""

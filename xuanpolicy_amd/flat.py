@@ -147,18 +147,14 @@ class FusedClipAdam:
         lr = float(lr) if not isinstance(lr, torch.Tensor) else float(lr.item())
         if sq is not None:
             buf, count = sq
-            rc = ops.lib().xpa_clip_adam_step_partials(
-                ops._p(self.fs.param), ops._p(self.fs.flat), ops._p(self.exp_avg), ops._p(self.exp_avg_sq),
-                self.fs.numel, ops._p(buf), int(count), max_norm, lr, float(b1),
-                float(b2), float(g["eps"]), self.step_count, ops._p(self.total_norm), ops._stream(self.fs.param.device))
-            _lib.check(rc, "xpa_clip_adam_step_partials")
+            _lib.call(ops.lib().xpa_clip_adam_step_partials, ops._p(self.fs.param), ops._p(self.fs.flat),
+                      ops._p(self.exp_avg), ops._p(self.exp_avg_sq), self.fs.numel, ops._p(buf), int(count), max_norm,
+                      lr, float(b1), float(b2), float(g["eps"]), self.step_count, ops._p(self.total_norm),
+                      ops._stream(self.fs.param.device))
         else:
-            rc = ops.lib().xpa_clip_adam_step(ops._p(self.fs.param), ops._p(self.fs.flat), ops._p(self.exp_avg),
-                                              ops._p(self.exp_avg_sq), self.fs.numel, ops._p(self.partials),
-                                              max_norm, lr, float(b1), float(b2),
-                                              float(g["eps"]), self.step_count, ops._p(self.total_norm),
-                                              ops._stream(self.fs.param.device))
-            _lib.check(rc, "xpa_clip_adam_step")
+            _lib.call(ops.lib().xpa_clip_adam_step, ops._p(self.fs.param), ops._p(self.fs.flat), ops._p(self.exp_avg),
+                      ops._p(self.exp_avg_sq), self.fs.numel, ops._p(self.partials), max_norm, lr, float(b1), float(b2),
+                      float(g["eps"]), self.step_count, ops._p(self.total_norm), ops._stream(self.fs.param.device))
         self._step_t.fill_(float(self.step_count))
         self.optimizer._opt_called = True  # the LR scheduler checks that an optimizer step happened
 
@@ -251,12 +247,10 @@ class FusedClipAdam:
         max_norm = -1.0 if max_norm is None else float(max_norm)
         g = self.optimizer.param_groups[0]
         b1, b2 = g["betas"]
-        rc = ops.lib().xpa_clip_adam_step_sched(ops._p(self.fs.param), ops._p(self.fs.flat), ops._p(self.exp_avg),
-                                                ops._p(self.exp_avg_sq), self.fs.numel, ops._p(self.partials),
-                                                max_norm, float(b1), float(b2), float(g["eps"]), ops._p(self._sched),
-                                                self.SCHED_WINDOW, ops._p(self._cursor), ops._p(self.total_norm),
-                                                ops._stream(self.fs.param.device))
-        _lib.check(rc, "xpa_clip_adam_step_sched")
+        _lib.call(ops.lib().xpa_clip_adam_step_sched, ops._p(self.fs.param), ops._p(self.fs.flat), ops._p(self.exp_avg),
+                  ops._p(self.exp_avg_sq), self.fs.numel, ops._p(self.partials), max_norm, float(b1), float(b2),
+                  float(g["eps"]), ops._p(self._sched), self.SCHED_WINDOW, ops._p(self._cursor),
+                  ops._p(self.total_norm), ops._stream(self.fs.param.device))
 
     def host_step(self):
         """The host bookkeeping of a scheduled step (after its launch or its graph replay)."""

@@ -90,9 +90,8 @@ class _Part:
 
 
 def _bias_act(code, y2d, bias, slope):
-    _lib.check(ops.lib().xpa_bias_act(code, ops._p(y2d), y2d.shape[0], y2d.shape[1],
-                                      ops._p(bias) if bias is not None else None, float(slope),
-                                      ops._stream(y2d.device)), "xpa_bias_act")
+    _lib.call(ops.lib().xpa_bias_act, code, ops._p(y2d), y2d.shape[0], y2d.shape[1],
+              ops._p(bias) if bias is not None else None, float(slope), ops._stream(y2d.device))
 
 
 def _act_bwd_bias(parts, code, g2d, h2d, slope, bias_grad):
@@ -106,12 +105,10 @@ def _act_bwd_bias(parts, code, g2d, h2d, slope, bias_grad):
     hp = ops._p(h2d) if code else None
     gp = ops._p(g2d) if code else None
     if k22:
-        _lib.check(L.xpa_act_bwd_bias(code, ops._p(g2d), hp, rows, cols, float(slope), gp, ops._p(part), s),
-                   "xpa_act_bwd_bias")
+        _lib.call(L.xpa_act_bwd_bias, code, ops._p(g2d), hp, rows, cols, float(slope), gp, ops._p(part), s)
     else:
-        _lib.check(L.xpa_act_bwd_colsum(code, ops._p(g2d), hp, rows, cols, float(slope), gp, ops._p(part), s),
-                   "xpa_act_bwd_colsum")
-    _lib.check(L.xpa_colsum_finalize(ops._p(part), part.shape[0], cols, ops._p(bias_grad), s), "xpa_colsum_finalize")
+        _lib.call(L.xpa_act_bwd_colsum, code, ops._p(g2d), hp, rows, cols, float(slope), gp, ops._p(part), s)
+    _lib.call(L.xpa_colsum_finalize, ops._p(part), part.shape[0], cols, ops._p(bias_grad), s)
 
 
 def _chain(layers, x):
@@ -310,8 +307,7 @@ class _Trunk:
         part = self.parts.buf(("fcab", rows, C), (G, C), g.device)
         ops.s3_gemm_group_act([(g, b, dz[:, c0:c0 + 256]) for b, c0 in zip(bd, c0s)], g.shape[1],
                               [y_flat[:, c0:c0 + 256] for c0 in c0s], code, slope, C, part)
-        _lib.check(ops.lib().xpa_colsum_finalize(ops._p(part), G, C, ops._p(conv.bias.grad), ops._stream(g.device)),
-                   "colsum db (fc act)")
+        _lib.call(ops.lib().xpa_colsum_finalize, ops._p(part), G, C, ops._p(conv.bias.grad), ops._stream(g.device))
         return dz
 
     # r06: the first fc layer's weight gradient on the split too (was hipBLASLt's f32 GEMM: 822 us per C3 minibatch,
@@ -360,8 +356,7 @@ class _Trunk:
         if x.dtype != torch.uint8 or x.device.type != "cuda" or not x.is_contiguous():
             raise ValueError("frames must be a contiguous uint8 ROCm tensor [B, H, W, C]")
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        _lib.check(ops.lib().xpa_frames_to_f32(ops._p(x), x.numel(), ops._p(out), ops._stream(x.device)),
-                   "xpa_frames_to_f32")
+        _lib.call(ops.lib().xpa_frames_to_f32, ops._p(x), x.numel(), ops._p(out), ops._stream(x.device))
         return out
 
     def _conv1_u8(self, xu):
@@ -372,8 +367,8 @@ class _Trunk:
         OH, OW = (H + 2 * pd - k) // st + 1, (W + 2 * pd - k) // st + 1
         w = conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous()
         y = torch.empty((B, OH, OW, 32), dtype=torch.float32, device=xu.device)
-        _lib.check(ops.lib().xpa_conv1_u8_fwd(code, ops._p(xu), B, H, W, C, k, st, pd, ops._p(w), ops._p(conv.bias), 32,
-                                              float(slope), ops._p(y), ops._stream(xu.device)), "xpa_conv1_u8_fwd")
+        _lib.call(ops.lib().xpa_conv1_u8_fwd, code, ops._p(xu), B, H, W, C, k, st, pd, ops._p(w), ops._p(conv.bias), 32,
+                  float(slope), ops._p(y), ops._stream(xu.device))
         return y
 
     @torch.no_grad()
@@ -415,8 +410,8 @@ class _Trunk:
             Cl = h.shape[3]
             s = torch.empty((B, Cl), dtype=torch.float32, device=x.device)
             am = torch.empty((B, Cl), dtype=torch.int32, device=x.device)
-            _lib.check(ops.lib().xpa_global_maxpool(ops._p(h), B, h.shape[1] * h.shape[2], Cl, ops._p(s), ops._p(am),
-                                                    ops._stream(x.device)), "xpa_global_maxpool")
+            _lib.call(ops.lib().xpa_global_maxpool, ops._p(h), B, h.shape[1] * h.shape[2], Cl, ops._p(s), ops._p(am),
+                      ops._stream(x.device))
             return s, (hs, am, None, [])
         flat = h.reshape(B, -1)                  # (H, W, C) order: no copy
         fouts = []
@@ -480,9 +475,8 @@ class _Trunk:
         h = h if h.is_contiguous() else h.contiguous()
         n = B * OH * OW * conv.out_channels
         y = torch.empty((n + slack,), dtype=torch.float32, device=h.device)[:n].view(B, OH, OW, conv.out_channels)
-        _lib.check(ops.lib().xpa_conv_fwd(code, ops._p(h), B, H, W, C, ops._p(conv.weight), ops._p(conv.bias),
-                                          conv.out_channels, k, st, pd, float(slope), ops._p(y), ops._stream(h.device)),
-                   "xpa_conv_fwd")
+        _lib.call(ops.lib().xpa_conv_fwd, code, ops._p(h), B, H, W, C, ops._p(conv.weight), ops._p(conv.bias),
+                  conv.out_channels, k, st, pd, float(slope), ops._p(y), ops._stream(h.device))
         return y
 
     def _conv_wgrad(self, conv, g, act, slope, y, x):
@@ -496,12 +490,11 @@ class _Trunk:
         part = self.parts.buf(("wg", cout, cols), (G, cout * cols), g.device)
         bpart = self.parts.buf(("wgb", cout), (G, cout), g.device) if act >= 0 else None
         g = g if g.is_contiguous() else g.contiguous()
-        _lib.check(L.xpa_conv_wgrad(act, ops._p(g), ops._p(y) if act >= 0 else None, float(slope), ops._p(x), B, H, W, C,
-                                    cout, k, conv.stride[0], conv.padding[0], ops._p(part), ops._p(bpart), st),
-                   "xpa_conv_wgrad")
-        _lib.check(L.xpa_colsum_finalize(ops._p(part), G, cout * cols, ops._p(conv.weight.grad), st), "colsum dW")
+        _lib.call(L.xpa_conv_wgrad, act, ops._p(g), ops._p(y) if act >= 0 else None, float(slope), ops._p(x), B, H, W,
+                  C, cout, k, conv.stride[0], conv.padding[0], ops._p(part), ops._p(bpart), st)
+        _lib.call(L.xpa_colsum_finalize, ops._p(part), G, cout * cols, ops._p(conv.weight.grad), st)
         if act >= 0:
-            _lib.check(L.xpa_colsum_finalize(ops._p(bpart), G, cout, ops._p(conv.bias.grad), st), "colsum db")
+            _lib.call(L.xpa_colsum_finalize, ops._p(bpart), G, cout, ops._p(conv.bias.grad), st)
 
     def _conv_dgrad(self, conv, dz, x_shape, prev):
         """K28 data gradient from dz (the block's pre-activation gradient, NHWC) into the block's input; prev = (code,
@@ -516,9 +509,9 @@ class _Trunk:
         G = int(L.xpa_conv_dgrad_num_partials(B, H, W))
         bpart = self.parts.buf(("dgb", B * H * W, Cin), (G, Cin), dz.device)
         dz = dz if dz.is_contiguous() else dz.contiguous()
-        _lib.check(L.xpa_conv_dgrad(ops._p(dz), B, OH, OW, conv.out_channels, ops._p(conv.weight), Cin, k, s, p, H, W,
-                                    code, ops._p(y_prev), float(slope), ops._p(dx), ops._p(bpart), st), "xpa_conv_dgrad")
-        _lib.check(L.xpa_colsum_finalize(ops._p(bpart), G, Cin, ops._p(bgrad), st), "colsum db (dgrad)")
+        _lib.call(L.xpa_conv_dgrad, ops._p(dz), B, OH, OW, conv.out_channels, ops._p(conv.weight), Cin, k, s, p, H, W,
+                  code, ops._p(y_prev), float(slope), ops._p(dx), ops._p(bpart), st)
+        _lib.call(L.xpa_colsum_finalize, ops._p(bpart), G, Cin, ops._p(bgrad), st)
         return dx
 
     @staticmethod
@@ -537,15 +530,12 @@ class _Trunk:
         g = g if g.is_contiguous() else g.contiguous()
         B, H, W, C = xu.shape
         code, slope, y = act if act is not None else (-1, 0.0, None)
-        _lib.check(L.xpa_conv1_u8_wgrad_act(code, ops._p(g), ops._p(y) if y is not None else None, float(slope),
-                                            ops._p(xu), B, H, W, C, 8, conv.stride[0], conv.padding[0], 32,
-                                            ops._p(self._wg_part), ops._p(self._wb_part) if y is not None else None,
-                                            st), "xpa_conv1_u8_wgrad_act")
-        _lib.check(L.xpa_colsum_finalize(ops._p(self._wg_part), G, 8192, ops._p(conv.weight.grad), st),
-                   "xpa_colsum_finalize")
+        _lib.call(L.xpa_conv1_u8_wgrad_act, code, ops._p(g), ops._p(y) if y is not None else None, float(slope),
+                  ops._p(xu), B, H, W, C, 8, conv.stride[0], conv.padding[0], 32, ops._p(self._wg_part),
+                  ops._p(self._wb_part) if y is not None else None, st)
+        _lib.call(L.xpa_colsum_finalize, ops._p(self._wg_part), G, 8192, ops._p(conv.weight.grad), st)
         if y is not None:
-            _lib.check(L.xpa_colsum_finalize(ops._p(self._wb_part), G, 32, ops._p(conv.bias.grad), st),
-                       "xpa_colsum_finalize")
+            _lib.call(L.xpa_colsum_finalize, ops._p(self._wb_part), G, 32, ops._p(conv.bias.grad), st)
 
     @staticmethod
     def _dgrad_ok(conv):
@@ -560,9 +550,8 @@ class _Trunk:
         """K27: d input (NHWC [B, H, W, 32]) from g = d output (NHWC [B, OH, OW, 64], contiguous)."""
         B, H, W = in_shape[0], in_shape[1], in_shape[2]
         dx = torch.empty((B, H, W, 32), dtype=torch.float32, device=g.device)
-        _lib.check(ops.lib().xpa_conv_dgrad_s2k(ops._p(g), B, g.shape[1], g.shape[2], 64, ops._p(conv.weight), 32,
-                                                conv.kernel_size[0], conv.stride[0], conv.padding[0], H, W, ops._p(dx),
-                                                ops._stream(g.device)), "xpa_conv_dgrad_s2k")
+        _lib.call(ops.lib().xpa_conv_dgrad_s2k, ops._p(g), B, g.shape[1], g.shape[2], 64, ops._p(conv.weight), 32,
+                  conv.kernel_size[0], conv.stride[0], conv.padding[0], H, W, ops._p(dx), ops._stream(g.device))
         return dx
 
     @torch.no_grad()
@@ -612,11 +601,9 @@ class _Trunk:
                 L, st = ops.lib(), ops._stream(y.device)
                 if getattr(self, "err", None) is None:
                     self.err = torch.zeros((1,), dtype=torch.int32, device=y.device)   # argmax outside [0, HW)
-                _lib.check(L.xpa_maxpool_act_bwd_bias(code, ops._p(ds.contiguous()), ops._p(am), ops._p(y), B, HW, Cy,
-                                                      float(slope), ops._p(dz), ops._p(part), ops._p(self.err), st),
-                           "xpa_maxpool_act_bwd_bias")
-                _lib.check(L.xpa_colsum_finalize(ops._p(part), part.shape[0], Cy, ops._p(conv.bias.grad), st),
-                           "xpa_colsum_finalize")
+                _lib.call(L.xpa_maxpool_act_bwd_bias, code, ops._p(ds.contiguous()), ops._p(am), ops._p(y), B, HW, Cy,
+                          float(slope), ops._p(dz), ops._p(part), ops._p(self.err), st)
+                _lib.call(L.xpa_colsum_finalize, ops._p(part), part.shape[0], Cy, ops._p(conv.bias.grad), st)
                 g, g_dz = dz, True
             else:
                 g = g.reshape(y.shape)

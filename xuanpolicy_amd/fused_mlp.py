@@ -320,20 +320,18 @@ class FusedActorCritic:
             if not deferred and defer_trunk and self._sign_on(code):
                 # K13 writes h's sign bits beside h: K42S's act' (32 B per row read instead of h's 1 KiB)
                 x.hsign = self._sign_buf(B, x.device)
-                _lib.check(ops.lib().xpa_thin_linear_act_fwd_gather_sign(
-                    code, ops._p(x.flat), x.flat.stride(0), x.flat.shape[0], ops._p(x.idx), B, lin.in_features,
-                    lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope, ops._p(h), h.stride(0),
-                    ops._p(adv) if adv_partials is not None else None,
-                    ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered),
-                    ops._p(x.hsign), ops._stream(x.device)), "xpa_thin_linear_act_fwd_gather_sign")
+                _lib.call(ops.lib().xpa_thin_linear_act_fwd_gather_sign, code, ops._p(x.flat), x.flat.stride(0),
+                          x.flat.shape[0], ops._p(x.idx), B, lin.in_features, lin.out_features, ops._p(lin.weight),
+                          ops._p(lin.bias), slope, ops._p(h), h.stride(0),
+                          ops._p(adv) if adv_partials is not None else None,
+                          ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered),
+                          ops._p(x.hsign), ops._stream(x.device))
                 return [h] + self._chain_forward(self.rep[1:], h)
-            _lib.check(ops.lib().xpa_thin_linear_act_fwd_gather(
-                code, ops._p(x.flat), x.flat.stride(0), x.flat.shape[0], ops._p(x.idx), B, lin.in_features,
-                lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope, None if deferred else ops._p(h),
-                h.stride(0),
-                ops._p(adv) if adv_partials is not None else None,
-                ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered),
-                ops._stream(x.device)), "xpa_thin_linear_act_fwd_gather")
+            _lib.call(ops.lib().xpa_thin_linear_act_fwd_gather, code, ops._p(x.flat), x.flat.stride(0), x.flat.shape[0],
+                      ops._p(x.idx), B, lin.in_features, lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope,
+                      None if deferred else ops._p(h), h.stride(0), ops._p(adv) if adv_partials is not None else None,
+                      ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered),
+                      ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
         if norm is not None:
             # x RAW: observation normalisation fused into the first layer (xpa_thin_linear_act_fwd_norm);
@@ -343,19 +341,17 @@ class FusedActorCritic:
             lin, code, slope = self.rep[0]
             mean, var, clip, xn, col, col_ld, cursor = norm
             h = torch.empty((x.shape[0], lin.out_features), dtype=torch.float32, device=x.device)
-            _lib.check(ops.lib().xpa_thin_linear_act_fwd_norm(
-                code, ops._p(x), x.stride(0), x.shape[0], lin.in_features, lin.out_features, ops._p(lin.weight),
-                ops._p(lin.bias), slope, ops._p(h), h.stride(0), ops._p(mean), ops._p(var), float(clip), ops._p(xn),
-                xn.stride(0), ops._p(col), int(col_ld), ops._p(cursor), ops._stream(x.device)),
-                "xpa_thin_linear_act_fwd_norm")
+            _lib.call(ops.lib().xpa_thin_linear_act_fwd_norm, code, ops._p(x), x.stride(0), x.shape[0], lin.in_features,
+                      lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope, ops._p(h), h.stride(0),
+                      ops._p(mean), ops._p(var), float(clip), ops._p(xn), xn.stride(0), ops._p(col), int(col_ld),
+                      ops._p(cursor), ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
         if self.thin0 and x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1:
             lin, code, slope = self.rep[0]
             h = torch.empty((x.shape[0], lin.out_features), dtype=torch.float32, device=x.device)
-            _lib.check(ops.lib().xpa_thin_linear_act_fwd(code, ops._p(x), x.stride(0), x.shape[0], lin.in_features,
-                                                         lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope,
-                                                         ops._p(h), h.stride(0), ops._stream(x.device)),
-                       "xpa_thin_linear_act_fwd")
+            _lib.call(ops.lib().xpa_thin_linear_act_fwd, code, ops._p(x), x.stride(0), x.shape[0], lin.in_features,
+                      lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope, ops._p(h), h.stride(0),
+                      ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
         return self._chain_forward(self.rep, x)
 
@@ -375,14 +371,12 @@ class FusedActorCritic:
         if isinstance(x, Rows) and getattr(x, "gathered", None) is not None:
             x = x.gathered
         if isinstance(x, Rows):
-            _lib.check(L.xpa_thin_linear_act_bwd_gather(code, ops._p(g), g.stride(0), ops._p(h), h.stride(0), rows,
-                                                        ops._p(x.flat), x.flat.stride(0), x.flat.shape[0],
-                                                        ops._p(x.idx), din, lin.out_features, slope, ops._p(pdw),
-                                                        ops._p(pdb), s), "xpa_thin_linear_act_bwd_gather")
+            _lib.call(L.xpa_thin_linear_act_bwd_gather, code, ops._p(g), g.stride(0), ops._p(h), h.stride(0), rows,
+                      ops._p(x.flat), x.flat.stride(0), x.flat.shape[0], ops._p(x.idx), din, lin.out_features, slope,
+                      ops._p(pdw), ops._p(pdb), s)
         else:
-            _lib.check(L.xpa_thin_linear_act_bwd(code, ops._p(g), g.stride(0), ops._p(h), h.stride(0), rows,
-                                                 ops._p(x), x.stride(0), din, lin.out_features, slope, ops._p(pdw),
-                                                 ops._p(pdb), s), "xpa_thin_linear_act_bwd")
+            _lib.call(L.xpa_thin_linear_act_bwd, code, ops._p(g), g.stride(0), ops._p(h), h.stride(0), rows, ops._p(x),
+                      x.stride(0), din, lin.out_features, slope, ops._p(pdw), ops._p(pdb), s)
         self._cq.add(pdw, lin.weight.grad)
         self._cq.add(pdb, lin.bias.grad)
 
@@ -650,9 +644,9 @@ class FusedActorCritic:
             self._partials[key] = part
         s = ops._stream(g.device)
         L = ops.lib()
-        _lib.check(L.xpa_act_bwd_colsum(code, ops._p(g), ops._p(h) if code else None, rows, cols, slope,
-                                        ops._p(g) if code else None, ops._p(part), s), "xpa_act_bwd_colsum")
-        _lib.check(L.xpa_colsum_finalize(ops._p(part), part.shape[0], cols, ops._p(out), s), "xpa_colsum_finalize")
+        _lib.call(L.xpa_act_bwd_colsum, code, ops._p(g), ops._p(h) if code else None, rows, cols, slope,
+                  ops._p(g) if code else None, ops._p(part), s)
+        _lib.call(L.xpa_colsum_finalize, ops._p(part), part.shape[0], cols, ops._p(out), s)
 
     def _split_buf(self, k, name, device):
         key = ("s3split", name, k)
@@ -862,12 +856,12 @@ class FusedActorCritic:
             self._partials[key] = ws
         p_dw, p_dbh, p_dbo, dz = ws
         s = ops._stream(g.device)
-        _lib.check(L.xpa_head_backward(code_h, K, ops._p(g), g.stride(0), ops._p(h), ops._p(lin_o.weight), B, H, slope,
-                                       ops._p(dz), ops._p(p_dw), ops._p(p_dbh), ops._p(p_dbo), s), "xpa_head_backward")
+        _lib.call(L.xpa_head_backward, code_h, K, ops._p(g), g.stride(0), ops._p(h), ops._p(lin_o.weight), B, H, slope,
+                  ops._p(dz), ops._p(p_dw), ops._p(p_dbh), ops._p(p_dbo), s)
         G = p_dw.shape[0]
-        _lib.check(L.xpa_colsum_finalize(ops._p(p_dw), G, K * H, ops._p(lin_o.weight.grad), s), "colsum dW")
-        _lib.check(L.xpa_colsum_finalize(ops._p(p_dbh), G, H, ops._p(lin_h.bias.grad), s), "colsum db_h")
-        _lib.check(L.xpa_colsum_finalize(ops._p(p_dbo), G, K, ops._p(lin_o.bias.grad), s), "colsum db_o")
+        _lib.call(L.xpa_colsum_finalize, ops._p(p_dw), G, K * H, ops._p(lin_o.weight.grad), s)
+        _lib.call(L.xpa_colsum_finalize, ops._p(p_dbh), G, H, ops._p(lin_h.bias.grad), s)
+        _lib.call(L.xpa_colsum_finalize, ops._p(p_dbo), G, K, ops._p(lin_o.bias.grad), s)
         return dz
 
     def _chain_backward(self, layers, inputs, outs, g, need_dx, accumulate=None, allow_head=True, thin_first=False):

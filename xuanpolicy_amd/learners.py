@@ -382,8 +382,7 @@ class _FusedPolicyGradient(Learner):
                 ws[G] = (torch.zeros((G, fused.fs.numel), dtype=torch.float32, device=obs_flat.device),
                          torch.zeros((G, 8), dtype=torch.float64, device=obs_flat.device))
             a.grad_part, a.loss_part = ws[G][0].data_ptr(), ws[G][1].data_ptr()
-        _lib.check(ops.lib().xpa_small_mlp_update(ctypes.byref(a), ops._stream(obs_flat.device)),
-                   "xpa_small_mlp_update")
+        _lib.call(ops.lib().xpa_small_mlp_update, ctypes.byref(a), ops._stream(obs_flat.device))
         return out
 
     def small_update(self, obs_flat, idx, act, adv, ret, old_logp=None, use_advnorm=True):

@@ -155,8 +155,7 @@ def s3_split(b, out=None):
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
     _req(out, "out", torch.uint8, (nbytes,))
-    _lib.check(lib().xpa_s3_split_b(_p(b), k, n, b.stride(0), b.stride(1), _p(out), _stream(b.device)),
-               "xpa_s3_split_b")
+    _lib.call(lib().xpa_s3_split_b, _p(b), k, n, b.stride(0), b.stride(1), _p(out), _stream(b.device))
     return out
 
 
@@ -187,7 +186,7 @@ def s3_split_batch(pairs, scales=None, cs=None):
             _SPLIT_PLANS.clear()
         plan = _SPLIT_PLANS[key] = (n, arrs, [ctypes.cast(a, ctypes.c_void_p) for a in arrs])
     n, _keep, args = plan
-    _lib.check(L.xpa_s3_split_batch(n, *args, _stream(pairs[0][0].device)), "xpa_s3_split_batch")
+    _lib.call(L.xpa_s3_split_batch, n, *args, _stream(pairs[0][0].device))
 
 
 def _s3_split_batch_scaled(pairs, scales, cs):
@@ -221,8 +220,8 @@ def _s3_split_batch_scaled(pairs, scales, cs):
             _SPLIT_PLANS.clear()
         plan = _SPLIT_PLANS[key] = (n, arrs, [ctypes.cast(a, ctypes.c_void_p) for a in arrs])
     n, _keep, args = plan
-    _lib.check(L.xpa_s3_split_batch_scaled(n, *args, _p(cs[0]) if cs else None, float(cs[1]) if cs else 0.0,
-                                           _stream(pairs[0][0].device)), "xpa_s3_split_batch_scaled")
+    _lib.call(L.xpa_s3_split_batch_scaled, n, *args, _p(cs[0]) if cs else None, float(cs[1]) if cs else 0.0,
+              _stream(pairs[0][0].device))
 
 
 def s3_gemm_trunk_bwd_crit(dz_a, b_split, k_a, k_c, mask, dv, cs, h_sign, x, act, slope, partial_dw=None,
@@ -247,16 +246,15 @@ def s3_gemm_trunk_bwd_crit(dz_a, b_split, k_a, k_c, mask, dv, cs, h_sign, x, act
         partial_db = torch.empty(G, 256, dtype=torch.float32, device=dz_a.device)
     _req(partial_dw, "partial_dw", torch.float32, (G, 256 * d_in))
     _req(partial_db, "partial_db", torch.float32, (G, 256))
-    _lib.check(L.xpa_s3_gemm_trunk_bwd_crit(_p(dz_a), ldz, _p(b_split), k_a, k_c, _p(mask), _p(dv), _p(cs), _p(h_sign),
-                                            _p(x), ldx, rows, d_in, int(act), float(slope), _p(partial_dw),
-                                            _p(partial_db), _stream(dz_a.device)), "xpa_s3_gemm_trunk_bwd_crit")
+    _lib.call(L.xpa_s3_gemm_trunk_bwd_crit, _p(dz_a), ldz, _p(b_split), k_a, k_c, _p(mask), _p(dv), _p(cs), _p(h_sign),
+              _p(x), ldx, rows, d_in, int(act), float(slope), _p(partial_dw), _p(partial_db), _stream(dz_a.device))
     return partial_dw, partial_db
 
 
 def s3_wgrad_pair_slices(rows):
     """(sa, per_a, sc, per_c) of K41P for `rows`."""
     v = [ctypes.c_int64() for _ in range(4)]
-    _lib.check(lib().xpa_s3_wgrad_pair_slices(rows, *[ctypes.byref(x) for x in v]), "xpa_s3_wgrad_pair_slices")
+    _lib.call(lib().xpa_s3_wgrad_pair_slices, rows, *[ctypes.byref(x) for x in v])
     sa, sc, per_a, per_c = (x.value for x in v)
     return sa, per_a, sc, per_c
 
@@ -281,9 +279,8 @@ def s3_wgrad_pair(dz_a, h, mask, dv, wc, slope, out_a=None, out_c=None):
         out_c = torch.empty(sc, 256, 256, dtype=torch.float32, device=dz_a.device)
     _req(out_a, "out_a", torch.float32, (sa, 256, 256))
     _req(out_c, "out_c", torch.float32, (sc, 256, 256))
-    _lib.check(lib().xpa_s3_wgrad_pair(_p(dz_a), lda, _p(h), ldb, rows, _p(mask), _p(dv), _p(wc), float(slope), sa,
-                                       per_a, sc, per_c, _p(out_a), _p(out_c), _stream(dz_a.device)),
-               "xpa_s3_wgrad_pair")
+    _lib.call(lib().xpa_s3_wgrad_pair, _p(dz_a), lda, _p(h), ldb, rows, _p(mask), _p(dv), _p(wc), float(slope), sa,
+              per_a, sc, per_c, _p(out_a), _p(out_c), _stream(dz_a.device))
     return out_a, out_c
 
 
@@ -297,7 +294,7 @@ def s3_gemm(a, b_split, k, out=None):
     ldc = _row_stride(out, "out", 256)
     if out.shape[0] != m:
         raise ValueError("out must have %d rows" % m)
-    _lib.check(lib().xpa_s3_gemm(_p(a), lda, _p(b_split), _p(out), ldc, m, k, 256, _stream(a.device)), "xpa_s3_gemm")
+    _lib.call(lib().xpa_s3_gemm, _p(a), lda, _p(b_split), _p(out), ldc, m, k, 256, _stream(a.device))
     return out
 
 
@@ -327,8 +324,7 @@ def s3_gemm_group(problems, k):
         if len(_GROUP_ARGS) > 64:
             _GROUP_ARGS.clear()
         _GROUP_ARGS[key] = arrs
-    _lib.check(lib().xpa_s3_gemm_group(n, arrs[0], arrs[1], arrs[2], lda, ldc, m, k, _stream(a0.device)),
-               "xpa_s3_gemm_group")
+    _lib.call(lib().xpa_s3_gemm_group, n, arrs[0], arrs[1], arrs[2], lda, ldc, m, k, _stream(a0.device))
 
 
 def s3_gemm_group_act(problems, k, ys, act, slope, channels, bias_partial):
@@ -350,9 +346,9 @@ def s3_gemm_group_act(problems, k, ys, act, slope, channels, bias_partial):
     G = int(lib().xpa_s3_gemm_group_act_num_partials(n, m))
     _req(bias_partial, "bias_partial", torch.float32, (G, channels))
     arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])   # noqa: E731
-    _lib.check(lib().xpa_s3_gemm_group_act(n, arr([p[0] for p in problems]), arr([p[1] for p in problems]),
-                                           arr([p[2] for p in problems]), arr(ys), lda, ldc, m, k, act, float(slope),
-                                           channels, _p(bias_partial), _stream(a0.device)), "xpa_s3_gemm_group_act")
+    _lib.call(lib().xpa_s3_gemm_group_act, n, arr([p[0] for p in problems]), arr([p[1] for p in problems]),
+              arr([p[2] for p in problems]), arr(ys), lda, ldc, m, k, act, float(slope), channels, _p(bias_partial),
+              _stream(a0.device))
 
 
 def s3_gemm_trunk_bwd(dz, b_split, k, h, x, act, slope, partial_dw=None, partial_db=None, h_sign=None):
@@ -375,13 +371,11 @@ def s3_gemm_trunk_bwd(dz, b_split, k, h, x, act, slope, partial_dw=None, partial
     _req(partial_db, "partial_db", torch.float32, (G, 256))
     if h_sign is not None:
         _req(h_sign, "h_sign", torch.int32, (rows, 8))
-        _lib.check(L.xpa_s3_gemm_trunk_bwd_sign(_p(dz), ldz, _p(b_split), k, _p(h_sign), _p(x), ldx, rows, d_in,
-                                                int(act), float(slope), _p(partial_dw), _p(partial_db),
-                                                _stream(dz.device)), "xpa_s3_gemm_trunk_bwd_sign")
+        _lib.call(L.xpa_s3_gemm_trunk_bwd_sign, _p(dz), ldz, _p(b_split), k, _p(h_sign), _p(x), ldx, rows, d_in,
+                  int(act), float(slope), _p(partial_dw), _p(partial_db), _stream(dz.device))
         return partial_dw, partial_db
-    _lib.check(L.xpa_s3_gemm_trunk_bwd(_p(dz), ldz, _p(b_split), k, _p(h), ldh, _p(x), ldx, rows, d_in, int(act),
-                                       float(slope), _p(partial_dw), _p(partial_db), _stream(dz.device)),
-               "xpa_s3_gemm_trunk_bwd")
+    _lib.call(L.xpa_s3_gemm_trunk_bwd, _p(dz), ldz, _p(b_split), k, _p(h), ldh, _p(x), ldx, rows, d_in, int(act),
+              float(slope), _p(partial_dw), _p(partial_db), _stream(dz.device))
     return partial_dw, partial_db
 
 
@@ -400,8 +394,8 @@ def s3_gemm_rows_pair(a, b0_split, b1_split, bias, out=None):
     nb = int(lib().xpa_s3_split_bytes(256, 256))
     for b in (b0_split, b1_split):
         _req(b, "b_split", torch.uint8, (nb,))
-    _lib.check(lib().xpa_s3_gemm_rows_pair(_p(a), lda, _p(b0_split), _p(b1_split), _p(bias), _p(out), ldc, m,
-                                           _stream(a.device)), "xpa_s3_gemm_rows_pair")
+    _lib.call(lib().xpa_s3_gemm_rows_pair, _p(a), lda, _p(b0_split), _p(b1_split), _p(bias), _p(out), ldc, m,
+              _stream(a.device))
     return out
 
 
@@ -429,10 +423,10 @@ def s3_gemm_rows_pair_trunk(x, w, b, act, slope, mean, var, clip, xn, col, col_l
     nb = int(lib().xpa_s3_split_bytes(256, 256))
     for bb in (b0_split, b1_split):
         _req(bb, "b_split", torch.uint8, (nb,))
-    _lib.check(lib().xpa_s3_gemm_rows_pair_trunk(
-        int(act), _p(x), x.stride(0), d_in, _p(w), _p(b), float(slope), _p(mean), _p(var), float(clip), _p(xn),
-        xn.stride(0), _p(col) if col is not None else None, int(col_ld), _p(cursor) if col is not None else None,
-        _p(b0_split), _p(b1_split), _p(bias), _p(out), ldc, m, _stream(x.device)), "xpa_s3_gemm_rows_pair_trunk")
+    _lib.call(lib().xpa_s3_gemm_rows_pair_trunk, int(act), _p(x), x.stride(0), d_in, _p(w), _p(b), float(slope),
+              _p(mean), _p(var), float(clip), _p(xn), xn.stride(0), _p(col) if col is not None else None, int(col_ld),
+              _p(cursor) if col is not None else None, _p(b0_split), _p(b1_split), _p(bias), _p(out), ldc, m,
+              _stream(x.device))
     return out
 
 
@@ -449,10 +443,9 @@ def s3_split_padded(b, k_pad, out=None):
         out = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
     _req(out, "out", torch.uint8, (nbytes,))
     arr = lambda t, v: (t * 1)(v)   # noqa: E731
-    _lib.check(L.xpa_s3_split_batch_padded(1, arr(ctypes.c_void_p, b.data_ptr()), arr(ctypes.c_int64, k_pad),
-                                           arr(ctypes.c_int64, kv), arr(ctypes.c_int64, b.stride(0)),
-                                           arr(ctypes.c_int64, b.stride(1)), arr(ctypes.c_void_p, out.data_ptr()),
-                                           _stream(b.device)), "xpa_s3_split_batch_padded")
+    _lib.call(L.xpa_s3_split_batch_padded, 1, arr(ctypes.c_void_p, b.data_ptr()), arr(ctypes.c_int64, k_pad),
+              arr(ctypes.c_int64, kv), arr(ctypes.c_int64, b.stride(0)), arr(ctypes.c_int64, b.stride(1)),
+              arr(ctypes.c_void_p, out.data_ptr()), _stream(b.device))
     return out
 
 
@@ -470,8 +463,8 @@ def s3_gemm_value(a, b_split, k, bias, act, slope, w_out, b_out, out=None):
     if out is None:
         out = torch.empty(m, dtype=torch.float32, device=a.device)
     _req(out, "out", torch.float32, (m,))
-    _lib.check(lib().xpa_s3_gemm_value(_p(a), a.stride(0), _p(b_split), _p(out), m, k, _p(bias), int(act), float(slope),
-                                       _p(w_out), _p(b_out), _stream(a.device)), "xpa_s3_gemm_value")
+    _lib.call(lib().xpa_s3_gemm_value, _p(a), a.stride(0), _p(b_split), _p(out), m, k, _p(bias), int(act), float(slope),
+              _p(w_out), _p(b_out), _stream(a.device))
     return out
 
 
@@ -492,10 +485,8 @@ def s3_gemm_bias_act(a, b_split, k, bias, act, slope, out=None, sign=None, ridx=
         ldc = _row_stride(out, "out", 256)
         if sign is not None:
             _req(sign, "sign", torch.int32, (m, 8))
-        _lib.check(lib().xpa_s3_gemm_bias_act_rows(_p(a), a.stride(0), _p(ridx), _p(b_split), _p(out), ldc, m, k,
-                                                   _p(bias), int(act), float(slope),
-                                                   _p(sign) if sign is not None else None, _stream(a.device)),
-                   "xpa_s3_gemm_bias_act_rows")
+        _lib.call(lib().xpa_s3_gemm_bias_act_rows, _p(a), a.stride(0), _p(ridx), _p(b_split), _p(out), ldc, m, k,
+                  _p(bias), int(act), float(slope), _p(sign) if sign is not None else None, _stream(a.device))
         return out
     lda = _row_stride(a, "a", k)
     m = a.shape[0]
@@ -507,9 +498,8 @@ def s3_gemm_bias_act(a, b_split, k, bias, act, slope, out=None, sign=None, ridx=
         raise ValueError("out must have %d rows" % m)
     if sign is not None:
         _req(sign, "sign", torch.int32, (m, 8))
-    _lib.check(lib().xpa_s3_gemm_bias_act(_p(a), lda, _p(b_split), _p(out), ldc, m, k, _p(bias), int(act),
-                                          float(slope), _p(sign) if sign is not None else None, _stream(a.device)),
-               "xpa_s3_gemm_bias_act")
+    _lib.call(lib().xpa_s3_gemm_bias_act, _p(a), lda, _p(b_split), _p(out), ldc, m, k, _p(bias), int(act), float(slope),
+              _p(sign) if sign is not None else None, _stream(a.device))
     return out
 
 
@@ -532,14 +522,12 @@ def s3_gemm_trunk_bwd_dz(dz, b_split, k, h_sign, act, slope, dz_out, partial_db,
         _req(mask, "mask", torch.int32, (rows, 8))
         _req(dv, "dv", torch.float32, (rows,))
         _req(cs, "cs", torch.float32, (256,))
-        _lib.check(L.xpa_s3_gemm_trunk_bwd_crit_dz(_p(dz), ldz, _p(b_split), k_a, k_c, _p(mask), _p(dv), _p(cs),
-                                                   _p(h_sign), rows, int(act), float(slope), _p(dz_out), ld_out,
-                                                   _p(partial_db), _stream(dz.device)), "xpa_s3_gemm_trunk_bwd_crit_dz")
+        _lib.call(L.xpa_s3_gemm_trunk_bwd_crit_dz, _p(dz), ldz, _p(b_split), k_a, k_c, _p(mask), _p(dv), _p(cs),
+                  _p(h_sign), rows, int(act), float(slope), _p(dz_out), ld_out, _p(partial_db), _stream(dz.device))
         return dz_out, partial_db
     ldz = _row_stride(dz, "dz", k)
-    _lib.check(L.xpa_s3_gemm_trunk_bwd_dz(_p(dz), ldz, _p(b_split), k, _p(h_sign), rows, int(act), float(slope),
-                                          _p(dz_out), ld_out, _p(partial_db), _stream(dz.device)),
-               "xpa_s3_gemm_trunk_bwd_dz")
+    _lib.call(L.xpa_s3_gemm_trunk_bwd_dz, _p(dz), ldz, _p(b_split), k, _p(h_sign), rows, int(act), float(slope),
+              _p(dz_out), ld_out, _p(partial_db), _stream(dz.device))
     return dz_out, partial_db
 
 
@@ -557,10 +545,9 @@ def gather_minibatch_pitched(idx, obs, obs_out, adv=None, adv_partials=None):
     if adv is not None:
         _req(adv, "adv", torch.float32)
         _req(adv_partials, "adv_partials", torch.float64, (gather_num_partials(B), 2))
-    _lib.check(lib().xpa_gather_minibatch_pitched(_p(idx), B, obs.shape[0], _p(obs), d * 4, _p(obs_out),
-                                                  obs_out.stride(0) * 4, _p(adv) if adv is not None else None,
-                                                  _p(adv_partials) if adv is not None else None, None,
-                                                  _stream(obs.device)), "xpa_gather_minibatch_pitched")
+    _lib.call(lib().xpa_gather_minibatch_pitched, _p(idx), B, obs.shape[0], _p(obs), d * 4, _p(obs_out),
+              obs_out.stride(0) * 4, _p(adv) if adv is not None else None,
+              _p(adv_partials) if adv is not None else None, None, _stream(obs.device))
     return obs_out
 
 
@@ -586,8 +573,8 @@ def s3_wgrad(a, b, out=None, slices=None, aidx=None, m=None):
         if out is None:
             out = torch.empty(S, m, 256, dtype=torch.float32, device=a.device)
         _req(out, "out", torch.float32, (S, m, 256))
-        _lib.check(lib().xpa_s3_wgrad_rows(_p(a), a.stride(0), _p(aidx), _p(b), ldb, rows, m, 256, S, _p(out),
-                                           _stream(a.device)), "xpa_s3_wgrad_rows")
+        _lib.call(lib().xpa_s3_wgrad_rows, _p(a), a.stride(0), _p(aidx), _p(b), ldb, rows, m, 256, S, _p(out),
+                  _stream(a.device))
         return out
     _req(a, "a", torch.float32, contiguous=False)
     _req(b, "b", torch.float32, contiguous=False)
@@ -607,8 +594,7 @@ def s3_wgrad(a, b, out=None, slices=None, aidx=None, m=None):
         if out is None:
             out = torch.empty(S, m, 256, dtype=torch.float32, device=a.device)
         _req(out, "out", torch.float32, (S, m, 256))
-        _lib.check(lib().xpa_s3_wgrad_padded(_p(a), lda, _p(b), ldb, rows, m, 256, S, _p(out), _stream(a.device)),
-                   "xpa_s3_wgrad_padded")
+        _lib.call(lib().xpa_s3_wgrad_padded, _p(a), lda, _p(b), ldb, rows, m, 256, S, _p(out), _stream(a.device))
         return out
     rows, m = a.shape
     lda, ldb = _row_stride(a, "a", m), _row_stride(b, "b", 256)
@@ -618,7 +604,7 @@ def s3_wgrad(a, b, out=None, slices=None, aidx=None, m=None):
     if out is None:
         out = torch.empty(S, m, 256, dtype=torch.float32, device=a.device)
     _req(out, "out", torch.float32, (S, m, 256))
-    _lib.check(lib().xpa_s3_wgrad(_p(a), lda, _p(b), ldb, rows, m, 256, S, _p(out), _stream(a.device)), "xpa_s3_wgrad")
+    _lib.call(lib().xpa_s3_wgrad, _p(a), lda, _p(b), ldb, rows, m, 256, S, _p(out), _stream(a.device))
     return out
 
 
@@ -633,13 +619,11 @@ def gae_scan(rew, val, term, closed, boot, gamma, gae_lambda, use_gae=True, adv=
     ret = torch.empty_like(rew) if ret is None else _req(ret, "ret", torch.float32, (N, T))
     ev = TIMER.kernel_events("gae")
     if ev is None:
-        rc = lib().xpa_gae_scan(_p(rew), _p(val), _p(term), _p(closed), _p(boot), N, T, float(gamma), float(gae_lambda),
-                                int(bool(use_gae)), _p(adv), _p(ret), _stream(rew.device))
+        _lib.call(lib().xpa_gae_scan, _p(rew), _p(val), _p(term), _p(closed), _p(boot), N, T, float(gamma),
+                  float(gae_lambda), int(bool(use_gae)), _p(adv), _p(ret), _stream(rew.device))
     else:
-        rc = lib().xpa_gae_scan_timed(_p(rew), _p(val), _p(term), _p(closed), _p(boot), N, T, float(gamma),
-                                      float(gae_lambda), int(bool(use_gae)), _p(adv), _p(ret), ev[0], ev[1],
-                                      _stream(rew.device))
-    _lib.check(rc, "xpa_gae_scan")
+        _lib.call(lib().xpa_gae_scan_timed, _p(rew), _p(val), _p(term), _p(closed), _p(boot), N, T, float(gamma),
+                  float(gae_lambda), int(bool(use_gae)), _p(adv), _p(ret), ev[0], ev[1], _stream(rew.device))
     return adv, ret
 
 
@@ -658,10 +642,8 @@ def gae_scan_compact(rew, val, term, slot_t, vboot, gamma, gae_lambda, use_gae=T
     ret = torch.empty_like(rew) if ret is None else _req(ret, "ret", torch.float32, (N, T))
     ev = TIMER.kernel_events("gae")
     e0, e1 = (None, None) if ev is None else ev
-    rc = lib().xpa_gae_scan_compact(_p(rew), _p(val), _p(term), _p(slot_t), _p(vboot), N, T, float(gamma),
-                                    float(gae_lambda), int(bool(use_gae)), _p(adv), _p(ret), _p(boot), e0, e1,
-                                    _stream(rew.device))
-    _lib.check(rc, "xpa_gae_scan_compact")
+    _lib.call(lib().xpa_gae_scan_compact, _p(rew), _p(val), _p(term), _p(slot_t), _p(vboot), N, T, float(gamma),
+              float(gae_lambda), int(bool(use_gae)), _p(adv), _p(ret), _p(boot), e0, e1, _stream(rew.device))
     return adv, ret
 
 
@@ -693,11 +675,9 @@ def gae_scan_value(rew, val, term, slot_t, z_critic, act, w_critic, b_critic, ga
     ret = torch.empty_like(rew) if ret is None else _req(ret, "ret", torch.float32, (N, T))
     ev = TIMER.kernel_events("gae")
     e0, e1 = (None, None) if ev is None else ev
-    rc = lib().xpa_gae_scan_value(_p(rew), _p(val), _p(term), _p(slot_t), int(act[0]), _p(z_critic), ld,
-                                  float(act[1]), _p(w_critic), _p(b_critic), N, T, HEAD_HIDDEN, float(gamma),
-                                  float(gae_lambda), int(bool(use_gae)), _p(adv), _p(ret), _p(boot), e0, e1,
-                                  _stream(rew.device))
-    _lib.check(rc, "xpa_gae_scan_value")
+    _lib.call(lib().xpa_gae_scan_value, _p(rew), _p(val), _p(term), _p(slot_t), int(act[0]), _p(z_critic), ld,
+              float(act[1]), _p(w_critic), _p(b_critic), N, T, HEAD_HIDDEN, float(gamma), float(gae_lambda),
+              int(bool(use_gae)), _p(adv), _p(ret), _p(boot), e0, e1, _stream(rew.device))
     return adv, ret
 
 
@@ -731,7 +711,7 @@ def dispatch_floor_us(device, reps=50):
     xpa_gae_scan_timed uses: the fixed cost every launch carries on it (bench.py reports it beside K1)."""
     st = _stream(device)
     return _event_timed_median_us(
-        lambda e0, e1: _lib.check(lib().xpa_dispatch_floor_timed(e0, e1, st), "xpa_dispatch_floor_timed"), reps)
+        lambda e0, e1: _lib.call(lib().xpa_dispatch_floor_timed, e0, e1, st), reps)
 
 
 def stream_copy_us(rew, val, term, reps=50):
@@ -742,8 +722,7 @@ def stream_copy_us(rew, val, term, reps=50):
     st = _stream(rew.device)
 
     def launch(e0, e1):
-        _lib.check(lib().xpa_stream_copy_timed(_p(rew), _p(val), _p(term), _p(a), _p(o), n, e0, e1, st),
-                   "xpa_stream_copy_timed")
+        _lib.call(lib().xpa_stream_copy_timed, _p(rew), _p(val), _p(term), _p(a), _p(o), n, e0, e1, st)
     return _event_timed_median_us(launch, reps)
 
 
@@ -752,8 +731,8 @@ def random_permutation(n, seed, counter, out=None, device=None):
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=device if device is not None else "cuda")
     _req(out, "out", torch.int64, (n,))
-    _lib.check(lib().xpa_random_permutation(n, int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF, _p(out),
-                                            _stream(out.device)), "xpa_random_permutation")
+    _lib.call(lib().xpa_random_permutation, n, int(seed) & 0xFFFFFFFF, int(counter) & 0xFFFFFFFF, _p(out),
+              _stream(out.device))
     return out
 
 
@@ -785,10 +764,9 @@ def gather_minibatch(idx, obs, adv=None, obs_out=None, adv_partials=None, err=No
             adv_partials = torch.empty((gather_num_partials(B), 2), dtype=torch.float64, device=obs.device)
         else:
             _req(adv_partials, "adv_partials", torch.float64, (gather_num_partials(B), 2))
-    rc = lib().xpa_gather_minibatch(_p(idx), B, obs.shape[0], _p(obs), row_bytes, _p(obs_out), _p(adv) if adv is not None else None,
-                                    _p(adv_partials) if adv is not None else None,
-                                    _p(_req(err, "err", torch.int32, (1,))) if err is not None else None, _stream(obs.device))
-    _lib.check(rc, "xpa_gather_minibatch")
+    _lib.call(lib().xpa_gather_minibatch, _p(idx), B, obs.shape[0], _p(obs), row_bytes, _p(obs_out),
+              _p(adv) if adv is not None else None, _p(adv_partials) if adv is not None else None,
+              _p(_req(err, "err", torch.int32, (1,))) if err is not None else None, _stream(obs.device))
     return obs_out, (adv_partials if adv is not None else None)
 
 
@@ -846,20 +824,18 @@ def policy_loss(algo, dist, head, logstd, v, act, adv, ret, old_logp=None, idx=N
     s = _stream(head.device)
     L = lib()
     ev = TIMER.start("loss")
-    rc = L.xpa_policy_loss_fwd_bwd(ALGO[algo], DIST[dist], B, A, _p(head), _p(logstd) if dist == "gaussian" else None,
-                                   _p(v), _p(idx), rows, _p(act), _p(old_logp) if algo == "ppo" else None, _p(adv), _p(ret),
-                                   _p(adv_partials), adv_partials.shape[0] if adv_partials is not None else 0,
-                                   float(clip_range), float(vf_coef), float(ent_coef), _p(ws.d_head), _p(ws.d_v),
-                                   _p(ws.partials), s)
+    _lib.call(L.xpa_policy_loss_fwd_bwd, ALGO[algo], DIST[dist], B, A, _p(head),
+              _p(logstd) if dist == "gaussian" else None, _p(v), _p(idx), rows, _p(act),
+              _p(old_logp) if algo == "ppo" else None, _p(adv), _p(ret), _p(adv_partials),
+              adv_partials.shape[0] if adv_partials is not None else 0, float(clip_range), float(vf_coef),
+              float(ent_coef), _p(ws.d_head), _p(ws.d_v), _p(ws.partials), s)
     TIMER.stop("loss", ev)
-    _lib.check(rc, "xpa_policy_loss_fwd_bwd")
     d_logstd = ws.d_logstd
     if d_logstd_out is not None and dist == "gaussian":
         _req(d_logstd_out, "d_logstd_out", torch.float32, (A,))
         d_logstd = d_logstd_out
-    rc = L.xpa_policy_loss_finalize(ALGO[algo], DIST[dist], B, A, _p(ws.partials), ws.partials.shape[0],
-                                    float(vf_coef), float(ent_coef), _p(ws.scalars), _p(d_logstd), s)
-    _lib.check(rc, "xpa_policy_loss_finalize")
+    _lib.call(L.xpa_policy_loss_finalize, ALGO[algo], DIST[dist], B, A, _p(ws.partials), ws.partials.shape[0],
+              float(vf_coef), float(ent_coef), _p(ws.scalars), _p(d_logstd), s)
     return ws.scalars, ws.d_head, d_logstd, ws.d_v
 
 
@@ -895,7 +871,7 @@ class HeadWorkspace:
 
 
 def _colsum(part, out, s):
-    _lib.check(lib().xpa_colsum_finalize(_p(part), part.shape[0], part.shape[1], _p(out), s), "xpa_colsum_finalize")
+    _lib.call(lib().xpa_colsum_finalize, _p(part), part.shape[0], part.shape[1], _p(out), s)
 
 
 class ColsumQueue:
@@ -946,9 +922,8 @@ class ColsumQueue:
             if loss is not None:   # a deferred loss finalize with no column tiles to ride on: run it alone
                 a, d, B, K, lp, vf, ent, sc, dls = loss
                 dev = device if device is not None else lp.device
-                _lib.check(lib().xpa_policy_loss_finalize_sq(a, d, B, K, _p(lp), lp.shape[0], vf, ent, _p(sc), _p(dls),
-                                                             _p(sq) if sq is not None else None, _stream(dev)),
-                           "xpa_policy_loss_finalize")
+                _lib.call(lib().xpa_policy_loss_finalize_sq, a, d, B, K, _p(lp), lp.shape[0], vf, ent, _p(sc), _p(dls),
+                          _p(sq) if sq is not None else None, _stream(dev))
             return None, 0
         key = tuple((p.data_ptr(), p.shape[0], p.shape[1], o.data_ptr(), tm) for p, o, tm in self.items)
         plan = self._plans.get(key)
@@ -974,9 +949,8 @@ class ColsumQueue:
         one = sq is not None and len(plan) == 1 and plan[0][3] + 2 <= sq.numel()
         if loss is not None and not one:   # the loss finalize on its own (d logstd share into sq[0] if any)
             a, d, B, K, lp, vf, ent, sc, dls = loss
-            _lib.check(L.xpa_policy_loss_finalize_sq(a, d, B, K, _p(lp), lp.shape[0], vf, ent, _p(sc), _p(dls),
-                                                     _p(sq) if sq is not None else None, s),
-                       "xpa_policy_loss_finalize")
+            _lib.call(L.xpa_policy_loss_finalize_sq, a, d, B, K, _p(lp), lp.shape[0], vf, ent, _p(sc), _p(dls),
+                      _p(sq) if sq is not None else None, s)
             loss = None
         if one:
             if self._ticket is None:
@@ -985,30 +959,24 @@ class ColsumQueue:
             if tmap is not None:
                 la = loss if loss is not None else (0, 0, 0, 0, None, 0.0, 0.0, None, None)
                 a, d, B, K, lp, vf, ent, sc, dls = la
-                _lib.check(L.xpa_colsum_finalize_batch_map(n, *args, ctypes.cast(tmap, ctypes.c_void_p), _p(sq),
-                                                           _p(self._ticket), a, d, B, K,
-                                                           _p(lp) if lp is not None else None,
-                                                           lp.shape[0] if lp is not None else 0, vf, ent,
-                                                           _p(sc) if sc is not None else None,
-                                                           _p(dls) if dls is not None else None, s),
-                           "xpa_colsum_finalize_batch_map")
+                _lib.call(L.xpa_colsum_finalize_batch_map, n, *args, ctypes.cast(tmap, ctypes.c_void_p), _p(sq),
+                          _p(self._ticket), a, d, B, K, _p(lp) if lp is not None else None,
+                          lp.shape[0] if lp is not None else 0, vf, ent, _p(sc) if sc is not None else None,
+                          _p(dls) if dls is not None else None, s)
             elif loss is not None:   # one launch: the column tiles + the loss finalize block
                 a, d, B, K, lp, vf, ent, sc, dls = loss
-                _lib.check(L.xpa_colsum_finalize_batch_sq_loss(n, *args, _p(sq), _p(self._ticket), a, d, B, K, _p(lp),
-                                                               lp.shape[0], vf, ent, _p(sc), _p(dls), s),
-                           "xpa_colsum_finalize_batch_sq_loss")
+                _lib.call(L.xpa_colsum_finalize_batch_sq_loss, n, *args, _p(sq), _p(self._ticket), a, d, B, K, _p(lp),
+                          lp.shape[0], vf, ent, _p(sc), _p(dls), s)
             else:
-                _lib.check(L.xpa_colsum_finalize_batch_sq(n, *args, _p(sq), _p(self._ticket), s),
-                           "xpa_colsum_finalize_batch_sq")
+                _lib.call(L.xpa_colsum_finalize_batch_sq, n, *args, _p(sq), _p(self._ticket), s)
             total = sq[1 + tiles:2 + tiles]
         else:
             for n, _keep, args, _tiles, tmap in plan:
                 if tmap is not None:
-                    _lib.check(L.xpa_colsum_finalize_batch_map(n, *args, ctypes.cast(tmap, ctypes.c_void_p), None, None,
-                                                               0, 0, 0, 0, None, 0, 0.0, 0.0, None, None, s),
-                               "xpa_colsum_finalize_batch_map")
+                    _lib.call(L.xpa_colsum_finalize_batch_map, n, *args, ctypes.cast(tmap, ctypes.c_void_p), None, None,
+                              0, 0, 0, 0, None, 0, 0.0, 0.0, None, None, s)
                 else:
-                    _lib.check(L.xpa_colsum_finalize_batch(n, *args, s), "xpa_colsum_finalize_batch")
+                    _lib.call(L.xpa_colsum_finalize_batch, n, *args, s)
         written = sum(o.numel() for _, o, _ in self.items)
         self.items = []
         return total, written
@@ -1094,38 +1062,29 @@ def fused_heads(algo, dist, ws, z_actor, w_actor, b_actor, act_actor, z_critic, 
         din = xr.shape[1]
         if xr.dim() != 2 or xr.shape[0] != B or din > TRUNK_DMAX or tuple(w0.shape) != (H, din):
             raise ValueError("trunk rows must be [%d, <= %d] with w_in [%d, d_in]" % (B, TRUNK_DMAX, H))
+    # every head kernel ends in the same output-layer / loss / workspace arguments; a branch states only its prefix
+    head_a, head_c = (ALGO[algo], DIST[dist], act_actor[0], B, K, H), (act_critic[0], B, H)
+    tail_a = (_p(w_actor), _p(b_actor), float(act_actor[1]), p_logstd, _p(idx), rows, _p(act), p_old, _p(adv),
+              _p(adv_partials), n_adv, float(clip_range), float(ent_coef), _p(ws.dz_actor), _p(ws.p_dw_actor),
+              _p(ws.p_dbh_actor), _p(ws.p_dbo_actor), _p(ws.loss_partials), W, s)
+    tail_c = (_p(w_critic), _p(b_critic), float(act_critic[1]), _p(idx), rows, _p(ret), float(vf_coef),
+              _p(ws.dz_critic), _p(ws.p_dw_critic), _p(ws.p_dbh_critic), _p(ws.p_dbo_critic), _p(ws.loss_partials), W, s)
+    if trunk is not None:
+        trunk_in = (_p(xr), xr.stride(0), din, _p(w0), _p(b0), float(slope0))
     if trunk is not None and wh_split is not None:
         # K16R: h formed from the gathered rows inside both launches (Wh as its bf16 planes); the actor writes h
         # and its sign bits
         if h_sign is not None:
             _req(h_sign, "h_sign", torch.int32, (B, 8))
         wsa, wsc = wh_split
-        _lib.check(L.xpa_head_gemm_s3r_actor(ALGO[algo], DIST[dist], act_actor[0], B, K, H, _p(xr), xr.stride(0), din,
-                                             _p(w0), _p(b0), float(slope0), _p(h_out), h_out.stride(0),
-                                             _p(h_sign) if h_sign is not None else None, _p(wsa), _p(bha), ld,
-                                             _p(w_actor), _p(b_actor), float(act_actor[1]), p_logstd, _p(idx), rows,
-                                             _p(act), p_old, _p(adv), _p(adv_partials), n_adv, float(clip_range),
-                                             float(ent_coef), _p(ws.dz_actor), _p(ws.p_dw_actor), _p(ws.p_dbh_actor),
-                                             _p(ws.p_dbo_actor), _p(ws.loss_partials), W, s), "xpa_head_gemm_s3r_actor")
-        _lib.check(L.xpa_head_gemm_s3r_critic(act_critic[0], B, H, _p(xr), xr.stride(0), din, _p(w0), _p(b0),
-                                              float(slope0), _p(wsc), _p(bhc), ld, _p(w_critic), _p(b_critic),
-                                              float(act_critic[1]), _p(idx), rows, _p(ret), float(vf_coef),
-                                              _p(ws.dz_critic), _p(ws.p_dw_critic), _p(ws.p_dbh_critic),
-                                              _p(ws.p_dbo_critic), _p(ws.loss_partials), W, s),
-                   "xpa_head_gemm_s3r_critic")
+        _lib.call(L.xpa_head_gemm_s3r_actor, *head_a, *trunk_in, _p(h_out), h_out.stride(0),
+                  _p(h_sign) if h_sign is not None else None, _p(wsa), _p(bha), ld, *tail_a)
+        _lib.call(L.xpa_head_gemm_s3r_critic, *head_c, *trunk_in, _p(wsc), _p(bhc), ld, *tail_c)
     elif trunk is not None:
-        _lib.check(L.xpa_head_gemm_trunk_actor(ALGO[algo], DIST[dist], act_actor[0], B, K, H, _p(xr), xr.stride(0), din,
-                                               _p(w0), _p(b0), float(slope0), _p(h_out), h_out.stride(0), _p(wha),
-                                               _p(bha), ld, _p(w_actor), _p(b_actor), float(act_actor[1]), p_logstd,
-                                               _p(idx), rows, _p(act), p_old, _p(adv), _p(adv_partials), n_adv,
-                                               float(clip_range), float(ent_coef), _p(ws.dz_actor), _p(ws.p_dw_actor),
-                                               _p(ws.p_dbh_actor), _p(ws.p_dbo_actor), _p(ws.loss_partials), W, s),
-                   "xpa_head_gemm_trunk_actor")
+        _lib.call(L.xpa_head_gemm_trunk_actor, *head_a, *trunk_in, _p(h_out), h_out.stride(0), _p(wha), _p(bha), ld,
+                  *tail_a)
         # the critic reads the h the actor launch wrote (plain K16)
-        _lib.check(L.xpa_head_gemm_critic(act_critic[0], B, H, _p(h_out), h_out.stride(0), _p(whc), _p(bhc), ld,
-                                          _p(w_critic), _p(b_critic), float(act_critic[1]), _p(idx), rows, _p(ret),
-                                          float(vf_coef), _p(ws.dz_critic), _p(ws.p_dw_critic), _p(ws.p_dbh_critic),
-                                          _p(ws.p_dbo_critic), _p(ws.loss_partials), W, s), "xpa_head_gemm_critic")
+        _lib.call(L.xpa_head_gemm_critic, *head_c, _p(h_out), h_out.stride(0), _p(whc), _p(bhc), ld, *tail_c)
     elif gemm is not None:
         # K16W (wave-specialised, the epilogue overlapped with the GEMM) for heads up to 8 wide; K16 otherwise
         wsa = K16W_ENABLED and K <= 8
@@ -1138,37 +1097,21 @@ def fused_heads(algo, dist, ws, z_actor, w_actor, b_actor, act_actor, z_critic, 
             else:
                 fa, fc = L.xpa_head_gemm_s3p_actor, L.xpa_head_gemm_s3p_critic
             wha, whc = wh_split
-        _lib.check(fa(ALGO[algo], DIST[dist], act_actor[0], B, K, H, _p(x), x.stride(0), _p(wha),
-                      _p(bha), ld, _p(w_actor), _p(b_actor), float(act_actor[1]), p_logstd, _p(idx),
-                      rows, _p(act), p_old, _p(adv), _p(adv_partials), n_adv, float(clip_range),
-                      float(ent_coef), _p(ws.dz_actor), _p(ws.p_dw_actor), _p(ws.p_dbh_actor),
-                      _p(ws.p_dbo_actor), _p(ws.loss_partials), W, s), "xpa_head_gemm_actor")
+        _lib.call(fa, *head_a, _p(x), x.stride(0), _p(wha), _p(bha), ld, *tail_a)
         if crit_mask is not None:
             if not (wh_split is not None and S3_HEADS == "s3q" and not K16W_ENABLED):
                 raise ValueError("crit_mask needs the K16Q heads")
             cm, cdv = crit_mask
             _req(cm, "crit mask", torch.int32, (B, 8))
             _req(cdv, "crit dv", torch.float32, (B,))
-            _lib.check(L.xpa_head_gemm_s3q_critic_mask(act_critic[0], B, H, _p(x), x.stride(0), _p(whc), _p(bhc), ld,
-                                                       _p(w_critic), _p(b_critic), float(act_critic[1]), _p(idx), rows,
-                                                       _p(ret), float(vf_coef), None, _p(ws.p_dw_critic),
-                                                       _p(ws.p_dbh_critic), _p(ws.p_dbo_critic), _p(ws.loss_partials),
-                                                       W, s, _p(cm), _p(cdv)), "xpa_head_gemm_s3q_critic_mask")
+            # no dz_critic (tail_c[7]); the mask and dv follow the stream
+            _lib.call(L.xpa_head_gemm_s3q_critic_mask, *head_c, _p(x), x.stride(0), _p(whc), _p(bhc), ld, *tail_c[:7],
+                      None, *tail_c[8:], _p(cm), _p(cdv))
         else:
-            _lib.check(fc(act_critic[0], B, H, _p(x), x.stride(0), _p(whc), _p(bhc), ld, _p(w_critic),
-                          _p(b_critic), float(act_critic[1]), _p(idx), rows, _p(ret), float(vf_coef),
-                          _p(ws.dz_critic), _p(ws.p_dw_critic), _p(ws.p_dbh_critic),
-                          _p(ws.p_dbo_critic), _p(ws.loss_partials), W, s), "xpa_head_gemm_critic")
+            _lib.call(fc, *head_c, _p(x), x.stride(0), _p(whc), _p(bhc), ld, *tail_c)
     else:
-        _lib.check(L.xpa_head_fused_actor(ALGO[algo], DIST[dist], act_actor[0], B, K, H, ld, _p(z_actor), _p(w_actor),
-                                          _p(b_actor), float(act_actor[1]), p_logstd, _p(idx), rows, _p(act), p_old,
-                                          _p(adv), _p(adv_partials), n_adv, float(clip_range), float(ent_coef),
-                                          _p(ws.dz_actor), _p(ws.p_dw_actor), _p(ws.p_dbh_actor), _p(ws.p_dbo_actor),
-                                          _p(ws.loss_partials), W, s), "xpa_head_fused_actor")
-        _lib.check(L.xpa_head_fused_critic(act_critic[0], B, H, ld, _p(z_critic), _p(w_critic), _p(b_critic),
-                                           float(act_critic[1]), _p(idx), rows, _p(ret), float(vf_coef),
-                                           _p(ws.dz_critic), _p(ws.p_dw_critic), _p(ws.p_dbh_critic),
-                                           _p(ws.p_dbo_critic), _p(ws.loss_partials), W, s), "xpa_head_fused_critic")
+        _lib.call(L.xpa_head_fused_actor, *head_a, ld, _p(z_actor), *tail_a)
+        _lib.call(L.xpa_head_fused_critic, *head_c, ld, _p(z_critic), *tail_c)
     TIMER.stop("heads", ev)
     g = grads or {}
     d_logstd = g.get("logstd")
@@ -1180,9 +1123,8 @@ def fused_heads(algo, dist, ws, z_actor, w_actor, b_actor, act_actor, z_critic, 
         queue.defer_loss(ALGO[algo], DIST[dist], B, K, ws.loss_partials, vf_coef, ent_coef, ws.scalars, d_logstd)
     else:
         # sq_logstd: device address of one double receiving sum(d_logstd^2) (the clip norm's share of logstd)
-        _lib.check(L.xpa_policy_loss_finalize_sq(ALGO[algo], DIST[dist], B, K, _p(ws.loss_partials), ws.G,
-                                                 float(vf_coef), float(ent_coef), _p(ws.scalars), _p(d_logstd),
-                                                 sq_logstd, s), "xpa_policy_loss_finalize")
+        _lib.call(L.xpa_policy_loss_finalize_sq, ALGO[algo], DIST[dist], B, K, _p(ws.loss_partials), ws.G,
+                  float(vf_coef), float(ent_coef), _p(ws.scalars), _p(d_logstd), sq_logstd, s)
     for key, part in (("w_actor", ws.p_dw_actor), ("b_actor", ws.p_dbo_actor), ("bh_actor", ws.p_dbh_actor),
                       ("w_critic", ws.p_dw_critic), ("b_critic", ws.p_dbo_critic), ("bh_critic", ws.p_dbh_critic)):
         if key in g:
@@ -1217,14 +1159,13 @@ def rms_update(x, mean, var, count, partials=None, reduce_partials=None, world=1
     s = _stream(x.device)
     if ticket is not None and reduce_partials is None:
         _req(ticket, "ticket", torch.int32, (1,))
-        _lib.check(lib().xpa_rms_update(_p(x), n, dim, ld, _p(mean), _p(var), _p(count), _p(partials), _p(ticket), s),
-                   "xpa_rms_update")
+        _lib.call(lib().xpa_rms_update, _p(x), n, dim, ld, _p(mean), _p(var), _p(count), _p(partials), _p(ticket), s)
         return
-    _lib.check(lib().xpa_rms_partials(_p(x), n, dim, ld, _p(mean), _p(partials), s), "xpa_rms_partials")
+    _lib.call(lib().xpa_rms_partials, _p(x), n, dim, ld, _p(mean), _p(partials), s)
     if reduce_partials is not None:
         reduce_partials(partials)
         n = n * int(world)
-    _lib.check(lib().xpa_rms_merge(_p(partials), np_, n, dim, _p(mean), _p(var), _p(count), s), "xpa_rms_merge")
+    _lib.call(lib().xpa_rms_merge, _p(partials), np_, n, dim, _p(mean), _p(var), _p(count), s)
 
 
 def store_column(x, buf, cursor):
@@ -1236,8 +1177,7 @@ def store_column(x, buf, cursor):
         raise ValueError("store_column: buf must be [N, T] + x.shape[1:]")
     _req(cursor, "cursor", torch.int32, (4,))
     row_bytes = x[0].numel() * x.element_size()
-    _lib.check(lib().xpa_store_column(_p(x), N, row_bytes, _p(buf), buf.shape[1], _p(cursor), _stream(x.device)),
-               "xpa_store_column")
+    _lib.call(lib().xpa_store_column, _p(x), N, row_bytes, _p(buf), buf.shape[1], _p(cursor), _stream(x.device))
 
 
 def obs_normalize(x, mean, var, clip_range, out, col_out=None, col_ld=0, cursor=None):
@@ -1250,9 +1190,8 @@ def obs_normalize(x, mean, var, clip_range, out, col_out=None, col_ld=0, cursor=
     if col_out is not None:
         _req(col_out, "col_out", torch.float32)
         _req(cursor, "cursor", torch.int32, (4,))
-    rc = lib().xpa_obs_normalize(_p(x), n, dim, ldx, _p(mean), _p(var), float(clip_range), _p(out), ldo, _p(col_out),
-                                 int(col_ld), _p(cursor), _stream(x.device))
-    _lib.check(rc, "xpa_obs_normalize")
+    _lib.call(lib().xpa_obs_normalize, _p(x), n, dim, ldx, _p(mean), _p(var), float(clip_range), _p(out), ldo,
+              _p(col_out), int(col_ld), _p(cursor), _stream(x.device))
     return out
 
 
@@ -1279,10 +1218,9 @@ def rollout_sample(dist, head, logstd, v, cursor, seed, buf_act, buf_logp, buf_v
         raise ValueError("env_in must be float32 [n_envs, act_dim]")
     if dist == "gaussian":
         _req(logstd, "logstd", torch.float32, (A,))
-    rc = lib().xpa_rollout_sample(DIST[dist], N, A, T, _p(head), _p(logstd) if dist == "gaussian" else None, _p(v),
-                                  _p(cursor), int(seed) & 0xFFFFFFFF, float(act_clip), _p(buf_act), _p(buf_logp),
-                                  _p(buf_val), _p(env_in), ld_env, _stream(head.device))
-    _lib.check(rc, "xpa_rollout_sample")
+    _lib.call(lib().xpa_rollout_sample, DIST[dist], N, A, T, _p(head), _p(logstd) if dist == "gaussian" else None,
+              _p(v), _p(cursor), int(seed) & 0xFFFFFFFF, float(act_clip), _p(buf_act), _p(buf_logp), _p(buf_val),
+              _p(env_in), ld_env, _stream(head.device))
 
 
 def rollout_policy_head(dist, z_actor, z_critic, act, w_actor, b_actor, w_critic, b_critic, logstd, cursor, seed,
@@ -1308,12 +1246,10 @@ def rollout_policy_head(dist, z_actor, z_critic, act, w_actor, b_actor, w_critic
     ld_env = _row_stride(env_in, "env_in", A)
     if dist == "gaussian":
         _req(logstd, "logstd", torch.float32, (A,))
-    rc = lib().xpa_rollout_policy_head(DIST[dist], act[0], N, A, T, H, ld, _p(z_actor), _p(z_critic), float(act[1]),
-                                       _p(w_actor), _p(b_actor), _p(w_critic), _p(b_critic),
-                                       _p(logstd) if dist == "gaussian" else None, _p(cursor), int(seed) & 0xFFFFFFFF,
-                                       float(act_clip), _p(buf_act), _p(buf_logp), _p(buf_val), _p(env_in), ld_env,
-                                       _stream(z_actor.device))
-    _lib.check(rc, "xpa_rollout_policy_head")
+    _lib.call(lib().xpa_rollout_policy_head, DIST[dist], act[0], N, A, T, H, ld, _p(z_actor), _p(z_critic),
+              float(act[1]), _p(w_actor), _p(b_actor), _p(w_critic), _p(b_critic),
+              _p(logstd) if dist == "gaussian" else None, _p(cursor), int(seed) & 0xFFFFFFFF, float(act_clip),
+              _p(buf_act), _p(buf_logp), _p(buf_val), _p(env_in), ld_env, _stream(z_actor.device))
 
 
 def rollout_step_workspace(n_envs, obs_dim, rms, device):
@@ -1323,6 +1259,15 @@ def rollout_step_workspace(n_envs, obs_dim, rms, device):
     if nd <= 0:
         raise ValueError("K14F needs 1 <= obs_dim <= 64")
     return (torch.empty(nd, dtype=torch.float64, device=device), torch.zeros(nt.value, dtype=torch.int32, device=device))
+
+
+def _post_tail(ret_mean, ret_var, ret_count, returns, buf_rew, buf_term, buf_closed, buf_boot, gamma, mask_returns,
+               use_rewnorm, rew_range, atari_lifeloss, part, ticket):
+    """The arguments every K8 form ends in after its cursor (xpa_rollout_post*; K14F's xpa_rollout_step_synthbox takes
+    them without a cursor)."""
+    return (_p(ret_mean), _p(ret_var), _p(ret_count), _p(returns), _p(buf_rew), _p(buf_term), _p(buf_closed),
+            _p(buf_boot), float(gamma), int(bool(mask_returns)), int(bool(use_rewnorm)), float(rew_range),
+            int(bool(atari_lifeloss)), _p(part), _p(ticket))
 
 
 def _rollout_step_post(post, N, T, D, device):
@@ -1350,10 +1295,10 @@ def _rollout_step_post(post, N, T, D, device):
     _req(tickets, "tickets", torch.int32, (nt.value,))
     return [_p(p["slot_obs"]), _p(p["slot_t"]), S, _p(p["overflow"]), int(bool(p.get("slot_from_next", False))),
             _p(p["obs_mean"]), _p(p["obs_var"]), _p(p.get("obs_count")), float(p["obs_clip"]), _p(p["boot_norm"]), ldn,
-            _p(p["ret_mean"]), _p(p["ret_var"]), _p(p["ret_count"]), _p(p["returns"]), _p(p["buf_rew"]),
-            _p(p["buf_term"]), _p(p["buf_closed"]), _p(p["buf_boot"]), float(p["gamma"]),
-            int(bool(p.get("mask_returns", True))), int(bool(p.get("use_rewnorm", True))), float(p.get("rew_range", 5.0)),
-            int(bool(p.get("atari_lifeloss", False))), _p(part), _p(tickets)]
+            *_post_tail(p["ret_mean"], p["ret_var"], p["ret_count"], p["returns"], p["buf_rew"], p["buf_term"],
+                        p["buf_closed"], p["buf_boot"], p["gamma"], p.get("mask_returns", True),
+                        p.get("use_rewnorm", True), p.get("rew_range", 5.0), p.get("atari_lifeloss", False), part,
+                        tickets)]
 
 
 def rollout_policy_head_synthbox(z_actor, z_critic, act, w_actor, b_actor, w_critic, b_critic, logstd, cursor, seed,
@@ -1383,24 +1328,17 @@ def rollout_policy_head_synthbox(z_actor, z_critic, act, w_actor, b_actor, w_cri
     if env.num_envs != N or env.A != A or env.discrete:
         raise ValueError("the fused env step needs a continuous-action env of matching shape")
     from .envs import NOISE, TERM_THRESH, RESET_SCALE
+    # K14 + the env step: the arguments both entry points begin with
+    head_env = (act[0], N, A, T, H, ld, _p(z_actor), _p(z_critic), float(act[1]), _p(w_actor), _p(b_actor), _p(w_critic),
+                _p(b_critic), _p(logstd), _p(cursor), int(seed) & 0xFFFFFFFF, float(act_clip), _p(buf_act), _p(buf_logp),
+                _p(buf_val), env.D, _p(env.Wcat_t), env.noise_seed, env.max_episode_steps, NOISE, TERM_THRESH,
+                RESET_SCALE, _p(env.X), env.X.stride(0), _p(env.final_obs), _p(env.rew), _p(env.term), _p(env.trunc),
+                _p(env.ep_step), _p(env.ep_index), _p(env.ep_score), _p(env.ep_last_score), _p(env.ep_last_len))
     if post is not None:
-        rc = lib().xpa_rollout_step_synthbox(
-            act[0], N, A, T, H, ld, _p(z_actor), _p(z_critic), float(act[1]), _p(w_actor), _p(b_actor), _p(w_critic),
-            _p(b_critic), _p(logstd), _p(cursor), int(seed) & 0xFFFFFFFF, float(act_clip), _p(buf_act), _p(buf_logp),
-            _p(buf_val), env.D, _p(env.Wcat_t), env.noise_seed, env.max_episode_steps, NOISE, TERM_THRESH,
-            RESET_SCALE, _p(env.X), env.X.stride(0), _p(env.final_obs), _p(env.rew), _p(env.term), _p(env.trunc),
-            _p(env.ep_step), _p(env.ep_index), _p(env.ep_score), _p(env.ep_last_score), _p(env.ep_last_len),
-            *_rollout_step_post(post, N, T, env.D, z_actor.device), _stream(z_actor.device))
-        _lib.check(rc, "xpa_rollout_step_synthbox")
-        return
-    rc = lib().xpa_rollout_policy_head_synthbox(
-        act[0], N, A, T, H, ld, _p(z_actor), _p(z_critic), float(act[1]), _p(w_actor), _p(b_actor), _p(w_critic),
-        _p(b_critic), _p(logstd), _p(cursor), int(seed) & 0xFFFFFFFF, float(act_clip), _p(buf_act), _p(buf_logp),
-        _p(buf_val), env.D, _p(env.Wcat_t), env.noise_seed, env.max_episode_steps, NOISE, TERM_THRESH,
-        RESET_SCALE, _p(env.X), env.X.stride(0), _p(env.final_obs), _p(env.rew), _p(env.term), _p(env.trunc),
-        _p(env.ep_step), _p(env.ep_index), _p(env.ep_score), _p(env.ep_last_score), _p(env.ep_last_len),
-        _stream(z_actor.device))
-    _lib.check(rc, "xpa_rollout_policy_head_synthbox")
+        _lib.call(lib().xpa_rollout_step_synthbox, *head_env, *_rollout_step_post(post, N, T, env.D, z_actor.device),
+                  _stream(z_actor.device))
+    else:
+        _lib.call(lib().xpa_rollout_policy_head_synthbox, *head_env, _stream(z_actor.device))
 
 
 def value_head(z_critic, act, w_critic, b_critic, out=None):
@@ -1412,8 +1350,8 @@ def value_head(z_critic, act, w_critic, b_critic, out=None):
     _req(w_critic, "w_critic", torch.float32, (1, H))
     out = torch.empty((N,), dtype=torch.float32, device=z_critic.device) if out is None else out
     _req(out, "out", torch.float32, (N,))
-    _lib.check(lib().xpa_value_head(act[0], N, H, z_critic.stride(0), _p(z_critic), float(act[1]), _p(w_critic),
-                                    _p(b_critic), _p(out), _stream(z_critic.device)), "xpa_value_head")
+    _lib.call(lib().xpa_value_head, act[0], N, H, z_critic.stride(0), _p(z_critic), float(act[1]), _p(w_critic),
+              _p(b_critic), _p(out), _stream(z_critic.device))
     return out
 
 
@@ -1452,6 +1390,8 @@ def rollout_post(rew, term, trunc, v_boot, cursor, ret_mean, ret_var, ret_count,
         _req(t, name, torch.float32, (N, T))
     _req(buf_closed, "buf_closed", torch.uint8, (N, T))
     part, ticket = workspace if workspace is not None else post_workspace(N, rew.device)
+    tail = (_p(cursor),) + _post_tail(ret_mean, ret_var, ret_count, returns, buf_rew, buf_term, buf_closed, buf_boot,
+                                      gamma, mask_returns, use_rewnorm, rew_range, atari_lifeloss, part, ticket)
     if deferred is not None and len(deferred) in (8, 9):
         # (final_obs RAW, slot_obs, slot_t, overflow, obs_mean, obs_var, obs_clip, boot_norm[, slot_src RAW]):
         # normalisation of the final observations folded into K8 (xpa_rollout_post_deferred_norm); slot_src (A2C:
@@ -1474,23 +1414,13 @@ def rollout_post(rew, term, trunc, v_boot, cursor, ret_mean, ret_var, ret_count,
                 raise ValueError("rms_x must have one row per env")
             _req(rcount, "obs_count", torch.float64, (1,))
             _req(rpart, "rms_part", torch.float64, (2 * int(lib().xpa_rollout_post_num_blocks(N)), D))
-            rc = lib().xpa_rollout_post_deferred_norm_rms(
-                N, T, _p(rew), _p(term), _p(trunc), _p(final_obs), ldf, _p(slot_src), lds, D, _p(obs_mean),
-                _p(obs_var), _p(rcount), float(obs_clip), _p(boot_norm), ldn, _p(slot_obs), _p(slot_t), S,
-                _p(overflow), _p(cursor), _p(ret_mean), _p(ret_var), _p(ret_count), _p(returns), _p(buf_rew),
-                _p(buf_term), _p(buf_closed), _p(buf_boot), float(gamma), int(bool(mask_returns)),
-                int(bool(use_rewnorm)), float(rew_range), int(bool(atari_lifeloss)), _p(part), _p(ticket), _p(rx), rld,
-                _p(rpart), _stream(rew.device))
-            _lib.check(rc, "xpa_rollout_post_deferred_norm_rms")
+            _lib.call(lib().xpa_rollout_post_deferred_norm_rms, N, T, _p(rew), _p(term), _p(trunc), _p(final_obs), ldf,
+                      _p(slot_src), lds, D, _p(obs_mean), _p(obs_var), _p(rcount), float(obs_clip), _p(boot_norm), ldn,
+                      _p(slot_obs), _p(slot_t), S, _p(overflow), *tail, _p(rx), rld, _p(rpart), _stream(rew.device))
             return
-        rc = lib().xpa_rollout_post_deferred_norm(
-            N, T, _p(rew), _p(term), _p(trunc), _p(final_obs), ldf, _p(slot_src), lds,
-            D, _p(obs_mean), _p(obs_var), float(obs_clip),
-            _p(boot_norm), ldn, _p(slot_obs), _p(slot_t), S, _p(overflow), _p(cursor), _p(ret_mean), _p(ret_var),
-            _p(ret_count), _p(returns), _p(buf_rew), _p(buf_term), _p(buf_closed), _p(buf_boot), float(gamma),
-            int(bool(mask_returns)), int(bool(use_rewnorm)), float(rew_range), int(bool(atari_lifeloss)), _p(part),
-            _p(ticket), _stream(rew.device))
-        _lib.check(rc, "xpa_rollout_post_deferred_norm")
+        _lib.call(lib().xpa_rollout_post_deferred_norm, N, T, _p(rew), _p(term), _p(trunc), _p(final_obs), ldf,
+                  _p(slot_src), lds, D, _p(obs_mean), _p(obs_var), float(obs_clip), _p(boot_norm), ldn, _p(slot_obs),
+                  _p(slot_t), S, _p(overflow), *tail, _stream(rew.device))
         return
     if deferred is not None:
         boot_obs, slot_obs, slot_t, overflow = deferred
@@ -1499,22 +1429,13 @@ def rollout_post(rew, term, trunc, v_boot, cursor, ret_mean, ret_var, ret_count,
         ld = _row_stride(boot_obs, "boot_obs", D)
         _req(slot_obs, "slot_obs", torch.float32, (S * N, D))
         _req(overflow, "overflow", torch.int32, (1,))
-        rc = lib().xpa_rollout_post_deferred(N, T, _p(rew), _p(term), _p(trunc), _p(boot_obs), ld, D, _p(slot_obs),
-                                             _p(slot_t), S, _p(overflow), _p(cursor), _p(ret_mean), _p(ret_var),
-                                             _p(ret_count), _p(returns), _p(buf_rew), _p(buf_term), _p(buf_closed),
-                                             _p(buf_boot), float(gamma), int(bool(mask_returns)),
-                                             int(bool(use_rewnorm)), float(rew_range), int(bool(atari_lifeloss)),
-                                             _p(part), _p(ticket), _stream(rew.device))
-        _lib.check(rc, "xpa_rollout_post_deferred")
+        _lib.call(lib().xpa_rollout_post_deferred, N, T, _p(rew), _p(term), _p(trunc), _p(boot_obs), ld, D,
+                  _p(slot_obs), _p(slot_t), S, _p(overflow), *tail, _stream(rew.device))
         return
     if v_boot_mid is not None:
         _req(v_boot_mid, "v_boot_mid", torch.float32, (N,))
-    rc = lib().xpa_rollout_post(N, T, _p(rew), _p(term), _p(trunc), _p(v_boot), _p(v_boot_mid), _p(cursor),
-                                _p(ret_mean), _p(ret_var),
-                                _p(ret_count), _p(returns), _p(buf_rew), _p(buf_term), _p(buf_closed), _p(buf_boot),
-                                float(gamma), int(bool(mask_returns)), int(bool(use_rewnorm)), float(rew_range),
-                                int(bool(atari_lifeloss)), _p(part), _p(ticket), _stream(rew.device))
-    _lib.check(rc, "xpa_rollout_post")
+    _lib.call(lib().xpa_rollout_post, N, T, _p(rew), _p(term), _p(trunc), _p(v_boot), _p(v_boot_mid), *tail,
+              _stream(rew.device))
 
 
 def _n_slots(slot_t, N):
@@ -1533,8 +1454,8 @@ def bootstrap_fixup(values, slot_t, buf_term, buf_boot):
     _req(values, "values", torch.float32, ((S + 1) * N,))
     _req(buf_term, "buf_term", torch.float32, (N, T))
     _req(buf_boot, "buf_boot", torch.float32, (N, T))
-    _lib.check(lib().xpa_rollout_bootstrap_fixup(N, T, _p(values), _p(slot_t), S, _p(buf_term), _p(buf_boot),
-                                                 _stream(values.device)), "xpa_rollout_bootstrap_fixup")
+    _lib.call(lib().xpa_rollout_bootstrap_fixup, N, T, _p(values), _p(slot_t), S, _p(buf_term), _p(buf_boot),
+              _stream(values.device))
 
 
 def dqn_td_loss(evalQ, targetQ, act, rew, term, gamma, dQ=None, td_abs=None, scalars=None, err=None):
@@ -1552,7 +1473,6 @@ def dqn_td_loss(evalQ, targetQ, act, rew, term, gamma, dQ=None, td_abs=None, sca
         _req(td_abs, "td_abs", torch.float32, (B,))
     scalars = torch.empty(2, dtype=torch.float32, device=evalQ.device) if scalars is None else \
         _req(scalars, "scalars", torch.float32, (2,))
-    rc = lib().xpa_dqn_td_loss(B, A, _p(evalQ), ld_e, _p(targetQ), ld_t, _p(act), _p(rew), _p(term), float(gamma),
-                               _p(dQ), A, _p(td_abs), _p(scalars), _p(err), _stream(evalQ.device))
-    _lib.check(rc, "xpa_dqn_td_loss")
+    _lib.call(lib().xpa_dqn_td_loss, B, A, _p(evalQ), ld_e, _p(targetQ), ld_t, _p(act), _p(rew), _p(term), float(gamma),
+              _p(dQ), A, _p(td_abs), _p(scalars), _p(err), _stream(evalQ.device))
     return dQ, td_abs, scalars

@@ -87,9 +87,8 @@ class PerOffPolicyBuffer:
         self._put(self.rewards, rews)
         self._put(self.terminals, terminals)
         self._put(self.next_observations, next_obs)
-        _lib.check(ops.lib().xpa_per_store(ops._p(self.sum_tree), ops._p(self.min_tree), ops._p(self._max_priority),
-                                           self.n_envs, self.capacity, self.ptr, self._alpha, ops._stream(self.device)),
-                   "xpa_per_store")
+        _lib.call(ops.lib().xpa_per_store, ops._p(self.sum_tree), ops._p(self.min_tree), ops._p(self._max_priority),
+                  self.n_envs, self.capacity, self.ptr, self._alpha, ops._stream(self.device))
         self.ptr = (self.ptr + 1) % self.n_size
         self.size = min(self.size + 1, self.n_size)
 
@@ -108,11 +107,10 @@ class PerOffPolicyBuffer:
             if uniforms.numel() != self.n_envs * b:
                 raise ValueError("uniforms must have n_envs * batch_size / n_envs entries")
         self._calls += 1
-        _lib.check(ops.lib().xpa_per_sample(ops._p(self.sum_tree), ops._p(self.min_tree), self.n_envs, self.capacity,
-                                            self.size, b, self.n_size, ops._p(uniforms), self.seed & 0xFFFFFFFF,
-                                            self._calls & 0xFFFFFFFF, float(beta), int(self.wrap_uint8), ops._p(steps),
-                                            ops._p(flat), ops._p(weights), ops._p(self._sample_err),
-                                            ops._stream(self.device)), "xpa_per_sample")
+        _lib.call(ops.lib().xpa_per_sample, ops._p(self.sum_tree), ops._p(self.min_tree), self.n_envs, self.capacity,
+                  self.size, b, self.n_size, ops._p(uniforms), self.seed & 0xFFFFFFFF, self._calls & 0xFFFFFFFF,
+                  float(beta), int(self.wrap_uint8), ops._p(steps), ops._p(flat), ops._p(weights),
+                  ops._p(self._sample_err), ops._stream(self.device))
         return steps, flat, weights
 
     def _gather(self, arr, flat):
@@ -139,11 +137,9 @@ class PerOffPolicyBuffer:
             raise ValueError("idxes / priorities must have n_envs * batch_size / n_envs entries")
         if check:
             self._err.zero_()
-        _lib.check(ops.lib().xpa_per_update_priorities(ops._p(self.sum_tree), ops._p(self.min_tree),
-                                                       ops._p(self._max_priority), ops._p(self._scratch), self.n_envs,
-                                                       self.capacity, max(self.size, 1), ops._p(idx), ops._p(pr), b,
-                                                       self._alpha, ops._p(self._err), ops._stream(self.device)),
-                   "xpa_per_update_priorities")
+        _lib.call(ops.lib().xpa_per_update_priorities, ops._p(self.sum_tree), ops._p(self.min_tree),
+                  ops._p(self._max_priority), ops._p(self._scratch), self.n_envs, self.capacity, max(self.size, 1),
+                  ops._p(idx), ops._p(pr), b, self._alpha, ops._p(self._err), ops._stream(self.device))
         if check and int(self._err.item()):
             raise AssertionError("update_priorities: index outside [0, size)")
 
