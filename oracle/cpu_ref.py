@@ -493,8 +493,8 @@ class LearnerRef:
         self.iterations = 0
 
     def _kink_hooks_arm(self):
-        """Forward hooks recording every (Linear -> LeakyReLU / ReLU) pair's input, pre-activation and activation (the
-        activation with retain_grad) for _kink_rows."""
+        """Forward hooks recording every (Linear or Conv2d -> LeakyReLU / ReLU) pair's input, pre-activation and
+        activation (the activation with retain_grad) for _kink_rows."""
         torch = _torch()
         nn = torch.nn
         self._kink_rec, self._kink_handles = [], []
@@ -503,7 +503,7 @@ class LearnerRef:
                 continue
             mods = list(m)
             for a, b in zip(mods, mods[1:]):
-                if isinstance(a, nn.Linear) and isinstance(b, (nn.LeakyReLU, nn.ReLU)):
+                if isinstance(a, (nn.Linear, nn.Conv2d)) and isinstance(b, (nn.LeakyReLU, nn.ReLU)):
                     slope = float(b.negative_slope) if isinstance(b, nn.LeakyReLU) else 0.0
                     rec = {"lin": a, "slope": slope}
                     self._kink_rec.append(rec)
@@ -523,19 +523,29 @@ class LearnerRef:
         self._kink_handles, self._kink_rec = [], []
 
     def _kink_rows(self, cap=16):
-        """The (row, unit) pre-activations within 4e-6 of sum |a w| (the split GEMM's f32 error bound) of zero, the
-        closest first: [(z, h, row, unit, slope)]."""
+        """The pre-activations within 4e-6 of sum |a w| (the split GEMM's f32 error bound) of zero, the closest first:
+        [(z, h, index, slope)] — index = (row, unit) of a Linear layer's output, (image, channel, y, x) of a
+        convolution's (one output pixel of one image: a convolution is the same sum over its window)."""
         torch = _torch()
         cands = []
         for rec in getattr(self, "_kink_rec", []):
-            if "z" not in rec or rec["z"].dim() != 2:
+            if "z" not in rec or rec["z"].dim() not in (2, 4):
                 continue
-            z, a, W = rec["z"].detach(), rec["a"].detach(), rec["lin"].weight.detach()
-            bound = 4e-6 * (a.abs() @ W.abs().t())
+            z, a, lin = rec["z"].detach(), rec["a"].detach(), rec["lin"]
+            W = lin.weight.detach()
+            if z.dim() == 2:
+                bound = 4e-6 * (a.abs() @ W.abs().t())
+            else:
+                bound = 4e-6 * torch.nn.functional.conv2d(a.abs(), W.abs(), None, lin.stride, lin.padding, lin.dilation,
+                                                          lin.groups)
             r = z.abs() / (bound + 1e-30)
-            idx = ((r <= 1.0) & (bound > 1e-20)).nonzero()   # (an all-zero input row: z is exact on every side)
-            for i, u in idx.tolist():
-                cands.append((float(r[i, u]), rec["z"], rec["h"], i, u, rec["slope"]))
+            ok = (r <= 1.0) & (bound > 1e-20)   # (an all-zero input row: z is exact on every side)
+            idx = ok.nonzero()
+            if len(idx) > cap:   # the closest of this layer are enough: the cap below is over all layers
+                idx = idx[r[ok].argsort()[:cap]]
+            for ix in idx.tolist():
+                ix = tuple(ix)
+                cands.append((float(r[ix]), rec["z"], rec["h"], ix, rec["slope"]))
         cands.sort(key=lambda c: c[0])
         return [c[1:] for c in cands[:cap]]
 
@@ -568,7 +578,7 @@ class LearnerRef:
         e_loss = ent.mean()
         loss = a_loss - self.ent_coef * e_loss + self.vf_coef * c_loss
         self.optimizer.zero_grad()
-        boundary = []
+        boundary, boundary_rows = [], []   # boundary_rows: the minibatch row of each candidate in boundary
         kinks = self._kink_rows() if capture_grads else []
         if capture_grads and self.algo == "ppo":
             # rows whose ratio sits within f32 rounding of a clip bound (the window below): which branch of min() /
@@ -582,23 +592,25 @@ class LearnerRef:
                 g = torch.autograd.grad(-(adv[i] * ratio[i]) / ratio.shape[0], params, retain_graph=True,
                                         allow_unused=True)
                 boundary.append([torch.zeros_like(p) if x is None else x.detach().clone() for p, x in zip(params, g)])
+                boundary_rows.append(i)
         loss.backward(retain_graph=bool(kinks))
         if capture_grads:
             self.last_grads = [p.grad.detach().clone() for p in self.policy.parameters()]
-            # (row, unit) pre-activations within the f32 GEMM's rounding of a (Leaky)ReLU kink: the side the device's
-            # z lands on is not decided by the math either; flipping it changes that row's gradient by
+            # pre-activations (of Linear and Conv2d layers) within the f32 GEMM's rounding of a (Leaky)ReLU kink: the side
+            # the device's z lands on is not decided by the math either; flipping it changes that row's gradient by
             # (s_other - s) dL/dh(row, unit) grad_theta z(row, unit).  Kept per candidate (at most 16) beside the
             # clip-bound rows.
             params = list(self.policy.parameters())
-            for z, h, i, u, slope in kinks:
+            for z, h, ix, slope in kinks:
                 if h.grad is None:
                     continue
-                s_cur = 1.0 if float(z[i, u].detach()) > 0 else slope
-                g = torch.autograd.grad(z[i, u], params, retain_graph=True, allow_unused=True)
-                f = ((slope if s_cur == 1.0 else 1.0) - s_cur) * float(h.grad[i, u])
+                s_cur = 1.0 if float(z[ix].detach()) > 0 else slope
+                g = torch.autograd.grad(z[ix], params, retain_graph=True, allow_unused=True)
+                f = ((slope if s_cur == 1.0 else 1.0) - s_cur) * float(h.grad[ix])
                 boundary.append([torch.zeros_like(p) if x is None else f * x.detach() for p, x in zip(params, g)])
+                boundary_rows.append(ix[0])
             self._kink_hooks_clear()
-            self.boundary_grads = boundary
+            self.boundary_grads, self.boundary_rows = boundary, boundary_rows
         if self.algo == "a2c" or self.use_grad_clip:
             torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.clip_grad_norm)
         self.optimizer.step()

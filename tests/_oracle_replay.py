@@ -39,8 +39,11 @@ def replay_last_step_iteration(agent, D, A, hidden, discrete, algo, ent, n_epoch
                                clip_tol=None, envelope=None, lockstep=False, free_run_updates=None):
     """lockstep: also snapshot the device's weights and (pre-clip) gradients at every update and replay each update from
     the device's own weights (replay_updates: every update's loss scalars at loss_tol and its gradient per tensor, with no
-    drift carried over from earlier updates).  free_run_updates = n: the free-running replay (the oracle stepping its
-    own weights) asserts only its first n updates and not the final weights.
+    drift carried over from earlier updates), and return what that lockstep pass consumed, on the host: {"snaps",
+    "update_log", "records" (replay_updates_lockstep's record per update), "kwargs"} — replay_updates_lockstep(agent,
+    snaps=..., update_log=..., only_updates=[u], **kwargs) re-runs the check on perturbed copies
+    (tests/_lockstep_faults.py) without another device iteration.  free_run_updates = n: the free-running replay (the
+    oracle stepping its own weights) asserts only its first n updates and not the final weights.
     envelope: None, or a factor k — the updates after the first are then held to max(loss_tol, k x a MEASURED f64
     envelope) (replay_updates), the first one (identical starting weights) to loss_tol.
     pol: the oracle policy to replay with (default: the MLP actor-critic of `hidden`); it is loaded with the agent's
@@ -123,9 +126,18 @@ def replay_last_step_iteration(agent, D, A, hidden, discrete, algo, ent, n_epoch
         # returns (held to the f64 GAE above at 1e-5), so that a row whose ratio sits at a clip bound is classified from
         # the same advantage on both sides (r06: the f64 GAE's last-bit differences flipped such rows and moved a
         # first-layer gradient by 2e-3 relative L2 with no difference in the update itself)
-        replay_updates_lockstep(agent, pol, snaps, mem.advantages.cpu().numpy().astype(np.float64),
-                                mem.returns.cpu().numpy().astype(np.float64), discrete, A, algo, ent, n_epoch, n_mb,
-                                perm_counter, loss_tol=loss_tol)
+        adv_dev = mem.advantages.cpu().numpy().astype(np.float64)
+        ret_dev = mem.returns.cpu().numpy().astype(np.float64)
+        records = replay_updates_lockstep(agent, pol, snaps, adv_dev, ret_dev, discrete, A, algo, ent, n_epoch, n_mb,
+                                          perm_counter, loss_tol=loss_tol)
+        # what the lockstep pass consumed, on the host: replay_updates_lockstep(agent, **kwargs, snaps=..., update_log=...)
+        # re-runs the check on (perturbed) copies without another device iteration
+        return {"snaps": [([w.cpu() for w in ws], [g.cpu() for g in gs]) for ws, gs in snaps],
+                "update_log": [x.cpu().numpy().copy() for x in agent.update_log],
+                "records": records,
+                "kwargs": dict(pol=pol, adv=adv_dev, ret=ret_dev, discrete=discrete, A=A, algo=algo, ent=ent,
+                               n_epoch=n_epoch, n_mb=n_mb, perm_counter=perm_counter, loss_tol=loss_tol)}
+    return None
 
 
 def _check_deferred(agent, pol, N, T, term, closed, boot, expect_mid_truncations):
@@ -259,8 +271,139 @@ def replay_updates(agent, pol, opt_state, lr0, sched_epoch, perm_counter, adv, r
         np.testing.assert_allclose(val.detach().cpu().numpy(), ref.numpy(), rtol=1e-3, atol=atol, err_msg=k)
 
 
+def lockstep_check_update(lrn, u, snap, got, batch, ent, vf_coef, loss_tol=1e-4, grad_rtol=1e-3, grads=True,
+                          aux_scalars=False, tensor_rtol=None):
+    """One update of a lockstep replay.  lrn: the f32 oracle learner (cpu_ref.LearnerRef; its step is irrelevant, the
+    weights are reloaded here); snap = (weights, pre-clip gradient) of the device's update u; got: the device's loss
+    scalars in ops.OUT_KEYS order; batch = (obs, act, ret, adv, old_logp) of the minibatch, on the host, the advantages
+    as the loss saw them.  Loads the weights, runs the oracle update, holds the loss scalars to loss_tol * max(1, |x|),
+    lets the oracle's gradient take or drop each boundary candidate (LearnerRef.boundary_grads: clip-bound rows and
+    (Leaky)ReLU kink (row, unit)s, at most 16 each) where that moves it toward the device's — greedy over the
+    candidates, on the whole gradient — and then holds every tensor to grad_rtol in relative L2.
+    grads=False: the loss scalars only (g of snap may be None).  aux_scalars: also predict_value (loss_tol) and, for PPO,
+    the clip fraction to (2 + rows within f32 rounding of a clip bound) / B.  tensor_rtol: {parameter name: a bound
+    that replaces grad_rtol for that tensor}.
+    Returns the update's record: {"update", "candidates" (boundary candidates offered), "flips" (taken), "worst_l2",
+    "worst_name", "l2": {name: relative L2}}."""
+    pol = lrn.policy
+    w_dev, g_dev = snap
+    params = list(pol.parameters())
+    assert len(params) == len(w_dev)
+    with torch.no_grad():
+        for p, w in zip(params, w_dev):
+            p.copy_(torch.as_tensor(w).cpu().to(p.dtype))
+    o, a, r, ad, old_logp = batch
+    info = lrn.update(o, a, r, ad, old_logp, capture_grads=grads)
+    got = np.asarray(torch.as_tensor(got).cpu().numpy(), np.float64)
+    ref_loss = info["actor-loss"] - ent * info["entropy"] + vf_coef * info["critic-loss"]
+    assert abs(got[3] - ref_loss) <= loss_tol * max(1.0, abs(ref_loss)), ("lockstep loss", u, got[3], ref_loss)
+    for j, k in enumerate(("actor-loss", "critic-loss", "entropy")):
+        assert abs(got[j] - info[k]) <= loss_tol * max(1.0, abs(info[k])), ("lockstep", k, u, got[j], info[k])
+    if aux_scalars:
+        pv = info["predict_value"]
+        assert abs(got[5] - pv) <= loss_tol * max(1.0, abs(pv)), ("lockstep", "predict_value", u, got[5], pv)
+        if lrn.algo == "ppo":
+            tol = (2.0 + info["clip_boundary_rows"]) / len(a) + 1e-7
+            assert abs(got[4] - info["clip_ratio"]) <= tol, ("lockstep", "clip_ratio", u, got[4], info["clip_ratio"], tol)
+    rec = {"update": u, "candidates": 0, "flips": 0, "worst_l2": 0.0, "worst_name": None, "l2": {}}
+    if not grads:
+        return rec
+    # candidates at a clip bound or a kink: the device may have taken the other side of any of them; each one's
+    # gradient is added to / removed from the oracle's where that moves it toward the device's, then every tensor is held
+    gr_all = [gr.double() for gr in lrn.last_grads]
+    res = [torch.as_tensor(gd).cpu().double() - gr for gd, gr in zip(g_dev, gr_all)]
+    cands = getattr(lrn, "boundary_grads", [])
+    flips = 0
+    for bg in cands:
+        bg = [b.double() for b in bg]
+        n0 = sum(float((x * x).sum()) for x in res)
+        best = None
+        for sgn in (1.0, -1.0):
+            n1 = sum(float(((x - sgn * b) ** 2).sum()) for x, b in zip(res, bg))
+            if n1 < n0 and (best is None or n1 < best[0]):
+                best = (n1, sgn)
+        if best is not None:
+            res = [x - best[1] * b for x, b in zip(res, bg)]
+            flips += 1
+    rec["candidates"], rec["flips"] = len(cands), flips
+    # the oracle offers at most 16 clip-bound rows and 16 kink candidates: an adaptation with more freedom than that
+    # is not this check
+    assert flips <= len(cands) <= 32, ("lockstep candidates", u, flips, len(cands))
+    for name, rr, gr in zip((n for n, _ in pol.named_parameters()), res, gr_all):
+        l2 = float(rr.norm()) / (float(gr.norm()) + 1e-30)
+        rec["l2"][name] = l2
+        if rec["worst_name"] is None or l2 > rec["worst_l2"]:
+            rec["worst_l2"], rec["worst_name"] = l2, name
+    if os.environ.get("XPA_LOCKSTEP_REPORT"):   # diagnostics: print instead of asserting ("assert": print, then assert)
+        for name, l2 in rec["l2"].items():
+            print("LOCKSTEP", u, name, "%.3e" % l2, "flips", flips, "of", len(cands))
+        if os.environ["XPA_LOCKSTEP_REPORT"] != "assert":
+            return rec
+    for name, l2 in rec["l2"].items():
+        tol = (tensor_rtol or {}).get(name, grad_rtol)
+        assert l2 <= tol, ("lockstep grad (relative L2)", u, name, l2, "boundary flips", flips, "of", len(cands))
+    return rec
+
+
+class LockstepReplay:
+    """The oracle's side of a lockstep replay of one iteration of `agent`: the buffer (the device's advantages / returns
+    given), the device's epoch permutations and the f32 oracle learner.  batch(u) is update u's minibatch as the oracle
+    learner takes it; check(u, snap, got) is lockstep_check_update on it."""
+
+    def __init__(self, agent, pol, adv, ret, discrete, A, algo, ent, n_epoch, n_mb, perm_counter, loss_tol=1e-4,
+                 grad_rtol=1e-3):
+        N, T = agent.n_envs, agent.n_steps
+        cfg, mem = agent.config, agent.memory
+        pol.float()
+        clip = cfg.clip_grad_norm if algo == "ppo" else cfg.clip_grad
+        opt = torch.optim.SGD(pol.parameters(), lr=0.0)   # the step is irrelevant: weights are reloaded per update
+        self.lrn = cpu_ref.LearnerRef(pol, opt, None, algo, cfg.vf_coef, ent, getattr(cfg, "clip_range", 0.2), clip, True)
+        self.algo, self.ent, self.vf_coef, self.clip_range = algo, ent, cfg.vf_coef, getattr(cfg, "clip_range", 0.2)
+        self.loss_tol, self.grad_rtol = loss_tol, grad_rtol
+        self.names = [n for n, _ in pol.named_parameters()]
+        obs_np = mem.observations.cpu().numpy()
+        buf = cpu_ref.BufferRef(obs_np.shape[2:], () if discrete else (A,), {"old_logp": ()} if algo == "ppo" else {},
+                                N, T, obs_dtype=obs_np.dtype)
+        buf.observations[:] = obs_np
+        buf.actions[:] = mem.actions.cpu().numpy()
+        buf.values[:] = mem.values.cpu().numpy()
+        buf.returns[:], buf.advantages[:] = ret, adv
+        if algo == "ppo":
+            buf.auxiliary_infos["old_logp"][:] = mem.auxiliary_infos["old_logp"].cpu().numpy()
+        buf.size = T
+        self.buf = buf
+        self.B = N * T // n_mb
+        self.n_updates = n_epoch * n_mb
+        self.idx = []
+        for e in range(n_epoch):
+            perm = agent.epoch_permutation(N * T, counter=perm_counter + e).cpu().numpy()
+            self.idx += [perm[s:s + self.B] for s in range(0, N * T, self.B)]
+
+    def batch(self, u):
+        o, a, r, _, ad, ax = self.buf.sample(self.idx[u])
+        return o, a, r, ad, ax.get("old_logp")
+
+    def candidate_rows(self, u, snap):
+        """The minibatch rows of the boundary candidates the oracle offers at update u (clip-bound rows, kink rows)."""
+        with torch.no_grad():
+            for p, w in zip(self.lrn.policy.parameters(), snap[0]):
+                p.copy_(torch.as_tensor(w).cpu().to(p.dtype))
+        o, a, r, ad, old_logp = self.batch(u)
+        self.lrn.update(o, a, r, ad, old_logp, capture_grads=True)
+        return list(self.lrn.boundary_rows)
+
+    def row_oracle(self, u, snap):
+        """The f64 per-row oracle of update u at the snapshot's weights (tests/_lockstep_faults.py)."""
+        from tests._lockstep_faults import RowOracle
+        return RowOracle(self.lrn.policy, snap[0], self.batch(u), self.algo, self.ent, self.vf_coef, self.clip_range)
+
+    def check(self, u, snap, got, **kw):
+        return lockstep_check_update(self.lrn, u, snap, got, self.batch(u), self.ent, self.vf_coef,
+                                     loss_tol=self.loss_tol, grad_rtol=self.grad_rtol, **kw)
+
+
 def replay_updates_lockstep(agent, pol, snaps, adv, ret, discrete, A, algo, ent, n_epoch, n_mb, perm_counter,
-                            loss_tol=1e-4, grad_rtol=1e-3):
+                            loss_tol=1e-4, grad_rtol=1e-3, only_updates=None, update_log=None, aux_scalars=False):
     """Every update of the iteration replayed from the device's own weights at that update (snaps[u] = (weights,
     pre-clip gradient) taken as the device update reached its clip + Adam step): the loss scalars within loss_tol, and
     each parameter's gradient within grad_rtol in relative L2 norm.  (Element-wise, a gradient can differ where the math
@@ -270,62 +413,14 @@ def replay_updates_lockstep(agent, pol, snaps, adv, ret, discrete, A, algo, ent,
     the tensor's norm, a wrong or missing row is not.  A whole row's unclipped gradient is not: one such row of C4's
     8192-row minibatch moved the first layer's gradient by 2.3e-3 — so the oracle's gradient may take or drop each
     clip-bound row's contribution, r06.)  No drift is carried between updates, so no envelope is needed
-    (ppoclip_learner.py:24-65)."""
-    N, T = agent.n_envs, agent.n_steps
-    cfg, mem = agent.config, agent.memory
-    pol.float()
-    clip = cfg.clip_grad_norm if algo == "ppo" else cfg.clip_grad
-    opt = torch.optim.SGD(pol.parameters(), lr=0.0)   # the step is irrelevant: weights are reloaded per update
-    lrn = cpu_ref.LearnerRef(pol, opt, None, algo, cfg.vf_coef, ent, getattr(cfg, "clip_range", 0.2), clip, True)
-    obs_np = mem.observations.cpu().numpy()
-    buf = cpu_ref.BufferRef(obs_np.shape[2:], () if discrete else (A,), {"old_logp": ()} if algo == "ppo" else {}, N, T,
-                            obs_dtype=obs_np.dtype)
-    buf.observations[:] = obs_np
-    buf.actions[:] = mem.actions.cpu().numpy()
-    buf.values[:] = mem.values.cpu().numpy()
-    buf.returns[:], buf.advantages[:] = ret, adv
-    if algo == "ppo":
-        buf.auxiliary_infos["old_logp"][:] = mem.auxiliary_infos["old_logp"].cpu().numpy()
-    buf.size = T
-    B = N * T // n_mb
-    assert len(snaps) == n_epoch * n_mb == len(agent.update_log)
-    params = list(pol.parameters())
-    u = 0
-    for e in range(n_epoch):
-        perm = agent.epoch_permutation(N * T, counter=perm_counter + e).cpu().numpy()
-        for s in range(0, N * T, B):
-            w_dev, g_dev = snaps[u]
-            with torch.no_grad():
-                for p, w in zip(params, w_dev):
-                    p.copy_(w.cpu().to(p.dtype))
-            o, a, r, _, ad, ax = buf.sample(perm[s:s + B])
-            info = lrn.update(o, a, r, ad, ax.get("old_logp"), capture_grads=True)
-            got = agent.update_log[u].cpu().numpy()   # ops.OUT_KEYS order
-            ref_loss = info["actor-loss"] - ent * info["entropy"] + cfg.vf_coef * info["critic-loss"]
-            assert abs(got[3] - ref_loss) <= loss_tol * max(1.0, abs(ref_loss)), ("lockstep loss", u, got[3], ref_loss)
-            for j, k in enumerate(("actor-loss", "critic-loss", "entropy")):
-                assert abs(got[j] - info[k]) <= loss_tol * max(1.0, abs(info[k])), ("lockstep", k, u, got[j], info[k])
-            # rows at a clip bound (LearnerRef.boundary_grads): the device may have taken the other branch for any of
-            # them; each such row's unclipped gradient is added to / removed from the oracle's where that moves it
-            # toward the device's (greedy over the rows, on the whole gradient), then every tensor is held to grad_rtol
-            gr_all = [gr.double() for gr in lrn.last_grads]
-            res = [gd.cpu().double() - gr for gd, gr in zip(g_dev, gr_all)]
-            flips = 0
-            for bg in getattr(lrn, "boundary_grads", []):
-                bg = [b.double() for b in bg]
-                n0 = sum(float((x * x).sum()) for x in res)
-                best = None
-                for sgn in (1.0, -1.0):
-                    n1 = sum(float(((x - sgn * b) ** 2).sum()) for x, b in zip(res, bg))
-                    if n1 < n0 and (best is None or n1 < best[0]):
-                        best = (n1, sgn)
-                if best is not None:
-                    res = [x - best[1] * b for x, b in zip(res, bg)]
-                    flips += 1
-            for name, rr, gr in zip((n for n, _ in pol.named_parameters()), res, gr_all):
-                l2 = float(rr.norm()) / (float(gr.norm()) + 1e-30)
-                if os.environ.get("XPA_LOCKSTEP_REPORT"):
-                    print("LOCKSTEP", u, name, "%.3e" % l2, "flips", flips)
-                    continue
-                assert l2 <= grad_rtol, ("lockstep grad (relative L2)", u, name, l2, "boundary flips", flips)
-            u += 1
+    (ppoclip_learner.py:24-65).
+    only_updates: an iterable of update indices — only those are replayed (a perturbed record re-runs one update).
+    update_log: the device's loss scalars per update (default: agent.update_log).  Returns lockstep_check_update's
+    record of every replayed update."""
+    rp = LockstepReplay(agent, pol, adv, ret, discrete, A, algo, ent, n_epoch, n_mb, perm_counter, loss_tol, grad_rtol)
+    log = agent.update_log if update_log is None else update_log
+    assert len(snaps) == rp.n_updates == len(log)
+    only = None if only_updates is None else set(int(x) for x in only_updates)
+    assert only is None or all(0 <= x < rp.n_updates for x in only)
+    return [rp.check(u, snaps[u], log[u], aux_scalars=aux_scalars)
+            for u in range(rp.n_updates) if only is None or u in only]

@@ -121,8 +121,65 @@ def _gae_close(got, ref):
     assert not bad.any(), ("GAE mismatch", int(bad.sum()), float(np.abs(got - ref)[bad].max()))
 
 
-def _replay_atari(g, env, conv_path, efac=3, rtol=1e-4, base_atol=1e-5):
-    """Replay a G8 / G12 fixture (make_golden.capture_atari) through the device buffer and the learner the agent uses:
+LOCKSTEP_GRAD_UPDATES = (0, 1, 12, 20)   # and the last: the updates whose gradient is checked in lockstep
+
+
+def _lockstep_hooks(lrn, pol, cap):
+    """Record, per device update, the weights the update started from and its pre-clip gradient (as the learner reaches
+    its clip + Adam step, the hook tests/_oracle_replay.py uses) and the loss scalars update_fused returns."""
+    orig_step, orig_fused = lrn._sync_clip_step, lrn.update_fused
+
+    def snap_step(*a, **kw):
+        cap["w"] = [v.detach().clone() for v in pol.state_dict().values()]
+        cap["g"] = [p.grad.detach().clone() for p in pol.parameters()] if cap["want_grad"] else None
+        return orig_step(*a, **kw)
+
+    def fused(*a, **kw):
+        s = orig_fused(*a, **kw)
+        cap["scalars"] = s.detach().clone()
+        return s
+    lrn._sync_clip_step, lrn.update_fused = snap_step, fused
+
+
+def _lockstep_atari_update(ls, cap, u, batch, control):
+    """Update u of a G8P / G12P replay in lockstep: the CNN oracle (cpu_ref.build_atari_ac_ref) at the device's weights of
+    this update, on the same minibatch — every loss scalar (actor-loss, critic-loss, entropy, predict_value, the total)
+    to 1e-4 max(1, |x|) and the clip fraction to (2 + clip-bound rows) / B on every update, every tensor's gradient to
+    1e-3 relative L2 (boundary and kink adaptation as for the MLP replays) at LOCKSTEP_GRAD_UPDATES and the last.
+    control: at update 12 also the negative controls (the first conv weight's gradient scaled by 1 + 2e-3; the critic
+    loss off by 2e-4) — both must be red."""
+    import time
+    from tests import _lockstep_faults as faults
+    from tests._oracle_replay import lockstep_check_update
+    t0 = time.perf_counter()
+    o, a, r, ad, old_logp = batch
+    host = (o.cpu().numpy(), a.cpu().numpy().astype(np.int64).reshape(-1), r.cpu().numpy(), ad.cpu().numpy(),
+            None if old_logp is None else old_logp.cpu().numpy())
+    assert host[0].dtype == np.uint8
+    grads = cap["g"] is not None
+    snap, got = (cap["w"], cap["g"]), cap["scalars"].cpu().numpy()
+    lrn = ls["lrn"]
+    assert [tuple(w.shape) for w in snap[0]] == [tuple(p.shape) for p in lrn.policy.parameters()]
+    rec = lockstep_check_update(lrn, u, snap, got, host, ls["ent"], ls["vf"], grads=grads, aux_scalars=True)
+    if grads:
+        ls["records"].append(rec)
+        assert rec["flips"] <= rec["candidates"] <= 32
+    if control and u == 12:
+        names = [n for n, _ in lrn.policy.named_parameters()]
+        conv1 = "representation.model.0.weight"
+        assert names[0] == conv1 and snap[0][0].dim() == 4
+        (f_snaps, f_log) = faults.scale_grad([snap], [got], 0, names, conv1)
+        with pytest.raises(AssertionError, match=r"lockstep grad \(relative L2\)', 12, 'representation\.model\.0\.weight'"):
+            lockstep_check_update(lrn, u, f_snaps[0], f_log[0], host, ls["ent"], ls["vf"], aux_scalars=True)
+        (f_snaps, f_log) = faults.bias_scalar([snap], [got], 0, "critic-loss")
+        with pytest.raises(AssertionError, match=r"'lockstep', 'critic-loss', 12"):
+            lockstep_check_update(lrn, u, f_snaps[0], f_log[0], host, ls["ent"], ls["vf"], aux_scalars=True)
+    ls["seconds"] += time.perf_counter() - t0
+
+
+def _replay_atari(g, env, conv_path, efac=3, rtol=1e-4, base_atol=1e-5, lockstep=False, control=False):
+    """lockstep: also every update in lockstep with the CNN oracle (_lockstep_atari_update).
+    Replay a G8 / G12 fixture (make_golden.capture_atari) through the device buffer and the learner the agent uses:
     A2C_Learner (algo 0) or PPOCLIP_Learner (algo 1, old_logp from the buffer's aux column, clip_ratio checked).
     Loss scalars: rtol 1e-4 + max(base_atol, efac x the fixture's f64 envelope) — update 0 (identical starting weights)
     at the base tolerance; GAE at 1e-5 (_gae_close)."""
@@ -164,6 +221,16 @@ def _replay_atari(g, env, conv_path, efac=3, rtol=1e-4, base_atol=1e-5):
     obs = np.stack([e.reset()[0] for e in envs])
     B = N * T // n_mb
     u = k = 0
+    n_updates = len(g["infos"])
+    if lockstep:
+        from oracle import cpu_ref
+        pol_ref = cpu_ref.build_atari_ac_ref(K, filters, kernels, strides, fc)
+        assert len(list(pol_ref.parameters())) == len(pol.state_dict()) == len(list(pol.parameters()))
+        ls = {"lrn": cpu_ref.LearnerRef(pol_ref, torch.optim.SGD(pol_ref.parameters(), lr=0.0), None,
+                                        "ppo" if ppo else "a2c", vf, ent, clip, gn, True),
+              "ent": ent, "vf": vf, "records": [], "seconds": 0.0}
+        cap = {"want_grad": False}
+        _lockstep_hooks(lrn, pol, cap)
     keys = ["actor-loss", "critic-loss", "entropy", "learning_rate", "predict_value"] + (["clip_ratio"] if ppo else [])
     for it in range(g["act"].shape[0]):
         for t in range(T):
@@ -196,6 +263,8 @@ def _replay_atari(g, env, conv_path, efac=3, rtol=1e-4, base_atol=1e-5):
             for s in range(0, N * T, B):
                 o, a, r, v, ad, ax = buf.sample(perm[s:s + B])
                 assert o.dtype == torch.uint8
+                if lockstep:
+                    cap["want_grad"] = u in LOCKSTEP_GRAD_UPDATES or u == n_updates - 1
                 info = lrn.update(o, a, r, v, ad, ax["old_logp"]) if ppo else lrn.update(o, a, r, ad)
                 got = [float(info[kk]) for kk in keys]
                 ev = env["info"][u] if env is not None else np.zeros(len(keys))
@@ -208,9 +277,19 @@ def _replay_atari(g, env, conv_path, efac=3, rtol=1e-4, base_atol=1e-5):
                     dev = np.abs(np.asarray(got, np.float64) - g["infos"][u])
                     print("ENVELOPE u=%d dev/env=%s" % (u, np.round(dev / np.maximum(ev, 1e-12), 2)))
                 _close(got, g["infos"][u], rtol, atol, "update %d" % u)
+                if lockstep:
+                    _lockstep_atari_update(ls, cap, u, (o, a, r, ad, ax["old_logp"] if ppo else None), control)
                 u += 1
         buf.clear()
-    assert u == len(g["infos"])
+    assert u == n_updates
+    if lockstep:
+        assert [rc["update"] for rc in ls["records"]] == sorted(
+            {x for x in LOCKSTEP_GRAD_UPDATES if x < n_updates} | {n_updates - 1})
+        worst = max(ls["records"], key=lambda rc: rc["worst_l2"])
+        print("LOCKSTEP-ATARI %s: %d updates, oracle %.1f s, worst relative L2 %.3e (%s, update %d), candidates %s, "
+              "flips %s" % ("ppo" if ppo else "a2c", n_updates, ls["seconds"], worst["worst_l2"], worst["worst_name"],
+                            worst["update"], [rc["candidates"] for rc in ls["records"]],
+                            [rc["flips"] for rc in ls["records"]]))
     _check_sd1(pol, g, rtol=1e-3, atol=5e-5, env=env, efac=efac)
 
 
@@ -227,10 +306,12 @@ def test_a2c_atari_replays_reference_agent(golden, fixture, conv_path):
     512; 8 envs x 64 steps, minibatches of 256) replayed update by update.  A few Adam steps of an f32 net are
     chaotic in the last bits (tests/golden/make_envelopes.py): the prod fixture carries, per update and per tensor, how
     far the exact f64 replay lands from the reference, and the tolerances are max(base, 3 x that envelope) — update 0
-    (identical starting weights) is held to the base tolerances (1e-4 relative + 1e-5)."""
+    (identical starting weights) is held to the base tolerances (1e-4 relative + 1e-5).  G8P is also held in lockstep
+    (_lockstep_atari_update): every update's loss scalars against the CNN oracle at the device's weights of that update,
+    and the gradient at updates 0, 1 and the last."""
     g = golden(fixture)
     env = golden(fixture.replace(".npz", "_env.npz")) if "init_seed" in g else None
-    _replay_atari(g, env, conv_path)
+    _replay_atari(g, env, conv_path, lockstep=fixture.endswith("_prod.npz"))
 
 
 @pytest.mark.parametrize("fixture", ["atari_ppo.npz", "atari_ppo_prod.npz"])
@@ -241,10 +322,14 @@ def test_ppo_atari_replays_reference_agent(golden, fixture, conv_path):
     ent 0.01; 4 epochs x 4 minibatches), two recorded iterations, small and production AC_CNN_Atari — replayed
     through the device buffer (old_logp column), FusedCNNActorCritic and K2 in PPO mode (ratio / clip / old_logp,
     clip fraction): GAE at 1e-5, update 0's loss scalars at 1e-4 relative + 1e-5, later updates within 3x the
-    fixture's measured f64 envelope (make_envelopes.py), the final weights likewise."""
+    fixture's measured f64 envelope (make_envelopes.py), the final weights likewise.  G12P is also held in lockstep
+    (_lockstep_atari_update): every update's loss scalars and clip fraction against the CNN oracle at the device's
+    weights of that update (the envelope is as large as the quantities themselves from update ~12 on), the gradient at
+    updates 0, 1, 12, 20 and the last, and two negative controls at update 12."""
     g = golden(fixture)
     env = golden(fixture.replace(".npz", "_env.npz"))
-    _replay_atari(g, env, conv_path)
+    prod = fixture.endswith("_prod.npz")
+    _replay_atari(g, env, conv_path, lockstep=prod, control=prod)
 
 
 def test_atari_deferred_last_bootstrap_matches_per_step():

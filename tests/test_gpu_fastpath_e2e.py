@@ -248,3 +248,87 @@ def test_s3r_trunk_iteration_equals_k13_k16p(monkeypatch):
     for p1, i1 in runs[1:]:
         assert len(p0) == len(p1) and all(torch.equal(a, b) for a, b in zip(p0, p1))
         assert i0 == i1
+
+
+def _controls_on_device_record(agent, D, A, H, n_epoch, n_mb, free_run_updates, label):
+    """One device iteration replayed in lockstep (it must pass), then every fault of tests/_lockstep_faults.py but
+    wrong_branch injected into host copies of what that pass consumed, at one middle update: each must turn the check
+    red at its intended assertion.  No kernel runs for a fault."""
+    from tests import _lockstep_faults as faults
+    from tests._oracle_replay import LockstepReplay, replay_updates_lockstep
+    out = replay_last_step_iteration(agent, D, A, [H], False, "ppo", 0.0, n_epoch, n_mb, expect_mid_truncations=True,
+                                     lockstep=True, free_run_updates=free_run_updates)
+    snaps, log, kw, recs = out["snaps"], out["update_log"], out["kwargs"], out["records"]
+    worst = max(recs, key=lambda r: r["worst_l2"])
+    print("LOCKSTEP-CONTROL %s clean: worst relative L2 %.3e (%s, update %d), candidates %s, flips %s" % (
+        label, worst["worst_l2"], worst["worst_name"], worst["update"], [r["candidates"] for r in recs],
+        [r["flips"] for r in recs]))
+    assert len(recs) == n_epoch * n_mb and all(r["flips"] <= r["candidates"] <= 32 for r in recs)
+    grad_rtol, loss_tol = 1e-3, kw["loss_tol"]
+    u = n_epoch * n_mb // 2
+    rp = LockstepReplay(agent, **kw)
+    cand = rp.candidate_rows(u, snaps[u])
+    dropped = faults.drop_rows(snaps, log, u, rp.row_oracle(u, snaps[u]), cand, grad_rtol)
+    print("LOCKSTEP-CONTROL %s drop_rows: k = %d of B = %d" % (label, dropped[2], rp.B))
+    assert dropped[2] <= rp.B // 64
+    out_w, first_w = "actor.mu.2.weight", "representation.model.0.weight"
+    assert out_w in rp.names and first_w in rp.names
+    grad = r"lockstep grad \(relative L2\)', %d" % u
+    controls = [("scale_grad " + n, faults.scale_grad(snaps, log, u, rp.names, n, grad_rtol), [u],
+                 grad + ", '%s'" % n.replace(".", r"\.")) for n in (out_w, first_w)]
+    controls.append(("drop_rows", dropped[:2], [u], grad))
+    controls.append(("swap_updates", faults.swap_updates(snaps, log, u), [u], "lockstep"))
+    controls.append(("swap_logs", faults.swap_logs(snaps, log, u), [u],
+                     r"lockstep loss|'lockstep', '(actor-loss|critic-loss|entropy)'"))
+    controls += [("bias_scalar " + k, faults.bias_scalar(snaps, log, u, k, loss_tol), [u],
+                  r"'lockstep', '%s', %d" % (k, u)) for k in ("actor-loss", "critic-loss", "entropy")]
+    import re
+    missed = []
+    for name, (f_snaps, f_log), only, match in controls:
+        try:
+            got = replay_updates_lockstep(agent, snaps=f_snaps, update_log=f_log, only_updates=only, **kw)
+        except AssertionError as e:
+            if not re.search(match, str(e)):
+                missed.append((name, "red at another assertion", str(e)))
+            continue
+        missed.append((name, "not red", [(r["flips"], r["candidates"], r["worst_l2"], r["worst_name"]) for r in got]))
+    assert not missed, missed
+
+
+def test_lockstep_controls_on_fast_path_record():
+    """Negative controls for the lockstep replay on real device data, C2 fast path (the path assertions of
+    test_fast_path_iteration_matches_oracle) at N x T = 256 x 32, minibatches of 2048: the clean iteration passes, every
+    injected fault (a tensor's gradient scaled by 1 + 2e-3, k rows dropped from the minibatch gradient, the snapshots /
+    loss scalars of two updates exchanged, one loss scalar off by 2e-4) is red."""
+    from xuanpolicy_amd.runner import build_synthbox_ppo
+    N, T, D, A, H = 256, 32, 17, 6, 256
+    agent = build_synthbox_ppo(n_envs=N, n_steps=T, obs_dim=D, act_dim=A, hidden=H, n_epoch=2, n_minibatch=4, seed=13,
+                               device=DEV, agent="PPO_Clip", discrete=False, ent_coef=0.0, max_episode_steps=T + 17)
+    fm = agent.learner._fused_mlp()
+    assert fm is not None and fm.fused_heads and fm.gemm_heads and fm.thin0 and fm.pair is not None
+    assert agent.defer_boot and agent.use_graph
+    assert agent._env_fused(fm)
+    agent.train(T, log=False)
+    agent.train(T - 1, log=False)
+    _controls_on_device_record(agent, D, A, H, 2, 4, None, "C2")
+
+
+def test_lockstep_controls_on_c4_shape_record(monkeypatch):
+    """The same negative controls on the C4 shape (SynthBox(376, 17), the wide trunk read through idx), whose updates
+    after the first are held by the lockstep replay alone."""
+    from xuanpolicy_amd.fused_mlp import FusedActorCritic
+    from xuanpolicy_amd.runner import build_synthbox_ppo
+    monkeypatch.setattr(FusedActorCritic, "WIDE_TRUNK", True)
+    monkeypatch.setattr(FusedActorCritic, "WIDE_DIRECT", True)
+    N, T, D, A, H = 256, 32, 376, 17, 256
+    agent = build_synthbox_ppo(n_envs=N, n_steps=T, obs_dim=D, act_dim=A, hidden=H, n_epoch=2, n_minibatch=4, seed=17,
+                               device=DEV, max_episode_steps=T + 17)
+    fm = agent.learner._fused_mlp()
+    assert fm is not None and fm.fused_heads and fm.gemm_heads and not fm.thin0 and fm.pair is not None
+    assert agent.defer_boot and agent.n_slots == 1 and not agent._env_fused(fm)
+    agent.train(T, log=False)
+    agent.train(T - 1, log=False)
+    _controls_on_device_record(agent, D, A, H, 2, 4, 1, "C4")
+    assert fm._wide_on()
+    keys = {k[0] for k in fm._partials if isinstance(k, tuple)}
+    assert "wide_bwd" in keys and "wide_x" not in keys, keys

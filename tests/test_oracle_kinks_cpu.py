@@ -38,3 +38,36 @@ def test_kink_candidate_is_the_other_side_gradient():
             assert float(g.abs().sum()) == 0, n
     # the weight row is the bias entry times x_row (grad_theta z = (x_row, 1))
     torch.testing.assert_close(w0[2], b0[2] * x[3], rtol=1e-5, atol=1e-9)
+
+
+def test_conv_kink_candidate_is_the_other_side_gradient():
+    """The same for a convolution's output pixel (the CNN oracle of the Atari replays): one (image, channel, y, x)
+    pre-activation of the first conv inside the rounding window is offered, its candidate is nonzero only in that
+    channel's filter and bias, and the filter entry is the bias entry times the input window."""
+    torch.manual_seed(0)
+    pol = cpu_ref.build_atari_ac_ref(3, filters=(4, 4), kernels=(4, 3), strides=(2, 1), fc=(16,), in_shape=(12, 12, 2))
+    B = 8
+    obs = np.random.default_rng(1).integers(0, 256, size=(B, 12, 12, 2)).astype(np.uint8)
+    conv0 = pol.representation.model[0]
+    n, c, y, x = 5, 2, 3, 1
+    xin = torch.as_tensor(np.transpose(obs / 255.0, (0, 3, 1, 2)), dtype=torch.float32)
+    pad = torch.nn.functional.pad(xin, (1, 1, 1, 1))            # padding (k - s) // 2 = 1
+    win = pad[n, :, 2 * y:2 * y + 4, 2 * x:2 * x + 4]
+    with torch.no_grad():
+        conv0.bias[c] = -float((win * conv0.weight[c]).sum()) + 1e-9
+    lrn = cpu_ref.LearnerRef(pol, torch.optim.SGD(pol.parameters(), lr=0.0), None, "a2c", 0.25, 0.01, 0.0, 0.5, True)
+    act = np.random.default_rng(2).integers(0, 3, size=B)
+    ret = np.random.default_rng(3).normal(size=B).astype(np.float32)
+    adv = np.random.default_rng(4).normal(size=B).astype(np.float32)
+    lrn.update(obs, act, ret, adv, None, capture_grads=True)
+    assert len(lrn.boundary_grads) >= 1 and lrn.boundary_rows[0] == n
+    names = [k for k, _ in pol.named_parameters()]
+    first = dict(zip(names, lrn.boundary_grads[0]))
+    w0, b0 = first["representation.model.0.weight"], first["representation.model.0.bias"]
+    others = [i for i in range(4) if i != c]
+    assert float(b0[c].abs()) > 0 and float(w0[c].abs().sum()) > 0
+    assert float(w0[others].abs().sum()) == 0 and float(b0[others].abs().sum()) == 0
+    for k, g in first.items():
+        if not k.startswith("representation.model.0."):
+            assert float(g.abs().sum()) == 0, k
+    torch.testing.assert_close(w0[c], b0[c] * win, rtol=1e-5, atol=1e-9)
