@@ -109,16 +109,26 @@ def test_fast_path_iteration_with_split_gemms_matches_oracle(agent_name, discret
     assert fm is not None and fm.gemm_heads and fm.pair is not None
     agent.train(T, log=False)
     agent.train(T - 1, log=False)
+    plan = fm.last_plan   # beside each workspace-key check: what the update's plan says it ran
     if crit:
         assert any(k[0] == "wgrad_pair" for k in fm._partials if isinstance(k, tuple)), "K41P not used"
+        assert plan.dw_hidden == "K41P"
         assert any(k[0] == "crit" for k in fm._partials if isinstance(k, tuple)), "the factored critic not used"
+        assert plan.heads == "K16Q-mask" and plan.trunk_bwd == "K42C"
     else:
         assert any(k[0] == "s3wgrad" for k in fm._partials if isinstance(k, tuple)), "K41 not used"
+        assert plan.dw_hidden == "K41V"
     assert any(k[0] == "s3split" for k in fm._partials if isinstance(k, tuple)), "K40 not used"
+    assert plan.splits[-1] == ("dx_crit" if crit else "dx")
     if heads in ("s3p", "s3q"):
         assert any(k[:2] == ("s3split", "s3p_a") for k in fm._partials if isinstance(k, tuple)), "K16P not used"
+        assert plan.splits[:2] == ("s3p_a", "s3p_c") and plan.heads.startswith("K16P" if heads == "s3p" else "K16Q")
         assert any(k[0] == "hsign" for k in fm._partials if isinstance(k, tuple)), "K16R / K42S not used"
+        assert plan.sign_bits == "K13"
+    else:
+        assert plan.heads == "K16S"
     assert any(k[0] == "k42" for k in fm._partials if isinstance(k, tuple)), "K42 not used"
+    assert plan.trunk_bwd in ("K42C", "K42S")
     replay_last_step_iteration(agent, D, A, [H], discrete, "ppo" if agent_name == "PPO_Clip" else "a2c", 0.01, 2, 4,
                                expect_mid_truncations=not discrete)
 
@@ -158,6 +168,9 @@ def test_c4_shape_iteration_matches_oracle(mode, monkeypatch):
     assert fm._wide_on() == wide
     keys = {k[0] for k in fm._partials if isinstance(k, tuple)}
     assert ("wide_bwd" in keys) == wide and ("wide_x" in keys) == (mode == "gather"), keys
+    plan = fm.last_plan
+    assert (plan.trunk_bwd == "K42C-dz") == wide and (plan.trunk_fwd == "K40F-pitched") == (mode == "gather"), plan
+    assert plan.trunk_fwd == {"direct": "K40F-idx", "gather": "K40F-pitched", "off": "chain"}[mode], plan
 
 
 def test_deferred_bootstraps_with_several_truncations_per_rollout():
@@ -195,6 +208,7 @@ def test_fast_path_iteration_with_f32_gemms_matches_oracle(agent_name, discrete,
     agent.train(T, log=False)
     agent.train(T - 1, log=False)
     assert not any(isinstance(k, tuple) and k[0] in ("s3split", "s3wgrad") for k in fm._partials)
+    assert fm.last_plan.splits == () and fm.last_plan.dw_hidden == "splitk" and fm.last_plan.heads == "K16"
     replay_last_step_iteration(agent, D, A, [H], discrete, "ppo" if agent_name == "PPO_Clip" else "a2c", 0.01, 2, 4,
                                expect_mid_truncations=not discrete)
 
@@ -239,10 +253,12 @@ def test_s3r_trunk_iteration_equals_k13_k16p(monkeypatch):
         agent = build_synthbox_ppo(n_envs=256, n_steps=32, obs_dim=17, act_dim=6, hidden=256, n_epoch=2,
                                    n_minibatch=4, seed=3, device="cuda:0")
         fm = agent.learner._fused_mlp()
-        assert fm is not None and fm.trunk_heads and fm._s3r_on() == s3r
+        assert fm is not None and fm.trunk_heads
         agent.train(32)
         torch.cuda.synchronize()
+        assert (fm.last_plan.heads == "K16R") == s3r and fm.last_plan.heads == ("K16R" if s3r else "K16P")
         assert any(isinstance(k, tuple) and k[0] == "hsign" for k in fm._partials) == (s3r or sign)
+        assert fm.last_plan.sign_bits == ("K16R" if s3r else "K13" if sign else None)
         runs.append(([p.detach().clone() for p in agent.policy.parameters()], [dict(i) for i in agent.infos]))
     p0, i0 = runs[0]
     for p1, i1 in runs[1:]:
@@ -332,3 +348,4 @@ def test_lockstep_controls_on_c4_shape_record(monkeypatch):
     assert fm._wide_on()
     keys = {k[0] for k in fm._partials if isinstance(k, tuple)}
     assert "wide_bwd" in keys and "wide_x" not in keys, keys
+    assert fm.last_plan.trunk_fwd == "K40F-idx" and fm.last_plan.trunk_bwd == "K42C-dz"

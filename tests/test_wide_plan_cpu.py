@@ -84,13 +84,16 @@ def test_wide_direct_respects_k41v_index_stage(d, B, direct):
 
 
 def test_trunk_backward_form_and_crit_plan_share_one_predicate():
-    """the factored critic is planned only where the fused trunk backward form applies (one predicate,
-    _trunk_bwd_form), and the planned backward raises instead of being stripped under python -O."""
-    import inspect
+    """the factored critic is planned only where a fused trunk backward runs — both are fields of one
+    UpdatePlan now (tests/test_update_plan_cpu.py walks every switch and input) — and a stage handed a plan it cannot
+    run raises, which python -O does not strip."""
     from xuanpolicy_amd.fused_mlp import FusedActorCritic
-    src = inspect.getsource(FusedActorCritic.loss_backward)
-    assert "assert self._trunk_bwd_fused" not in src and "RuntimeError" in src
-    assert "_trunk_bwd_form" in inspect.getsource(FusedActorCritic._crit_plan)
     fm = FusedActorCritic(cpu_ref.build_actor_critic_ref(17, 6, [256], [256], [256]))
     x = torch.zeros(8, 17)
-    assert fm._trunk_bwd_form(torch.zeros(8, 256), x, [torch.zeros(8, 256)]) is None   # no paired layer: no fused form
+    plan = fm.plan(x)
+    assert plan.trunk_bwd == "chain" and plan.dw_hidden == "splitk"   # no paired layer: no fused form
+    assert not hasattr(fm, "_trunk_bwd_form") and not hasattr(fm, "_crit_plan")
+    with pytest.raises(RuntimeError, match="no form"):
+        fm._trunk_backward(plan._replace(trunk_bwd="K99"), None, x, [], None)
+    with pytest.raises(RuntimeError, match="no form"):
+        fm._rep_forward(x, "K99")

@@ -18,6 +18,7 @@ kept (LeakyReLU/ReLU/tanh derivatives are functions of the output), no pre-activ
 Every parameter gradient is overwritten each update, so no zeroing pass is needed.
 """
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -98,8 +99,7 @@ class Rows:
         self.flat, self.idx = flat, idx
         self.gathered = None   # set by the gather forward: the rows as a contiguous [B, d] copy
         self.trunk = None      # K16X: (gathered rows, W0, b0, slope, h out) when the head launches form h
-        self.hsign = None      # K13's sign bits of h (int32 [B, 8]) for K42S
-        self.wide_direct = False   # r05: the wide trunk read these rows through idx (no gathered copy)
+        self.hsign = None      # K13's / K40F's sign bits of h (int32 [B, 8]) for K42S / K42W
         self.shape = (idx.shape[0], flat.shape[1])
         self.device = flat.device
         self.dtype = flat.dtype
@@ -109,6 +109,61 @@ def _vec4_rows(t):
     """The split GEMMs (K40 / K41 / K42) read operands as 16-B vectors: unit column stride, a row stride that is a
     multiple of 4 floats and a 16-B aligned base.  Anything else takes the f32 library / chain path."""
     return t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+def _no_form(stage, form):
+    """The one error of a stage handed a plan it cannot run (a raise, not an assert: python -O must not strip it)."""
+    raise RuntimeError("update plan: %s has no form %r" % (stage, form))
+
+
+_TRUNK_FWD = {   # UpdatePlan.trunk_fwd -> the entry points it launches
+    "chain": (), "K13": ("xpa_thin_linear_act_fwd",), "K13-gather": ("xpa_thin_linear_act_fwd_gather",),
+    "K13-gather-sign": ("xpa_thin_linear_act_fwd_gather_sign",), "K13-gather-only": ("xpa_thin_linear_act_fwd_gather",),
+    "K40F-idx": ("xpa_s3_split_batch_padded", "xpa_s3_gemm_bias_act_rows"),
+    "K40F-pitched": ("xpa_gather_minibatch_pitched", "xpa_s3_split_batch_padded", "xpa_s3_gemm_bias_act")}
+_DW_HIDDEN = {"K41P": ("xpa_s3_wgrad_pair_slices", "xpa_s3_wgrad_pair_slices", "xpa_s3_wgrad_pair"),
+              "K41V": ("xpa_s3_wgrad",), "splitk": ()}
+_TRUNK_BWD = {
+    "none": (), "K42C": ("xpa_s3_gemm_trunk_bwd_crit",), "K42S": ("xpa_s3_gemm_trunk_bwd_sign",),
+    "K42": ("xpa_s3_gemm_trunk_bwd",), "K42C-dz": ("xpa_s3_gemm_trunk_bwd_crit_dz",),
+    "K42W": ("xpa_s3_gemm_trunk_bwd_dz",), "K40+chain": ("xpa_s3_gemm",), "mm+chain": (), "chain": ()}
+
+
+class UpdatePlan(NamedTuple):
+    """The kernel form of every stage of one minibatch update (forward_hidden + loss_backward).  FusedActorCritic.plan
+    chooses it once per (switches, input geometry); the stages dispatch on these fields and test no capability of their
+    own ("Where the update's forms are decided")."""
+    trunk_fwd: str     # "chain" | "K13" | "K13-gather" | "K13-gather-sign" | "K13-gather-only" | "K40F-idx" | "K40F-pitched"
+    hidden: str        # the heads' hidden layers: "heads" (inside the head kernels) | "pair" (one F.linear) | "chains"
+    heads: str         # an ops.HEAD_FORMS name
+    splits: tuple      # the buffer names of _split_many's one launch, in order
+    dw_hidden: str     # "K41P" | "K41V" | "splitk"
+    trunk_bwd: str     # "K42C" | "K42S" | "K42" | "K42C-dz" | "K42W" | "K40+chain" | "mm+chain" | "chain" | "none"
+    sign_bits: object  # who writes h's sign bits: "K13" | "K16R" | "K40F" | None
+    early_sync: bool   # the paired layer's dW finalized and all-reduced ahead of the trunk backward
+
+    def launches(self, adv_moments=True):
+        """The library entry points one update calls, in order, up to and including the finalize flush.  A library
+        chain's own launches (K10 / K11 of a deeper representation or of unpaired heads) are not counted: the chain
+        forms list K13's backward of a one-layer thin trunk only."""
+        out = list(_TRUNK_FWD[self.trunk_fwd])
+        if self.trunk_fwd == "K40F-idx" and adv_moments:
+            out.insert(0, "xpa_gather_minibatch")   # K4 on zero-width rows: the advantage moments alone
+        if self.splits:
+            out.append("xpa_s3_split_batch_scaled" if "dx_crit" in self.splits else "xpa_s3_split_batch")
+        out += ops.HEAD_FORMS[self.heads]
+        if self.hidden != "chains":
+            out += _DW_HIDDEN[self.dw_hidden]
+        if self.early_sync:
+            out.append("xpa_colsum_finalize_batch")
+        out += _TRUNK_BWD[self.trunk_bwd]
+        wide = self.trunk_bwd in ("K42W", "K42C-dz")
+        if wide:
+            out.append("xpa_s3_wgrad_rows" if self.trunk_fwd == "K40F-idx" else "xpa_s3_wgrad")
+        elif self.trunk_bwd.endswith("chain") and self.trunk_fwd.startswith("K13"):
+            out.append("xpa_thin_linear_act_bwd")
+        out.append("xpa_colsum_finalize_batch_map" if wide else "xpa_colsum_finalize_batch_sq_loss")
+        return out
 
 
 class FusedActorCritic:
@@ -161,6 +216,9 @@ class FusedActorCritic:
         if n_params != n_cov:
             raise ValueError("policy has parameters outside the Linear chains")
         self._partials = {}
+        self._plans = {}        # (switches, dz layout, input geometry) -> UpdatePlan
+        self.last_plan = None   # the plan of the latest forward_hidden
+        self._roll_split = None
         self._cq = ops.ColsumQueue()
         self._cq_early = ops.ColsumQueue()
         self.early_grad_sync = None   # data-parallel: callable(grad_view) starting an early all-reduce
@@ -229,58 +287,44 @@ class FusedActorCritic:
                 and f.data_ptr() % 16 == 0 and per <= self.WIDE_VIDX_MAX
                 and f.untyped_storage().nbytes() // 4 >= f.storage_offset() + f.numel() + need)
 
-    def _wide_forward(self, x, adv, adv_partials):
+    def _wide_forward(self, x, adv, adv_partials, direct):
         """The wide trunk layer's forward on the minibatch rows x = Rows(flat, idx): W0^T's split (zero rows to d_pad),
-        then K40F (bias, activation and h's sign bits in the epilogue) reading the rows through idx straight from the
-        rollout buffer (+ the advantage moments from a row-less K4); or, where the buffer has no slack, the pitched
-        gather into a zero-padded [B, d_pad] buffer first."""
+        then K40F (bias, activation and h's sign bits in the epilogue).  direct: the rows read through idx straight from
+        the rollout buffer (+ the advantage moments from a row-less K4); else the pitched gather into a zero-padded
+        [B, d_pad] buffer first."""
         lin, code, slope = self.rep[0]
         B, d = x.idx.shape[0], lin.in_features
         kp = (d + 15) // 16 * 16
-        if self._wide_direct_ok(x, d):
+        if direct:
             if adv_partials is not None:   # K4's advantage moments alone (zero-width rows)
                 ops.gather_minibatch(x.idx, x.flat[:, :0], adv=adv, adv_partials=adv_partials,
                                      obs_out=x.flat.new_empty((B, 0)))
-            x.gathered = None
-            x.wide_direct = True
-            x.hsign = self._sign_buf(B, x.device)
-            wsplit = self._split_buf(kp, "w0t", x.device)
-            ops.s3_split_padded(lin.weight.t(), kp, out=wsplit)
-            h = torch.empty((B, lin.out_features), dtype=torch.float32, device=x.device)
-            ops.s3_gemm_bias_act(x.flat, wsplit, kp, lin.bias, code, slope, out=h, sign=x.hsign, ridx=x.idx)
-            return [h]
-        key = ("wide_x", B, kp)
-        xp = self._partials.get(key)
-        if xp is None:   # graph-capture safe: allocated (and its pad zeroed) on first (eager) use
-            xp = torch.zeros((B, kp), dtype=torch.float32, device=x.device)
-            self._partials[key] = xp
-        ops.gather_minibatch_pitched(x.idx, x.flat, xp, adv=adv if adv_partials is not None else None,
-                                     adv_partials=adv_partials)
-        x.gathered = xp
+            a, x.gathered = x.flat, None
+        else:   # (its pad zeroed once, at the allocation)
+            a = x.gathered = self._ws(("wide_x", B, kp),
+                                      lambda: torch.zeros((B, kp), dtype=torch.float32, device=x.device))
+            ops.gather_minibatch_pitched(x.idx, x.flat, a, adv=adv if adv_partials is not None else None,
+                                         adv_partials=adv_partials)
         x.hsign = self._sign_buf(B, x.device)
         wsplit = self._split_buf(kp, "w0t", x.device)
         ops.s3_split_padded(lin.weight.t(), kp, out=wsplit)
         h = torch.empty((B, lin.out_features), dtype=torch.float32, device=x.device)
-        ops.s3_gemm_bias_act(xp, wsplit, kp, lin.bias, code, slope, out=h, sign=x.hsign)
+        ops.s3_gemm_bias_act(a, wsplit, kp, lin.bias, code, slope, out=h, sign=x.hsign, ridx=x.idx if direct else None)
         return [h]
 
-    def _wide_bwd(self, dz, x, crit):
+    def _wide_bwd(self, dz, x, crit, direct):
         """K42W (or K42C's dz form with the factored critic): dz1 = (dz . Wh_pair) act'(h) and db0's partials; K41V's
         slices of x_pad^T dz1, finalized transposed (and trimmed to d_in) into W0's gradient."""
         lin, code, slope = self.rep[0]
         B, d = dz.shape[0], lin.in_features
-        direct = getattr(x, "wide_direct", False)
         xp = x.gathered
         kp = self._wide_mpad(d) if direct else xp.shape[1]
         S = self._wide_slices(kp)
-        key = ("wide_bwd", B, kp, S)
-        ws = self._partials.get(key)
-        if ws is None:
-            G = int(ops.lib().xpa_s3_gemm_trunk_bwd_num_partials(B))
-            ws = (torch.empty((B, 256), device=dz.device), torch.empty((G, 256), device=dz.device),
-                  torch.empty((S, kp, 256), device=dz.device))
-            self._partials[key] = ws
-        dz1, pdb, pdw = ws
+        dev = dz.device
+        dz1, pdb, pdw = self._ws(("wide_bwd", B, kp, S), lambda: (
+            torch.empty((B, 256), device=dev),
+            torch.empty((int(ops.lib().xpa_s3_gemm_trunk_bwd_num_partials(B)), 256), device=dev),
+            torch.empty((S, kp, 256), device=dev)))
         k = self.pair[0].shape[0]
         if crit is not None:
             H = ops.HEAD_HIDDEN
@@ -294,14 +338,106 @@ class FusedActorCritic:
             ops.s3_wgrad(xp, dz1, out=pdw, slices=S)
         self._cq.add(pdw.view(S, -1), lin.weight.grad, tmap=(256, d, d))
         self._cq.add(pdb, lin.bias.grad)
-        return True
 
-    def _rep_forward(self, x, norm=None, adv=None, adv_partials=None, defer_trunk=False):
-        if isinstance(x, Rows) and not self.thin0:
+    # ---- the update's plan -------------------------------------------------------------------------
+    def _trunk_form(self, x, in_heads):
+        """(UpdatePlan.trunk_fwd, .sign_bits) for input x.  in_heads: the head kernels run the hidden GEMMs
+        (forward_hidden -> loss_backward), so they may form the trunk too and K42S can take h's sign bits."""
+        if not isinstance(x, Rows):
+            k13 = self.thin0 and x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
+            return ("K13" if k13 else "chain"), None
+        if not self.thin0:
             if not self._wide_on():
                 raise ValueError("Rows input needs the thin (K13) or the wide (K40F) trunk layer")
-            return self._wide_forward(x, adv, adv_partials)
-        if isinstance(x, Rows):
+            d = self.rep[0][0].in_features
+            return ("K40F-idx" if self._wide_direct_ok(x, d) else "K40F-pitched"), "K40F"
+        code, d = self.rep[0][1], self.rep[0][0].in_features
+        planes = ops.S3_GEMMS and ops.S3_HEADS in ("s3p", "s3q") and not ops.K16W_ENABLED
+        # K16R (TRUNK_S3R, on Wh's planes) or K16X (use_trunk_heads, f32): K13 only gathers, the head launches form h
+        s3r = self.TRUNK_S3R and self.trunk_heads and planes
+        if in_heads and self.trunk_heads and (self.use_trunk_heads or s3r):
+            return "K13-gather-only", ("K16R" if s3r and code in (0, 1) else None)
+        # K42S: K13 writes h's sign bits beside h where the fused thin trunk backward can run from them
+        if (in_heads and self.SIGN_BITS and self.FUSE_TRUNK_BWD and code in (0, 1) and len(self.rep) == 1 and d <= 32
+                and self.pair is not None and self._dx_split_ok(self.pair[0])):
+            return "K13-gather-sign", "K13"
+        return "K13-gather", None
+
+    def _make_plan(self, x, dz_ok):
+        """The plan for input x (a tensor or Rows; CPU tensors do), dz_ok = the head workspace's dz rows are 16-B
+        vectors.  h and the other activations are fresh [B, 256] allocations: 16-B vectors by layout."""
+        rows, paired, n_rep = isinstance(x, Rows), self.pair is not None, len(self.rep)
+        hidden = "heads" if paired and self.gemm_heads else "pair" if paired else "chains"
+        trunk_fwd, sign = self._trunk_form(x, hidden == "heads")
+        in_heads, deferred = hidden == "heads", trunk_fwd == "K13-gather-only"
+        wide = trunk_fwd.startswith("K40F")
+        s3 = bool(ops.S3_GEMMS)
+        dx_split = paired and n_rep > 0 and self._dx_split_ok(self.pair[0])
+        code0, d0 = (self.rep[0][1], self.rep[0][0].in_features) if n_rep else (None, 0)
+        # K16P / K16Q / K16R read Wh^T's planes; a deferred trunk takes them only as K16R (K16X keeps Wh in f32)
+        planes = (in_heads and s3 and ops.S3_HEADS in ("s3p", "s3q") and not ops.K16W_ENABLED
+                  and (not deferred or (self.TRUNK_S3R and self.trunk_heads)))
+        # the fused thin trunk backward (K42 over K13's one layer) on the rows as a [B, d_in <= 32] tensor
+        x_ok = rows or (x.dim() == 2 and x.stride(1) == 1)
+        thin_bwd = (self.FUSE_TRUNK_BWD and dx_split and n_rep == 1 and self.thin0 and d0 <= 32 and dz_ok and x_ok)
+        wide_bwd = wide and dz_ok
+        # the factored critic (K16Q's mask, K41P, K42C): the K16Q heads on K13's / K40F's h, a LeakyReLU / ReLU critic
+        # hidden layer with one output, and a fused trunk backward that reads h's sign bits
+        crit = (self.CRIT_FACTORED and planes and not deferred and ops.S3_HEADS == "s3q" and self.critic[-2][1] == 1
+                and self.critic[-1][0].out_features == 1 and self.FUSE_TRUNK_BWD and code0 in (0, 1)
+                and sign is not None and (wide_bwd or thin_bwd))
+        heads = ops.head_form(in_heads, deferred, planes, crit, self.actor[-1][0].out_features)
+        splits = ("s3p_a", "s3p_c") if planes else ()
+        if dx_split:
+            splits += ("dx_crit" if crit else "dx",)
+        if crit:
+            dw_hidden = "K41P"
+        else:   # K41V: the layer input [B, 256] as 16-B vectors (the trunk's fresh output, or x itself without a trunk)
+            s_ok = n_rep > 0 or (not rows and x.dim() == 2 and _vec4_rows(x))
+            k41 = paired and s3 and self.actor[0][0].in_features == 256 and s_ok and dz_ok
+            dw_hidden = "K41V" if k41 else "splitk"
+        if n_rep == 0:
+            trunk_bwd = "none"
+        elif not paired:
+            trunk_bwd = "chain"
+        elif wide_bwd:
+            trunk_bwd = "K42C-dz" if crit else "K42W"
+        elif thin_bwd:
+            trunk_bwd = "K42C" if crit else "K42S" if sign else "K42"
+        else:
+            trunk_bwd = "K40+chain" if dx_split and dz_ok else "mm+chain"
+        return UpdatePlan(trunk_fwd, hidden, heads, splits, dw_hidden, trunk_bwd, sign,
+                          paired and self.early_grad_sync is not None)
+
+    def plan(self, x):
+        """The UpdatePlan of one minibatch update on x (what forward_hidden receives): the only reader of the update's
+        switches — ops.S3_GEMMS / S3_HEADS / K16W_ENABLED, the class switches below, use_trunk_heads, early_grad_sync —
+        and the only place a capability is tested.  Host logic alone.  Cached under every switch's value and the
+        input's geometry, so a switch flipped later takes effect and a steady-state update pays one dict lookup."""
+        hws = self._hws
+        dz_ok = hws is None or _vec4_rows(hws.dz_pair if hws.paired else hws.dz_actor)
+        if isinstance(x, Rows):   # + the storage's slack behind the last row (the row-index forms read into it)
+            f = x.flat
+            geom = (x.idx.shape[0], tuple(f.shape), f.stride(), f.dtype, f.data_ptr() % 16,
+                    f.untyped_storage().nbytes() // 4 - f.storage_offset() - f.numel())
+        else:
+            geom = (tuple(x.shape), x.stride(), x.dtype, x.data_ptr() % 16)
+        key = (ops.S3_GEMMS, ops.S3_HEADS, ops.K16W_ENABLED, self.WIDE_TRUNK, self.WIDE_DIRECT, self.WIDE_VIDX_MAX,
+               self.CRIT_FACTORED, self.FUSE_TRUNK_BWD, self.TRUNK_S3R, self.SIGN_BITS, self.use_trunk_heads,
+               self.early_grad_sync is not None, dz_ok, geom)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self._make_plan(x, dz_ok)
+        return plan
+
+    def _rep_forward(self, x, form=None, sign=None, norm=None, adv=None, adv_partials=None):
+        """The representation's forward in the given UpdatePlan.trunk_fwd form (sign: the plan's sign_bits); the
+        rollout-side callers give none and take the plain form for x."""
+        if form is None and norm is None:
+            form, sign = self._trunk_form(x, False)
+        if form in ("K40F-idx", "K40F-pitched"):
+            return self._wide_forward(x, adv, adv_partials, form == "K40F-idx")
+        if form in ("K13-gather", "K13-gather-sign", "K13-gather-only"):
             # K4's gather folded into K13's x staging (+ the advantage moments when adv_partials is given)
             lin, code, slope = self.rep[0]
             B = x.idx.shape[0]
@@ -309,28 +445,23 @@ class FusedActorCritic:
             # the gathered rows are written beside h (4 B x d_in per row) so the backward reads them contiguously
             # (reading them through idx again cost K13's backward 3.3 us per update)
             x.gathered = torch.empty((B, lin.in_features), dtype=torch.float32, device=x.device)
-            # K16X: gather-only (h = NULL); the actor head launch forms h and writes it here
-            # (only for forward_hidden -> loss_backward, where the K16X launches consume x.trunk; h is unwritten until then)
-            deferred = defer_trunk and self.trunk_heads and (self.use_trunk_heads or self._s3r_on()) and len(self.rep) == 1
+            # K16X / K16R: gather-only (h = NULL); the actor head launch forms h and writes it here
+            # (only for forward_hidden -> loss_backward, where the head launches consume x.trunk; h is unwritten until then)
+            deferred = form == "K13-gather-only"
             if deferred:
                 x.trunk = (x.gathered, lin.weight, lin.bias, slope, h)
-                if self._s3r_on() and code in (0, 1):   # K16R's sign bits of h for K42S (act' without reading h)
+                if sign == "K16R":   # K16R's sign bits of h for K42S (act' without reading h)
                     x.trunk = x.trunk + (self._sign_buf(B, x.device),)
             x.hsign = None
-            if not deferred and defer_trunk and self._sign_on(code):
+            fn, sign_out = ops.lib().xpa_thin_linear_act_fwd_gather, ()
+            if form == "K13-gather-sign":
                 # K13 writes h's sign bits beside h: K42S's act' (32 B per row read instead of h's 1 KiB)
                 x.hsign = self._sign_buf(B, x.device)
-                _lib.call(ops.lib().xpa_thin_linear_act_fwd_gather_sign, code, ops._p(x.flat), x.flat.stride(0),
-                          x.flat.shape[0], ops._p(x.idx), B, lin.in_features, lin.out_features, ops._p(lin.weight),
-                          ops._p(lin.bias), slope, ops._p(h), h.stride(0),
-                          ops._p(adv) if adv_partials is not None else None,
-                          ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered),
-                          ops._p(x.hsign), ops._stream(x.device))
-                return [h] + self._chain_forward(self.rep[1:], h)
-            _lib.call(ops.lib().xpa_thin_linear_act_fwd_gather, code, ops._p(x.flat), x.flat.stride(0), x.flat.shape[0],
-                      ops._p(x.idx), B, lin.in_features, lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope,
-                      None if deferred else ops._p(h), h.stride(0), ops._p(adv) if adv_partials is not None else None,
-                      ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered),
+                fn, sign_out = ops.lib().xpa_thin_linear_act_fwd_gather_sign, (ops._p(x.hsign),)
+            _lib.call(fn, code, ops._p(x.flat), x.flat.stride(0), x.flat.shape[0], ops._p(x.idx), B, lin.in_features,
+                      lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope, None if deferred else ops._p(h),
+                      h.stride(0), ops._p(adv) if adv_partials is not None else None,
+                      ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered), *sign_out,
                       ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
         if norm is not None:
@@ -346,29 +477,36 @@ class FusedActorCritic:
                       ops._p(mean), ops._p(var), float(clip), ops._p(xn), xn.stride(0), ops._p(col), int(col_ld),
                       ops._p(cursor), ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
-        if self.thin0 and x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1:
+        if form == "K13":
             lin, code, slope = self.rep[0]
             h = torch.empty((x.shape[0], lin.out_features), dtype=torch.float32, device=x.device)
             _lib.call(ops.lib().xpa_thin_linear_act_fwd, code, ops._p(x), x.stride(0), x.shape[0], lin.in_features,
                       lin.out_features, ops._p(lin.weight), ops._p(lin.bias), slope, ops._p(h), h.stride(0),
                       ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
+        if form != "chain":
+            _no_form("the trunk forward", form)
         return self._chain_forward(self.rep, x)
+
+    def _ws(self, key, make):
+        """The workspace kept under `key` in _partials, made on first (eager) use: graph-capture safe."""
+        ws = self._partials.get(key)
+        if ws is None:
+            ws = self._partials[key] = make()
+        return ws
 
     def _thin_backward(self, layer, g, h, x):
         lin, code, slope = layer
         rows, din = x.shape[0], lin.in_features
         L = ops.lib()
-        key = ("thin", rows, din)
-        ws = self._partials.get(key)
-        if ws is None:
+
+        def make():
             G = int(L.xpa_thin_bwd_num_partials(rows))
-            ws = (torch.empty((G, lin.out_features * din), device=g.device),
-                  torch.empty((G, lin.out_features), device=g.device))
-            self._partials[key] = ws
-        pdw, pdb = ws
+            return (torch.empty((G, lin.out_features * din), device=g.device),
+                    torch.empty((G, lin.out_features), device=g.device))
+        pdw, pdb = self._ws(("thin", rows, din), make)
         s = ops._stream(g.device)
-        if isinstance(x, Rows) and getattr(x, "gathered", None) is not None:
+        if isinstance(x, Rows) and x.gathered is not None:
             x = x.gathered
         if isinstance(x, Rows):
             _lib.call(L.xpa_thin_linear_act_bwd_gather, code, ops._p(g), g.stride(0), ops._p(h), h.stride(0), rows,
@@ -411,7 +549,7 @@ class FusedActorCritic:
         self._roll_split = (bufs[0], bufs[1])
 
     def _rollout_pair(self, s):
-        rs = getattr(self, "_roll_split", None)
+        rs = self._roll_split
         if rs is not None and s.dim() == 2 and s.shape[1] == 256 and _vec4_rows(s):
             return ops.s3_gemm_rows_pair(s, rs[0], rs[1], self.pair[1])
         return F.linear(s, self.pair[0], self.pair[1])
@@ -422,7 +560,7 @@ class FusedActorCritic:
     ROLLOUT_TRUNK = os.environ.get("XPA_ROLLOUT_TRUNK", "0") == "1"
 
     def _rollout_trunk_pair(self, x, norm):
-        rs = getattr(self, "_roll_split", None)
+        rs = self._roll_split
         if (not self.ROLLOUT_TRUNK or norm is None or rs is None or not self.thin0 or len(self.rep) != 1
                 or x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1):
             return None
@@ -473,7 +611,7 @@ class FusedActorCritic:
         """K40V (r06): the critic from x to its value in two launches — the trunk, then the critic's hidden layer on the
         split GEMM (the rollout's planes of Wh_critic^T, rollout_refresh) with act . w_out + b_out in its epilogue — or
         None where that form does not apply (no rollout planes, a critic deeper than one hidden layer)."""
-        rs = getattr(self, "_roll_split", None)
+        rs = self._roll_split
         if rs is None or len(self.critic) != 2:
             return None
         lin_ch, code, slope = self.critic[-2]
@@ -500,62 +638,55 @@ class FusedActorCritic:
     def forward_hidden(self, x, adv=None, adv_partials=None):
         """Forward up to the heads' last hidden pre-activations (K12 does the rest).  x may be Rows(flat, idx); then
         adv_partials (if given) receives the minibatch's advantage moments of adv[idx] (K4's partials)."""
-        rep_outs = self._rep_forward(x, adv=adv, adv_partials=adv_partials,
-                                     defer_trunk=self.pair is not None and self.gemm_heads)
+        B = x.shape[0]
+        if self._hws is None or self._hws.batch != B:   # before the plan, which reads dz's layout
+            self._hws = ops.HeadWorkspace(B, self.actor[-1][0].out_features, x.device, paired=self.pair is not None)
+        plan = self.last_plan = self.plan(x)
+        rep_outs = self._rep_forward(x, plan.trunk_fwd, plan.sign_bits, adv=adv, adv_partials=adv_partials)
         s = rep_outs[-1] if rep_outs else x
-        if self.pair is not None and self.gemm_heads:   # K16 forms z inside the head kernels
-            return (x, rep_outs, s, (([], s, None), ([], s, None)))
-        if self.pair is not None:   # one GEMM for both hidden layers: [B, 512] = actor | critic
+        if plan.hidden == "heads":   # K16 forms z inside the head kernels
+            return (x, rep_outs, s, (([], s, None), ([], s, None)), plan)
+        if plan.hidden == "pair":   # one GEMM for both hidden layers: [B, 512] = actor | critic
             H = ops.HEAD_HIDDEN
             ev = ops.TIMER.start("gemm_pair")
             z = F.linear(s, self.pair[0], self.pair[1])
             ops.TIMER.stop("gemm_pair", ev)
-            return (x, rep_outs, s, (([], s, z[:, :H]), ([], s, z[:, H:])))
+            return (x, rep_outs, s, (([], s, z[:, :H]), ([], s, z[:, H:])), plan)
         heads = []
         for layers in (self.actor, self.critic):
             outs = self._chain_forward(layers[:-2], s)
             lin = layers[-2][0]
             x_h = outs[-1] if outs else s
             heads.append((outs, x_h, F.linear(x_h, lin.weight, lin.bias)))
-        return (x, rep_outs, s, heads)
+        return (x, rep_outs, s, heads, plan)
 
     @torch.no_grad()
     def loss_backward(self, ctx, algo, dist, act, adv, ret, old_logp=None, idx=None, adv_partials=None,
                       clip_range=0.2, vf_coef=0.25, ent_coef=0.0):
         """K12 loss + head backward, then the hidden / trunk GEMMs.  Writes every parameter gradient;
         returns the loss-scalars device tensor (ops.OUT_KEYS)."""
-        x, rep_outs, s, ((a_outs, a_xh, z_a), (c_outs, c_xh, z_c)) = ctx
+        x, rep_outs, s, ((a_outs, a_xh, z_a), (c_outs, c_xh, z_c)), plan = ctx
         B = s.shape[0]
         lin_ao, _, _ = self.actor[-1]
         lin_ah, a_code, a_slope = self.actor[-2]
         lin_co, _, _ = self.critic[-1]
         lin_ch, c_code, c_slope = self.critic[-2]
-        K = lin_ao.out_features
-        paired = self.pair is not None
-        if self._hws is None or self._hws.batch != B:
-            self._hws = ops.HeadWorkspace(B, K, s.device, paired=paired)
-        gemm = wh_split = None
-        trunk = x.trunk if z_a is None and isinstance(x, Rows) else None
-        splits = []   # (matrix, name): every split this update needs, one launch (xpa_s3_split_batch)
-        if z_a is None:   # K16
+        gemm = wh_split = trunk = crit = None
+        if plan.hidden == "heads":   # K16
             gemm = (s, (lin_ah.weight, lin_ah.bias), (lin_ch.weight, lin_ch.bias))
-            # K16P / K16Q: Wh^T's planes.  With a deferred trunk the planes select K16R, which runs only behind
-            # TRUNK_S3R; the use_trunk_heads opt-in (K16X) takes Wh in f32
-            if (ops.S3_GEMMS and ops.S3_HEADS in ("s3p", "s3q") and not ops.K16W_ENABLED
-                    and (trunk is None or self._s3r_on())):
-                splits += [(lin_ah.weight.t(), "s3p_a"), (lin_ch.weight.t(), "s3p_c")]
-        crit = (self._crit_plan(x, rep_outs, c_code, B, s.device)
-                if paired and z_a is None and trunk is None and wh_split is None and splits else None)
-        scales = cs = None
-        if paired and len(self.rep) > 0 and self._dx_split_ok(self.pair[0]):
-            splits.append((self.pair[0], "dx"))
+            if plan.trunk_fwd == "K13-gather-only":
+                trunk = x.trunk
+        if plan.heads == "K16Q-mask":
+            crit = self._crit_bufs(B, s.device)
+        if plan.splits:   # every split this update needs, one launch (xpa_s3_split_batch)
+            mats = {"s3p_a": lin_ah.weight.t(), "s3p_c": lin_ch.weight.t()}   # the other names: Wh_pair for dX
+            scales = cs = None
             if crit is not None:   # K42C: the critic's rows of the dX split scaled by (1 - slope) wc, + cs
-                H = ops.HEAD_HIDDEN
-                scales = [None] * (len(splits) - 1) + [(lin_co.weight.view(-1), 1.0 - float(c_slope), H)]
+                scales = [None] * (len(plan.splits) - 1) + [(lin_co.weight.view(-1), 1.0 - float(c_slope),
+                                                             ops.HEAD_HIDDEN)]
                 cs = (crit[2], float(c_slope))
-        if splits:
-            bufs = self._split_many(splits, scales, cs)
-            if splits[0][1] == "s3p_a":
+            bufs = self._split_many([(mats[n] if n in mats else self.pair[0], n) for n in plan.splits], scales, cs)
+            if plan.splits[0] == "s3p_a":
                 wh_split = (bufs[0], bufs[1])
         grads = {"w_actor": lin_ao.weight.grad, "b_actor": lin_ao.bias.grad, "bh_actor": lin_ah.bias.grad,
                  "w_critic": lin_co.weight.grad, "b_critic": lin_co.bias.grad, "bh_critic": lin_ch.bias.grad}
@@ -572,31 +703,22 @@ class FusedActorCritic:
                                               wh_split=wh_split,
                                               defer_loss=True,
                                               trunk=trunk,
-                                              crit_mask=crit[:2] if crit is not None else None)
+                                              crit_mask=crit[:2] if crit is not None else None, form=plan.heads)
         have_rep = len(self.rep) > 0
-        if paired and crit is not None:   # r05: K41P + K42C, the critic's half factored (dz_critic never written)
-            q = self._cq_early if self.early_grad_sync is not None else self._cq
-            self._weight_grad_pair(s, crit, lin_co, c_slope, q)
-            if self.early_grad_sync is not None:
-                self._cq_early.flush(s.device)
-                self.early_grad_sync(self.pair[2])
-            if not self._trunk_bwd_fused(self._hws.dz_actor, x, rep_outs, crit=crit):
-                raise RuntimeError("factored critic planned but the fused trunk backward did not apply")
-            self._flush_with_norm(s.device)
-            return scalars
-        if paired:   # dW of both hidden layers and dX (K = 512, no accumulate pass) as single GEMMs
-            dz = self._hws.dz_pair
-            if self.early_grad_sync is not None:
+        if plan.hidden != "chains":   # paired: dW of both hidden layers and dX (K = 512) as single GEMMs
+            q = self._cq_early if plan.early_sync else self._cq
+            if plan.dw_hidden == "K41P":   # r05: with K42C, the critic's half factored (dz_critic never written)
+                dz = self._hws.dz_actor
+                self._weight_grad_pair(s, crit, lin_co, c_slope, q)
+            else:
+                dz = self._hws.dz_pair
+                self._weight_grad(dz, s, self.pair[2], queue=q, k41=plan.dw_hidden == "K41V")
+            if plan.early_sync:
                 # data-parallel: finalize this 0.5 MB slice now and start its all-reduce, which then overlaps
                 # the dX GEMM and the trunk backward (distributed.GradAllReduce.begin)
-                self._weight_grad(dz, s, self.pair[2], queue=self._cq_early)
                 self._cq_early.flush(s.device)
                 self.early_grad_sync(self.pair[2])
-            else:
-                self._weight_grad(dz, s, self.pair[2], queue=self._cq)
-            if have_rep and not self._trunk_bwd_fused(dz, x, rep_outs):
-                self._chain_backward(self.rep, [x] + rep_outs[:-1], rep_outs, self._dx(dz, self.pair[0]),
-                                     need_dx=False, thin_first=self.thin0)
+            self._trunk_backward(plan, dz, x, rep_outs, crit)
             self._flush_with_norm(s.device)   # every deferred column-sum finalize in one launch
             return scalars
         ds = self._from_dz(self.actor[:-1], [s] + a_outs, a_outs, dz_a, need_dx=have_rep)
@@ -636,12 +758,8 @@ class FusedActorCritic:
     # ------------------------------------------------------------------------------------------------
     def _bias_grad(self, code, g, h, slope, out):
         rows, cols = g.shape
-        key = (rows, cols)
-        part = self._partials.get(key)
-        if part is None:
-            part = torch.empty((int(ops.lib().xpa_act_bwd_num_partials(rows)), cols), dtype=torch.float32,
-                               device=g.device)
-            self._partials[key] = part
+        part = self._ws((rows, cols), lambda: torch.empty((int(ops.lib().xpa_act_bwd_num_partials(rows)), cols),
+                                                          dtype=torch.float32, device=g.device))
         s = ops._stream(g.device)
         L = ops.lib()
         _lib.call(L.xpa_act_bwd_colsum, code, ops._p(g), ops._p(h) if code else None, rows, cols, slope,
@@ -649,62 +767,32 @@ class FusedActorCritic:
         _lib.call(L.xpa_colsum_finalize, ops._p(part), part.shape[0], cols, ops._p(out), s)
 
     def _split_buf(self, k, name, device):
-        key = ("s3split", name, k)
-        buf = self._partials.get(key)
-        if buf is None:   # graph-capture safe: allocated on first (eager) use
-            buf = torch.empty(int(ops.lib().xpa_s3_split_bytes(k, 256)), dtype=torch.uint8, device=device)
-            self._partials[key] = buf
-        return buf
+        return self._ws(("s3split", name, k), lambda: torch.empty(int(ops.lib().xpa_s3_split_bytes(k, 256)),
+                                                                  dtype=torch.uint8, device=device))
 
     def _split_many(self, items, scales=None, cs=None):
         """The bf16 planes of every (matrix [k, 256], name) in one launch, into buffers kept per name (scales / cs:
         ops.s3_split_batch's, for K42C)."""
-        bufs = [self._split_buf(b.shape[0], name + ("_crit" if scales and sc else ""), b.device)
-                for (b, name), sc in zip(items, scales or [None] * len(items))]
+        bufs = [self._split_buf(b.shape[0], name, b.device) for b, name in items]
         ops.s3_split_batch([(b, o) for (b, _), o in zip(items, bufs)], scales, cs)
         return bufs
 
     # r05: the critic's half of the paired hidden layer's dX and dW factored (K42C / K41P: masked GEMMs on exact 0 / 1
-    # operands, three split products instead of six; dz_critic never stored) where it applies: the K16Q heads, a
-    # LeakyReLU / ReLU critic hidden layer and K42S's trunk backward
+    # operands, three split products instead of six; dz_critic never stored) where it applies (_make_plan)
     CRIT_FACTORED = True
 
-    def _crit_plan(self, x, rep_outs, c_code, B, device):
-        """(mask int32 [B, 8], dv [B], cs [256]) buffers when the factored critic backward applies, else None."""
-        if not (self.CRIT_FACTORED and ops.S3_GEMMS and ops.S3_HEADS == "s3q" and not ops.K16W_ENABLED and c_code == 1
-                and self.critic[-1][0].out_features == 1 and self.pair is not None and len(self.rep) == 1):
-            return None
-        lin, code, _ = self.rep[0]
-        if not (self.FUSE_TRUNK_BWD and self._dx_split_ok(self.pair[0]) and code in (0, 1)
-                and ((self.thin0 and lin.in_features <= 32) or self._wide_on())
-                and isinstance(x, Rows) and getattr(x, "hsign", None) is not None):
-            return None
-        xr = x.gathered
-        h = rep_outs[0] if rep_outs else None
-        x_ok = self._wide_on() or (isinstance(xr, torch.Tensor) and xr.dim() == 2 and xr.stride(1) == 1)
-        if not (x_ok and isinstance(h, torch.Tensor) and h.shape[1] == 256 and _vec4_rows(h)):
-            return None
-        if self._hws is None or self._trunk_bwd_form(self._hws.dz_actor, x, rep_outs) is None:
-            return None
-        key = ("crit", B)
-        bufs = self._partials.get(key)
-        if bufs is None:   # graph-capture safe: allocated on first (eager) use
-            bufs = (torch.empty((B, 8), dtype=torch.int32, device=device), torch.empty((B,), dtype=torch.float32,
-                                                                                       device=device),
-                    torch.empty((256,), dtype=torch.float32, device=device))
-            self._partials[key] = bufs
-        return bufs
+    def _crit_bufs(self, B, device):
+        """The factored critic's (mask int32 [B, 8], dv [B], cs [256]) buffers."""
+        return self._ws(("crit", B), lambda: (torch.empty((B, 8), dtype=torch.int32, device=device),
+                                              torch.empty((B,), dtype=torch.float32, device=device),
+                                              torch.empty((256,), dtype=torch.float32, device=device)))
 
     def _weight_grad_pair(self, s, crit, lin_co, c_slope, queue):
         """K41P: the paired hidden layer's dW slices (actor: dz_a^T h; critic: factored), two finalize segments."""
         B = s.shape[0]
         sa, per_a, sc, per_c = ops.s3_wgrad_pair_slices(B)
-        key = ("wgrad_pair", sa, sc)
-        ws = self._partials.get(key)
-        if ws is None:
-            ws = (torch.empty((sa, 256, 256), dtype=torch.float32, device=s.device),
-                  torch.empty((sc, 256, 256), dtype=torch.float32, device=s.device))
-            self._partials[key] = ws
+        ws = self._ws(("wgrad_pair", sa, sc), lambda: (torch.empty((sa, 256, 256), dtype=torch.float32, device=s.device),
+                                                       torch.empty((sc, 256, 256), dtype=torch.float32, device=s.device)))
         ops.s3_wgrad_pair(self._hws.dz_actor, s, crit[0], crit[1], lin_co.weight.view(-1), c_slope, ws[0], ws[1])
         g = self.pair[2]
         queue.add(ws[0].view(sa, -1), g[:256].reshape(-1))
@@ -719,113 +807,69 @@ class FusedActorCritic:
     # K42S by default: K13's gather form writes h's sign bits beside h and K42 reads them instead of h
     SIGN_BITS = True
 
-    def _s3r_on(self):
-        return (self.TRUNK_S3R and self.trunk_heads and ops.S3_GEMMS and ops.S3_HEADS in ("s3p", "s3q")
-                and not ops.K16W_ENABLED)
-
-    def _sign_on(self, code):
-        return (self.SIGN_BITS and self.FUSE_TRUNK_BWD and code in (0, 1) and len(self.rep) == 1 and self.pair is not None
-                and self._dx_split_ok(self.pair[0]) and self.rep[0][0].in_features <= 32)
-
     def _sign_buf(self, B, device):
-        key = ("hsign", B)
-        sign = self._partials.get(key)
-        if sign is None:   # graph-capture safe: allocated on first (eager) use
-            sign = torch.empty((B, 8), dtype=torch.int32, device=device)
-            self._partials[key] = sign
-        return sign
+        return self._ws(("hsign", B), lambda: torch.empty((B, 8), dtype=torch.int32, device=device))
 
-    def _trunk_bwd_form(self, dz, x, rep_outs):
-        """Which fused trunk backward applies (no side effects): "wide" (_wide_bwd), "thin" (K42 over K13's layer) or
-        None.  _crit_plan plans the factored critic only where this is not None, and _trunk_bwd_fused runs exactly this
-        form, so the two cannot disagree."""
-        if (self._wide_on() and isinstance(x, Rows) and getattr(x, "hsign", None) is not None
-                and (isinstance(x.gathered, torch.Tensor) or getattr(x, "wide_direct", False)) and _vec4_rows(dz)):
-            return "wide"
-        if not (self.FUSE_TRUNK_BWD and self.pair is not None and self._dx_split_ok(self.pair[0]) and len(self.rep) == 1
-                and self.thin0 and _vec4_rows(dz)):
-            return None
-        xr = x.gathered if isinstance(x, Rows) else x
-        if not isinstance(xr, torch.Tensor) or xr.dim() != 2 or xr.stride(1) != 1 or self.rep[0][0].in_features > 32:
-            return None
-        h = rep_outs[0] if rep_outs else None
-        if not isinstance(h, torch.Tensor) or h.stride(1) != 1 or h.shape[1] != 256:
-            return None
-        return "thin"
-
-    def _trunk_bwd_fused(self, dz, x, rep_outs, crit=None):
-        """K42: the dX GEMM and the one representation layer's backward (K13's) in one launch, g never stored.  Returns
-        False (nothing done) when it does not apply (_trunk_bwd_form): not the split GEMMs, more than one representation
-        layer, no K13 first layer, d_in > 32, or rows not given as the gathered minibatch.  The wide trunk layer:
-        _wide_bwd."""
-        form = self._trunk_bwd_form(dz, x, rep_outs)
-        if form == "wide":
-            return self._wide_bwd(dz, x, crit)
-        if form is None:
-            return False
+    def _trunk_backward(self, plan, dz, x, rep_outs, crit):
+        """The representation's backward from the paired hidden layer's dz in the plan's trunk_bwd form.  K42 / K42S /
+        K42C: the dX GEMM and the one thin layer's backward (K13's) in one launch, g never stored; K42W / K42C-dz: the
+        wide layer (_wide_bwd); the chain forms: dX by K40 (the planes this update's split launch wrote) or the f32
+        GEMM, then _chain_backward."""
+        form = plan.trunk_bwd
+        if form == "none":
+            return
+        if form not in ("K42", "K42S", "K42C", "K42W", "K42C-dz", "K40+chain", "mm+chain"):
+            _no_form("the trunk backward", form)
+        k = self.pair[0].shape[0]
+        if form in ("K42W", "K42C-dz"):
+            return self._wide_bwd(dz, x, crit, plan.trunk_fwd == "K40F-idx")
+        if form in ("K40+chain", "mm+chain"):
+            g = (ops.s3_gemm(dz, self._split_buf(k, "dx", dz.device), k) if form == "K40+chain"
+                 else torch.mm(dz, self.pair[0]))
+            self._chain_backward(self.rep, [x] + rep_outs[:-1], rep_outs, g, need_dx=False, thin_first=self.thin0)
+            return
         lin, code, slope = self.rep[0]
         xr = x.gathered if isinstance(x, Rows) else x
-        h = rep_outs[0]
-        rows = dz.shape[0]
-        key = ("k42", rows, lin.in_features)
-        ws = self._partials.get(key)
-        if ws is None:
+        rows, dev = dz.shape[0], dz.device
+
+        def make():
             G = int(ops.lib().xpa_s3_gemm_trunk_bwd_num_partials(rows))
-            ws = (torch.empty((G, 256 * lin.in_features), device=dz.device), torch.empty((G, 256), device=dz.device))
-            self._partials[key] = ws
-        k = self.pair[0].shape[0]
-        trunk = getattr(x, "trunk", None) if isinstance(x, Rows) else None
-        sign = trunk[5] if trunk is not None and len(trunk) > 5 else None   # K42S: act' from K16R's sign bits
-        if sign is None and isinstance(x, Rows):
-            sign = getattr(x, "hsign", None)   # or from K13's
-        if crit is not None:   # K42C: dz = the actor's half only
+            return torch.empty((G, 256 * lin.in_features), device=dev), torch.empty((G, 256), device=dev)
+        ws = self._ws(("k42", rows, lin.in_features), make)
+        # K42S / K42C: act' from h's sign bits, K16R's or K13's
+        sign = x.trunk[5] if plan.sign_bits == "K16R" else x.hsign if plan.sign_bits == "K13" else None
+        if form == "K42C":   # dz = the actor's half only
             H = ops.HEAD_HIDDEN
-            ops.s3_gemm_trunk_bwd_crit(dz, self._split_buf(k, "dx_crit", dz.device), H, k - H, crit[0], crit[1],
-                                       crit[2], sign, xr, code, slope, ws[0], ws[1])
+            ops.s3_gemm_trunk_bwd_crit(dz, self._split_buf(k, "dx_crit", dev), H, k - H, crit[0], crit[1], crit[2],
+                                       sign, xr, code, slope, ws[0], ws[1])
         else:
-            ops.s3_gemm_trunk_bwd(dz, self._split_buf(k, "dx", dz.device), k, h, xr, code, slope, ws[0], ws[1],
+            ops.s3_gemm_trunk_bwd(dz, self._split_buf(k, "dx", dev), k, rep_outs[0], xr, code, slope, ws[0], ws[1],
                                   h_sign=sign)
         self._cq.add(ws[0], lin.weight.grad)
         self._cq.add(ws[1], lin.bias.grad)
-        return True
 
     @staticmethod
     def _dx_split_ok(w):
         return ops.S3_GEMMS and w.shape[1] == 256 and w.shape[0] % 16 == 0
 
-    def _dx(self, dz, w):
-        """dX = dz w (w [k, n_in]): K40 on the bf16 matrix cores by the three-way split when ops.S3_GEMMS and the shape
-        fits (n_in = 256, k % 16 == 0; w's planes were written by this update's split launch), else the f32 GEMM."""
-        k, n_in = w.shape
-        if not (self._dx_split_ok(w) and _vec4_rows(dz)):
-            return torch.mm(dz, w)
-        return ops.s3_gemm(dz, self._split_buf(k, "dx", dz.device), k)
-
-    def _weight_grad(self, dz, x, out, queue=None):
+    def _weight_grad(self, dz, x, out, queue=None, k41=False):
         """dW = dz^T x.  Split-K (a batched GEMM over slices of the batch) when the GEMM alone would not
         fill the chip; with `queue` the slice sum is one more segment of the batched column-sum finalize
-        (f64, fixed order) instead of its own reduction launch.  With ops.S3_GEMMS and a fitting shape (n_in = 256,
-        n_out % 128 == 0) the slices come from K41 on the bf16 matrix cores by the three-way split."""
+        (f64, fixed order) instead of its own reduction launch.  k41 (the plan's K41V: ops.S3_GEMMS and a fitting
+        shape, n_in = 256, n_out % 128 == 0): the slices come from K41 on the bf16 matrix cores by the three-way split."""
         B, n_out = dz.shape
         n_in = x.shape[1]
-        if (queue is not None and ops.S3_GEMMS and n_in == 256 and n_out % 128 == 0 and isinstance(x, torch.Tensor)
-                and _vec4_rows(x) and _vec4_rows(dz)):
+        if k41:
             S = ops.s3_wgrad_slices(B, n_out)
-            key = ("s3wgrad", S, n_out)
-            ws = self._partials.get(key)
-            if ws is None:
-                ws = torch.empty((S, n_out, n_in), dtype=torch.float32, device=dz.device)
-                self._partials[key] = ws
+            ws = self._ws(("s3wgrad", S, n_out),
+                          lambda: torch.empty((S, n_out, n_in), dtype=torch.float32, device=dz.device))
             ops.s3_wgrad(dz, x, out=ws)
             queue.add(ws.view(S, n_out * n_in), out.view(-1))
             return
         s = _splitk_splits(B, n_out, n_in)
         if queue is not None:   # (s == 1: the finalize only copies, so every gradient still passes through it)
-            key = ("splitk", s, n_out, n_in)
-            ws = self._partials.get(key)
-            if ws is None:
-                ws = torch.empty((s, n_out, n_in), dtype=torch.float32, device=dz.device)
-                self._partials[key] = ws
+            ws = self._ws(("splitk", s, n_out, n_in),
+                          lambda: torch.empty((s, n_out, n_in), dtype=torch.float32, device=dz.device))
             if s > 1:
                 torch.bmm(dz.view(s, B // s, n_out).transpose(1, 2), x.reshape(s, B // s, n_in), out=ws)
             else:
@@ -845,16 +889,13 @@ class FusedActorCritic:
         h = outs[-2]
         B, H = h.shape
         K = g.shape[1]
-        key = ("head", B, H, K)
-        ws = self._partials.get(key)
         L = ops.lib()
-        if ws is None:
-            G = int(L.xpa_head_bwd_num_partials(B))
-            dev = g.device
-            ws = (torch.empty((G, K * H), device=dev), torch.empty((G, H), device=dev), torch.empty((G, K), device=dev),
-                  torch.empty((B, H), device=dev))
-            self._partials[key] = ws
-        p_dw, p_dbh, p_dbo, dz = ws
+
+        def make():
+            G, dev = int(L.xpa_head_bwd_num_partials(B)), g.device
+            return (torch.empty((G, K * H), device=dev), torch.empty((G, H), device=dev), torch.empty((G, K), device=dev),
+                    torch.empty((B, H), device=dev))
+        p_dw, p_dbh, p_dbo, dz = self._ws(("head", B, H, K), make)
         s = ops._stream(g.device)
         _lib.call(L.xpa_head_backward, code_h, K, ops._p(g), g.stride(0), ops._p(h), ops._p(lin_o.weight), B, H, slope,
                   ops._p(dz), ops._p(p_dw), ops._p(p_dbh), ops._p(p_dbo), s)

@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import _lib, graphs, ops
+from .fused_mlp import Rows
 from .policies import policy_discrete, policy_heads
 
 
@@ -160,7 +161,7 @@ class _FusedPolicyGradient(Learner):
             fm.early_grad_sync = (self.grad_sync.begin if getattr(self.grad_sync, "early_slice", False) else None)
             # obs may be fused_mlp.Rows(flat buffer, idx): K13 reads the minibatch through idx and, with adv_partials,
             # writes the minibatch's advantage moments itself (no K4 launch)
-            rows = type(obs).__name__ == "Rows"
+            rows = isinstance(obs, Rows)
             ctx = fm.forward_hidden(obs, adv=adv if rows else None, adv_partials=adv_partials if rows else None)
             scalars = fm.loss_backward(ctx, self.algo, self.dist, act, adv, ret, old_logp=old_logp, idx=idx,
                                        adv_partials=adv_partials, clip_range=self.clip_range, vf_coef=self.vf_coef,

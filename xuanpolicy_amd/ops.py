@@ -990,10 +990,47 @@ S3_HEADS = "s3q"   # with S3_GEMMS: "s3" K16S (both fragments split in the k loo
                    # "s3q" K16Q (K16P's bits, 32 x 128 wave tiles)
 
 
+# fused_heads' forms: name -> (actor entry point, critic entry point).  K16W's actor covers heads up to 8 wide; a wider
+# head keeps the K16S / K16 actor beside the K16W critic
+HEAD_FORMS = {
+    "K12": ("xpa_head_fused_actor", "xpa_head_fused_critic"),
+    "K16": ("xpa_head_gemm_actor", "xpa_head_gemm_critic"),
+    "K16S": ("xpa_head_gemm_s3_actor", "xpa_head_gemm_s3_critic"),
+    "K16P": ("xpa_head_gemm_s3p_actor", "xpa_head_gemm_s3p_critic"),
+    "K16Q": ("xpa_head_gemm_s3q_actor", "xpa_head_gemm_s3q_critic"),
+    "K16Q-mask": ("xpa_head_gemm_s3q_actor", "xpa_head_gemm_s3q_critic_mask"),
+    "K16W": ("xpa_head_gemm_ws_actor", "xpa_head_gemm_ws_critic"),
+    "K16S+W": ("xpa_head_gemm_s3_actor", "xpa_head_gemm_ws_critic"),
+    "K16+W": ("xpa_head_gemm_actor", "xpa_head_gemm_ws_critic"),
+    "K16X": ("xpa_head_gemm_trunk_actor", "xpa_head_gemm_critic"),
+    "K16R": ("xpa_head_gemm_s3r_actor", "xpa_head_gemm_s3r_critic"),
+}
+
+
+def head_form(gemm, trunk, wh_split, crit_mask, K):
+    """The HEAD_FORMS name that fused_heads' operands (each one: given or not) select for K-wide heads under
+    K16W_ENABLED / S3_GEMMS / S3_HEADS: the one place those three are read for the heads."""
+    if not gemm:
+        form = "K12"
+    elif trunk:
+        form = "K16R" if wh_split else "K16X"
+    elif K16W_ENABLED:
+        form = "K16W" if K <= 8 else "K16S+W" if S3_GEMMS else "K16+W"
+    elif wh_split:
+        form = "K16Q" if S3_HEADS == "s3q" else "K16P"
+    else:
+        form = "K16S" if S3_GEMMS else "K16"
+    if crit_mask:
+        if form != "K16Q":
+            raise ValueError("crit_mask needs the K16Q heads")
+        form = "K16Q-mask"
+    return form
+
+
 def fused_heads(algo, dist, ws, z_actor, w_actor, b_actor, act_actor, z_critic, w_critic, b_critic, act_critic,
                 logstd, act, adv, ret, old_logp=None, idx=None, adv_partials=None, clip_range=0.2, vf_coef=0.25,
                 ent_coef=0.0, grads=None, colsum_queue=None, gemm=None, sq_logstd=None, defer_loss=False, trunk=None,
-                wh_split=None, crit_mask=None):
+                wh_split=None, crit_mask=None, form=None):
     """K12 actor + critic heads, loss finalize and the column-sum finalizes.
 
     z_*: hidden pre-activations [B, 256] (unit column stride; row stride = the workspace dz row stride,
@@ -1006,6 +1043,7 @@ def fused_heads(algo, dist, ws, z_actor, w_actor, b_actor, act_actor, z_critic, 
     trunk as well K16R (h formed in both launches' k loops, the actor writes h and, given h_sign int32 [B, 8], its
     sign bits for K42S).  crit_mask = (mask int32 [B, 8], dv f32 [B]) with the K16Q heads (r05): the critic writes its
     hidden activations' sign bits and d loss / d v per row instead of dz_critic (K41P / K42C's factored critic).
+    form: the HEAD_FORMS name to run (fused_mlp's UpdatePlan.heads); None: head_form() of the operands given.
     (K x 256 / 1 x 256); act_*: (code, slope)
     of the hidden activation.  colsum_queue: an ops.ColsumQueue to defer the column-sum finalizes into
     (flushed by the caller), else they run here.  grads: dict with the gradient views to write — 'w_actor', 'b_actor',
@@ -1069,49 +1107,45 @@ def fused_heads(algo, dist, ws, z_actor, w_actor, b_actor, act_actor, z_critic, 
               _p(ws.p_dbh_actor), _p(ws.p_dbo_actor), _p(ws.loss_partials), W, s)
     tail_c = (_p(w_critic), _p(b_critic), float(act_critic[1]), _p(idx), rows, _p(ret), float(vf_coef),
               _p(ws.dz_critic), _p(ws.p_dw_critic), _p(ws.p_dbh_critic), _p(ws.p_dbo_critic), _p(ws.loss_partials), W, s)
-    if trunk is not None:
+    if form is None:
+        form = head_form(gemm is not None, trunk is not None, wh_split is not None, crit_mask is not None, K)
+    if (form not in HEAD_FORMS or (form != "K12") != (gemm is not None)
+            or (form in ("K16R", "K16X")) != (trunk is not None)
+            or (form in ("K16R", "K16P", "K16Q", "K16Q-mask") and wh_split is None)
+            or (form == "K16Q-mask") != (crit_mask is not None)):
+        raise ValueError("fused_heads cannot run form %r with these operands" % (form,))
+    fa, fc = (getattr(L, name) for name in HEAD_FORMS[form])
+    if form in ("K16R", "K16X"):
         trunk_in = (_p(xr), xr.stride(0), din, _p(w0), _p(b0), float(slope0))
-    if trunk is not None and wh_split is not None:
-        # K16R: h formed from the gathered rows inside both launches (Wh as its bf16 planes); the actor writes h
-        # and its sign bits
+    if form == "K16R":
+        # h formed from the gathered rows inside both launches (Wh as its bf16 planes); the actor writes h and its
+        # sign bits
         if h_sign is not None:
             _req(h_sign, "h_sign", torch.int32, (B, 8))
         wsa, wsc = wh_split
-        _lib.call(L.xpa_head_gemm_s3r_actor, *head_a, *trunk_in, _p(h_out), h_out.stride(0),
-                  _p(h_sign) if h_sign is not None else None, _p(wsa), _p(bha), ld, *tail_a)
-        _lib.call(L.xpa_head_gemm_s3r_critic, *head_c, *trunk_in, _p(wsc), _p(bhc), ld, *tail_c)
-    elif trunk is not None:
-        _lib.call(L.xpa_head_gemm_trunk_actor, *head_a, *trunk_in, _p(h_out), h_out.stride(0), _p(wha), _p(bha), ld,
-                  *tail_a)
+        _lib.call(fa, *head_a, *trunk_in, _p(h_out), h_out.stride(0), _p(h_sign) if h_sign is not None else None,
+                  _p(wsa), _p(bha), ld, *tail_a)
+        _lib.call(fc, *head_c, *trunk_in, _p(wsc), _p(bhc), ld, *tail_c)
+    elif form == "K16X":
+        _lib.call(fa, *head_a, *trunk_in, _p(h_out), h_out.stride(0), _p(wha), _p(bha), ld, *tail_a)
         # the critic reads the h the actor launch wrote (plain K16)
-        _lib.call(L.xpa_head_gemm_critic, *head_c, _p(h_out), h_out.stride(0), _p(whc), _p(bhc), ld, *tail_c)
-    elif gemm is not None:
-        # K16W (wave-specialised, the epilogue overlapped with the GEMM) for heads up to 8 wide; K16 otherwise
-        wsa = K16W_ENABLED and K <= 8
-        fa = L.xpa_head_gemm_ws_actor if wsa else L.xpa_head_gemm_s3_actor if S3_GEMMS else L.xpa_head_gemm_actor
-        fc = (L.xpa_head_gemm_ws_critic if K16W_ENABLED else L.xpa_head_gemm_s3_critic if S3_GEMMS
-              else L.xpa_head_gemm_critic)
-        if wh_split is not None and not wsa and not K16W_ENABLED:   # K16P / K16Q: the hidden weights as bf16 planes
-            if S3_HEADS == "s3q":
-                fa, fc = L.xpa_head_gemm_s3q_actor, L.xpa_head_gemm_s3q_critic
-            else:
-                fa, fc = L.xpa_head_gemm_s3p_actor, L.xpa_head_gemm_s3p_critic
+        _lib.call(fc, *head_c, _p(h_out), h_out.stride(0), _p(whc), _p(bhc), ld, *tail_c)
+    elif form == "K12":
+        _lib.call(fa, *head_a, ld, _p(z_actor), *tail_a)
+        _lib.call(fc, *head_c, ld, _p(z_critic), *tail_c)
+    else:
+        if form in ("K16P", "K16Q", "K16Q-mask"):   # the hidden weights as bf16 planes
             wha, whc = wh_split
         _lib.call(fa, *head_a, _p(x), x.stride(0), _p(wha), _p(bha), ld, *tail_a)
-        if crit_mask is not None:
-            if not (wh_split is not None and S3_HEADS == "s3q" and not K16W_ENABLED):
-                raise ValueError("crit_mask needs the K16Q heads")
+        if form == "K16Q-mask":
             cm, cdv = crit_mask
             _req(cm, "crit mask", torch.int32, (B, 8))
             _req(cdv, "crit dv", torch.float32, (B,))
             # no dz_critic (tail_c[7]); the mask and dv follow the stream
-            _lib.call(L.xpa_head_gemm_s3q_critic_mask, *head_c, _p(x), x.stride(0), _p(whc), _p(bhc), ld, *tail_c[:7],
-                      None, *tail_c[8:], _p(cm), _p(cdv))
+            _lib.call(fc, *head_c, _p(x), x.stride(0), _p(whc), _p(bhc), ld, *tail_c[:7], None, *tail_c[8:], _p(cm),
+                      _p(cdv))
         else:
             _lib.call(fc, *head_c, _p(x), x.stride(0), _p(whc), _p(bhc), ld, *tail_c)
-    else:
-        _lib.call(L.xpa_head_fused_actor, *head_a, ld, _p(z_actor), *tail_a)
-        _lib.call(L.xpa_head_fused_critic, *head_c, ld, _p(z_critic), *tail_c)
     TIMER.stop("heads", ev)
     g = grads or {}
     d_logstd = g.get("logstd")
