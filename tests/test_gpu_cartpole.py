@@ -299,7 +299,7 @@ def test_fused_rollout_matches_multi_kernel_steps(agent_name, hidden, obsnorm, n
         assert agent.defer_boot and agent.n_slots == 4
         agent.train(128 + 127, log=False)
         torch.cuda.synchronize()
-        assert (agent._small_rollout() is not None) == fused
+        assert (agent.plan().driver == "K32") == fused
         mem, env = agent.memory, agent.envs
         logp = mem.auxiliary_infos["old_logp"] if agent.algo == "ppo" else agent.logp_scratch
         res.append({k: v.detach().cpu().numpy().copy() for k, v in dict(

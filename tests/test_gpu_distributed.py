@@ -229,7 +229,7 @@ def _rollout_sync_worker(rank, world, port, q):
         agent = build_synthbox_ppo(n_envs=N, n_steps=T, n_epoch=2, n_minibatch=2, device=dev, shard=rank,
                                    sync_obs_rms="rollout", hidden=256)
         broadcast_parameters(agent.policy)
-        assert agent.sync_obs_rms_rollout and not agent.sync_obs_rms and agent.use_graph and agent._k14f_on()
+        assert agent.sync_obs_rms_rollout and not agent.sync_obs_rms and agent.use_graph and agent.plan().head == "K14F"
         c_start = float(agent.obs_count)
         agent.train(2 * T)
         torch.cuda.synchronize()

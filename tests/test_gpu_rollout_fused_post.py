@@ -29,7 +29,7 @@ def _run(monkeypatch, fused, n_envs, steps, agent_kind="PPO_Clip", max_ep=7):
     monkeypatch.setattr(ag, "FOLD_RMS", False)
     agent = build_synthbox_ppo(n_envs=n_envs, n_steps=16, obs_dim=17, act_dim=6, hidden=256, n_epoch=1, n_minibatch=4,
                                seed=11, device="cuda:0", max_episode_steps=max_ep, agent=agent_kind)
-    assert agent._k14f_on() == fused
+    assert (agent.plan().head == "K14F") == fused
     agent.train(steps, log=False)
     if not fused and agent.use_obsnorm:   # K14F has merged the observation the last step produced; the standalone
         agent._rms_update(agent.envs.obs)   # path merges it at the next step's start: catch up before comparing

@@ -71,7 +71,7 @@ def test_fold_rms_matches_standalone_update(monkeypatch):
         monkeypatch.setattr(ag, "FOLD_RMS", fold)
         agent = build_synthbox_ppo(n_envs=1000, n_steps=16, obs_dim=17, act_dim=6, hidden=256, n_epoch=1,
                                    n_minibatch=4, seed=9, device="cuda:0", max_episode_steps=7)
-        assert agent._rms_fold_ok() == fold
+        assert (agent.plan().rms == "fold-K8") == fold
         agent.train(16 + 7, log=False)   # one rollout + update, then 7 steps of the next
         stored = (agent.memory.observations[:, :7].clone(), agent.memory.values[:, :7].clone())
         if not fold:   # the fold has merged the observation the last step produced already; the standalone path

@@ -21,12 +21,14 @@ def main():
     env = agent.envs
     mem = agent.memory
     x = agent.obs_norm
-    rep = fm._rep_forward(x)
-    z = fm._rollout_pair(rep[-1])
+    plan = agent.plan()
+    rep = fm._rep_forward(x, plan.value_trunk)   # the plain form for the normalised rows
+    z = fm._rollout_pair(rep[-1], plan.pair)
     H = ops.HEAD_HIDDEN
     lin_ao, lin_co = fm.actor[-1][0], fm.critic[-1][0]
     _, code, slope = fm.actor[-2]
-    post = agent._k14f_post(True)
+    assert plan.head == "K14F"
+    post = agent._k14f_post(plan)
     res = {}
 
     def launch(p):

@@ -12,7 +12,8 @@ if __name__ == "__main__":
     st = torch.zeros(16, dtype=torch.int64, device="cuda:0")
     names = ["rms", "normalise", "-", "-", "forward", "sample+env+post", "ret_rms", "loop barrier"]
     for it in range(4):
-        a = agent._small_rollout()
+        assert agent.plan().driver == "K32"   # plan() also builds the argument block
+        a = agent._k32
         a.stamps = st.data_ptr()
         agent.train(128, log=False)
         torch.cuda.synchronize()

@@ -36,9 +36,10 @@ import torch
 
 from . import _lib, graphs, ops
 from .buffer import DummyOnPolicyBuffer, DummyOnPolicyBuffer_Atari
-from .fused_mlp import Rows
+from .fused_mlp import FusedActorCritic, Rows, _no_form
 from .learners import A2C_Learner, PerDQN_Learner, PPOCLIP_Learner
 from .policies import policy_discrete, policy_heads, space_shape
+from .rollout_plan import RolloutFacts, plan_rollout
 
 FLOAT_MAX = 3.0e38
 
@@ -149,10 +150,14 @@ class _OnPolicyAgent:
         self.logp_scratch = None if self.algo == "ppo" else torch.zeros((N, T), **f32)
         self.obs_mb = None
         self.adv_part = None
+        self._adv_parts = {}   # gather partials -> [g, 2] f64 advantage moments (one per minibatch size)
+        self._mb_bufs = {}     # (rows, dtype, row shape) -> (obs_mb, adv_part) of the gathered-minibatch feeds
+        self._mid_obs = self._env_in = self._raw_vb = self._raw_slots = self._vboot = None   # made on first use
         self.seed = int(_cfg(config, "seed", 1))
         self._perm_counter = 0
         self._perm_buf = None
         self.device_env = hasattr(envs, "step_device")
+        # The switches below, read after construction too: plan() is their one reader (rollout_plan.plan_rollout)
         self.fuse_env_step = True   # device SynthBox env stepped inside K14 when possible (_env_fused)
         self.fuse_value_gae = True  # deferred bootstraps' value head inside the GAE scan (xpa_gae_scan_value)
         # r06 (K40V): with fuse_value_gae, the deferred bootstraps' critic to the value on the split GEMM (the value head in
@@ -170,9 +175,11 @@ class _OnPolicyAgent:
         self._rms_pending = True
         self._rms_resets = getattr(envs, "resets", 0)
         self._rms_fold_part = None
-        # K32: whole device env steps (RMS, normalise, forward, sample, env, post) in one launch (_small_rollout)
+        # K32: whole device env steps (RMS, normalise, forward, sample, env, post) in one launch (plan().driver)
         self.fused_rollout = bool(_cfg(config, "fused_rollout", True))
-        self._k32 = self._k32_key = None
+        self._k32 = None                      # K32's argument block, rebuilt with the plan
+        self._plan = self._plan_key = None
+        self._params = list(policy.parameters())   # re-homing (flat.FlatState) moves their data, not the objects
         self.current_step = 0
         self.current_episode = np.zeros((N,), np.int32)
         self.iterations = 0
@@ -211,6 +218,7 @@ class _OnPolicyAgent:
         max_ep = int(getattr(envs, "max_episode_steps", getattr(envs, "max_episode_length", 0)) or 0)
         self.defer_boot = (bool(_cfg(config, "defer_bootstrap", True)) and not self.raw_obs
                            and hasattr(envs, "step_device") and max_ep > 0)
+        self.n_slots = 0
         if self.defer_boot:
             S = max(1, -(-(T - 1) // max_ep))
             self.n_slots = S
@@ -279,147 +287,174 @@ class _OnPolicyAgent:
         else:
             ops.obs_normalize(x, self.obs_mean, self.obs_var, self._obs_clip(), out)
 
-    # ---- one env step ---------------------------------------------------------------------------------
+    # ---- the iteration's forms ("Where the rollout's forms are decided") ------------------------
     def _rollout_mlp(self):
         """The learner's FusedActorCritic when it can drive the rollout forward (K14), else None."""
-        fm_get = getattr(self.learner, "_fused_mlp", None)
-        fm = fm_get() if fm_get is not None else None
+        fm = self.learner._fused_mlp()
         return fm if fm is not None and fm.rollout_ok else None
-
-    def _env_fused(self, fm):
-        """True when the device env's step runs inside the rollout's K14 launch (ops.rollout_policy_head_synthbox);
-        fuse_env_step = False keeps the separate env GEMM + K7 launches."""
-        ok = getattr(self.envs, "fusable_with_policy_step", None)
-        return bool(fm is not None and self.fuse_env_step and ok is not None and ok(self.dist))
-
-    def _sample_into_buffer(self, raw_x=None, fuse_env=False, post=None):
-        """raw_x: the raw observations, normalised inside the fused trunk (see _rollout_step_device).
-        fuse_env: also step the device env inside K14 (the caller then skips env.step_device()).
-        post (with fuse_env): K8's post step in the same launch (K14F, _k14f_post; the caller then skips _post)."""
-        mem = self.memory
-        logp_buf = mem.auxiliary_infos["old_logp"] if self.algo == "ppo" else self.logp_scratch
-        env_in = self.envs.act_in if self.device_env else self._act_scratch()
-        fm = self._rollout_mlp()
-        env = self.envs if fuse_env else None
-        if raw_x is not None:
-            T, D = self.n_steps, self.obs_dim
-            fm.rollout_act(raw_x, self.dist, self.cursor, self.seed, mem.actions, logp_buf, mem.values, env_in,
-                           act_clip=1.0, norm=(self.obs_mean, self.obs_var, self._obs_clip(), self.obs_norm,
-                                               mem.observations, T * D, self.cursor), env=env, post=post)
-            return
-        if fm is not None:
-            fm.rollout_act(self._policy_in, self.dist, self.cursor, self.seed, mem.actions, logp_buf, mem.values,
-                           env_in, act_clip=1.0, env=env, post=post)
-            return
-        if post is not None:
-            raise RuntimeError("K14F needs the fused rollout forward")
-        head, logstd, v = self._heads(self._policy_in)
-        ops.rollout_sample(self.dist, head.contiguous(), logstd, v.contiguous(), self.cursor, self.seed,
-                           mem.actions, logp_buf, mem.values, env_in, act_clip=1.0)
 
     def _rollout_cnn(self):
         """The learner's explicit CNN forward (fused_cnn.FusedCNNActorCritic) for raw-frame policies, else None."""
-        get = getattr(self.learner, "_fused_cnn", None)
-        return get() if (get is not None and self.raw_obs) else None
+        return self.learner._fused_cnn() if self.raw_obs else None
+
+    def plan(self, obs=None):
+        """The RolloutPlan of this agent as it stands, cached under every switch's value, the parameter and buffer
+        pointers, env.obs's geometry (obs: env.obs where the caller holds it) and the pending flag: a switch flipped
+        after construction takes effect, and a steady step pays this key and one comparison."""
+        L, fm = self.learner, self._rollout_mlp()
+        F = FusedActorCritic if fm is None else fm
+        if obs is None and self.device_env:
+            obs = self.envs.obs
+        key = (self.fuse_env_step, self.fuse_post, self.fold_rms, self.fuse_value_gae, self.value_gemm,
+               self.fuse_gather, self.fused_rollout, self.use_graph, self.graph_chunk, F.ROLLOUT_SPLIT, F.ROLLOUT_TRUNK,
+               F.WIDE_TRUNK, ops.S3_GEMMS, L.small_updates, L.small_split, L.graph_updates, L.grad_sync is None,
+               bool(self.memory._pending), None if obs is None else (obs.shape, obs.stride()),
+               self.memory.observations.data_ptr(), self.memory.actions.data_ptr(),
+               *[p.data_ptr() for p in self._params])
+        if key != self._plan_key:
+            self._plan = plan_rollout(self._facts(fm, F, obs))
+            self._k32 = self._build_small_rollout() if self._plan.driver == "K32" else None
+            self._plan_key = key
+        return self._plan
+
+    def _facts(self, fm, F, obs):
+        """What plan_rollout decides from (rollout_plan.RolloutFacts), gathered when plan()'s key changes."""
+        L, env, mem = self.learner, self.envs, self.memory
+        layers = L.small_policy_layers()
+        small = None
+        if layers is not None:
+            l0, l1, la, l2, _ = layers[0]
+            dims = (l0.in_features, l0.out_features, l1.out_features, l2.out_features, la.out_features)
+            small = dims + (int(ops.lib().xpa_small_rollout_lds_floats(self.n_envs, self.obs_dim, *dims[1:]))
+                            if self.device.type == "cuda" else 0,)
+        bufs = (mem.observations, mem.actions, mem.values, mem.rewards, mem.terminals, mem.boot)
+        obs_flat = mem.observations.reshape((self.buffer_size,) + tuple(mem.observations.shape[2:]))
+        fusable = getattr(env, "fusable_with_policy_step", None)
+        return RolloutFacts(
+            algo=self.algo, fuse_env_step=self.fuse_env_step, fuse_post=self.fuse_post, fold_rms=self.fold_rms,
+            fuse_value_gae=self.fuse_value_gae, value_gemm=self.value_gemm, fuse_gather=self.fuse_gather,
+            fused_rollout=self.fused_rollout, use_graph=self.use_graph, graph_chunk=self.graph_chunk,
+            rollout_split=F.ROLLOUT_SPLIT, rollout_trunk=F.ROLLOUT_TRUNK, s3_gemms=bool(ops.S3_GEMMS),
+            cuda=self.device.type == "cuda", use_obsnorm=self.use_obsnorm, raw_obs=self.raw_obs, atari=self.atari,
+            boot_from_reset=self.boot_from_reset, defer_boot=self.defer_boot, raw_defer=self.raw_defer,
+            raw_mid_next=self.raw_mid_next, n_slots=self.n_slots, n_steps=self.n_steps, obs_dim=self.obs_dim,
+            world=self.world, global_advnorm=self.global_advnorm, pending=bool(mem._pending),
+            sync_obs_rms=True if self.sync_obs_rms else "rollout" if self.sync_obs_rms_rollout else False,
+            env=getattr(env, "kind", "device") if self.device_env else "host",
+            env_fusable=bool(fusable is not None and fusable(self.dist)),
+            obs_rows=obs is not None and obs.dim() == 2 and obs.stride(1) == 1,
+            shape=None if fm is None else fm.rollout_shape(), cnn=self._rollout_cnn() is not None, small=small,
+            small_bufs=(all(b.dtype == torch.float32 and b.is_contiguous() for b in bufs)
+                        and mem.closed.is_contiguous()),
+            rows_ok=fm is not None and fm.rows_ok(obs_flat), small_update=L.small_update_ok(obs_flat, self.batch_size),
+            epoch_graphs=bool(L.graph_updates))
+
+    def _env_fused(self, fm=None):
+        """True when the device env's step runs inside the rollout's K14 launch (ops.rollout_policy_head_synthbox);
+        fuse_env_step = False keeps the separate env GEMM + K7 launches."""
+        return self.plan().env == "in-head"
+
+    # ---- one env step ---------------------------------------------------------------------------------
+    def _sample_into_buffer(self, plan, raw_x=None):
+        """The policy step in the plan's forms.  raw_x (obs "trunk"): the raw observations, normalised inside the fused
+        trunk.  Heads K14E / K14F also step the device env in the launch, K14F runs K8's post step there too (the
+        caller then skips env.step_device() / _post)."""
+        mem = self.memory
+        logp_buf = mem.auxiliary_infos["old_logp"] if self.algo == "ppo" else self.logp_scratch
+        env_in = self.envs.act_in if self.device_env else self._act_scratch()
+        if plan.head == "K3":
+            head, logstd, v = self._heads(plan.trunk, self._policy_in)
+            ops.rollout_sample(self.dist, head.contiguous(), logstd, v.contiguous(), self.cursor, self.seed,
+                               mem.actions, logp_buf, mem.values, env_in, act_clip=1.0)
+            return
+        if plan.head not in ("K14", "K14E", "K14F"):
+            _no_form("the rollout's head", plan.head)
+        norm = None
+        if raw_x is not None:
+            norm = (self.obs_mean, self.obs_var, self._obs_clip(), self.obs_norm, mem.observations,
+                    self.n_steps * self.obs_dim, self.cursor)
+        self._rollout_mlp().rollout_act(self._policy_in if raw_x is None else raw_x, self.dist, self.cursor, self.seed,
+                                        mem.actions, logp_buf, mem.values, env_in, act_clip=1.0, norm=norm,
+                                        env=self.envs if plan.head != "K14" else None,
+                                        post=self._k14f_post(plan) if plan.head == "K14F" else None,
+                                        trunk=plan.trunk, pair=plan.pair)
 
     @torch.no_grad()
-    def _heads(self, x):
-        fc = self._rollout_cnn() if x.dtype == torch.uint8 else None
-        if fc is not None:
-            return fc.heads(x)
+    def _heads(self, form, x):
+        """(head, logstd, v) of x through the module form of the plan's trunk: the explicit CNN forward or the policy."""
+        if form == "cnn":
+            return self._rollout_cnn().heads(x)
+        if form != "policy":
+            _no_form("the policy module's forward", form)
         return policy_heads(self.policy, x)
 
     def _act_scratch(self):
-        if getattr(self, "_env_in", None) is None:
+        if self._env_in is None:
             A = self.action_space.n if self.discrete else int(np.prod(self.action_space.shape))
             self._env_in = torch.zeros((self.n_envs, A), dtype=torch.float32, device=self.device)
         return self._env_in
 
-    def _post(self, rew, term, trunc, final_obs):
+    def _k8_args(self):
+        """What every form of K8 takes after its cursor (ops.rollout_post's keywords, K14F's post dict)."""
         mem = self.memory
-        # A2C over a device env stepped per step (replayed graphs: the host does not know which column is the last):
-        # both bootstrap values, K8 takes V(next obs) for closures before the last step (boot_from_reset)
-        mid = self.boot_from_reset and self.device_env
-        if self.raw_obs:
-            v_boot = self._zero_vboot if self.raw_defer else self._heads(final_obs)[2]
-            v_mid = (self._heads(self.envs.obs)[2] if (mid and not self.raw_defer and not self.raw_mid_next)
-                     else None)
-            self._post_kernel(rew, term, trunc, v_boot, v_mid)
-            return
-        if self.defer_boot:
+        return dict(ret_mean=self.ret_mean, ret_var=self.ret_var, ret_count=self.ret_count, returns=self.returns,
+                    buf_rew=mem.rewards, buf_term=mem.terminals, buf_closed=mem.closed, buf_boot=mem.boot,
+                    gamma=self.gamma, mask_returns=(self.algo == "ppo"), use_rewnorm=self.use_rewnorm,
+                    rew_range=self.rewnorm_range, atari_lifeloss=self.atari)
+
+    def _post(self, plan, rew, term, trunc, final_obs):
+        if plan.post == "K8-deferred":
             # final-obs normalisation folded into K8: kept truncation rows and, at the last step, every env's
-            # normalised final observation (boot_obs) — no separate normalise launch per step; with fold_rms also the
+            # normalised final observation (boot_obs) — no separate normalise launch per step; rms "fold-K8": also the
             # next step's obs_rms.update (its statistics then merged once this step's normalisations are done)
-            mem = self.memory
             rms = None
-            if self._rms_fold_ok():
+            if plan.rms == "fold-K8":
                 if self._rms_fold_part is None:
                     self._rms_fold_part = torch.empty((2 * int(ops.lib().xpa_rollout_post_num_blocks(self.n_envs)),
                                                        self.obs_dim), dtype=torch.float64, device=self.device)
                 rms = (self.envs.obs, self.obs_count, self._rms_fold_part)
-            ops.rollout_post(rew, term, trunc, None, self.cursor, self.ret_mean, self.ret_var, self.ret_count,
-                             self.returns, mem.rewards, mem.terminals, mem.closed, mem.boot, self.gamma,
-                             mask_returns=(self.algo == "ppo"), use_rewnorm=self.use_rewnorm,
-                             rew_range=self.rewnorm_range, atari_lifeloss=self.atari,
+            ops.rollout_post(rew, term, trunc, None, self.cursor, **self._k8_args(),
                              deferred=(final_obs, self.slot_obs, self.slot_t, self.slot_overflow, self.obs_mean,
                                        self.obs_var, self._obs_clip(), self.boot_obs)
-                             + ((self.envs.obs,) if self.boot_from_reset else ()),
+                             + ((self.envs.obs,) if plan.mid == "slots-from-next" else ()),
                              workspace=self.post_ws, rms=rms)
             return
-        self._normalize_into(final_obs, self.boot_obs, False)
-        v_boot = self._boot_values(self.boot_obs)
+        if plan.post != "K8":
+            _no_form("the post step", plan.post)
+        # per-step bootstrap values; mid "critic": A2C over a device env stepped per step (replayed graphs: the host
+        # does not know which column is the last) gives both, K8 takes V(next obs) for closures before the last step
+        v_boot = self._zero_vboot if plan.boot == "zero" else self._step_values(plan, final_obs, self.boot_obs)
         v_mid = None
-        if mid:
-            if getattr(self, "_mid_obs", None) is None:
+        if plan.mid == "critic":
+            if self._mid_obs is None and not self.raw_obs:
                 self._mid_obs = torch.empty_like(self.boot_obs)
-            self._normalize_into(self.envs.obs, self._mid_obs, False)
-            v_mid = self._boot_values(self._mid_obs)
-        self._post_kernel(rew, term, trunc, v_boot, v_mid)
+            v_mid = self._step_values(plan, self.envs.obs, self._mid_obs).contiguous()
+        ops.rollout_post(rew, term, trunc, v_boot.contiguous(), self.cursor, **self._k8_args(),
+                         workspace=self.post_ws, v_boot_mid=v_mid)
 
-    def _boot_values(self, x):
-        fm = self._rollout_mlp()
-        if fm is not None:
-            return fm.rollout_value(x)
-        with torch.no_grad():
-            return policy_heads(self.policy, x)[2]
+    def _step_values(self, plan, x, norm_out):
+        """V(x) for K8's per-step bootstraps: raw frames as they are, else normalised into norm_out first."""
+        if plan.obs == "raw":
+            return self._heads(plan.value_trunk, x)[2]
+        self._normalize_into(x, norm_out, False)
+        return self._values(plan, norm_out)
 
-    def _post_kernel(self, rew, term, trunc, v_boot, v_mid=None):
-        mem = self.memory
-        ops.rollout_post(rew, term, trunc, v_boot.contiguous(), self.cursor, self.ret_mean, self.ret_var,
-                         self.ret_count, self.returns, mem.rewards, mem.terminals, mem.closed, mem.boot, self.gamma,
-                         mask_returns=(self.algo == "ppo"), use_rewnorm=self.use_rewnorm,
-                         rew_range=self.rewnorm_range, atari_lifeloss=self.atari, workspace=self.post_ws,
-                         v_boot_mid=v_mid.contiguous() if v_mid is not None else None)
+    def _values(self, plan, x):
+        """The critic alone on normalised rows x in the plan's value_trunk form."""
+        if plan.value_trunk in ("K13", "chain"):
+            return self._rollout_mlp().rollout_value(x, trunk=plan.value_trunk)
+        return self._heads(plan.value_trunk, x)[2]
 
-    def _rms_fold_ok(self):
-        """The next step's obs_rms.update rides in the step's last launch — K14F (_k14f_on) or, with FOLD_RMS, K8 —
-        (device env, per-rank statistics, deferred bootstraps, D <= 64)."""
-        return ((self.fold_rms or self._k14f_on()) and self.device_env and self.use_obsnorm and not self.sync_obs_rms
-                and self.defer_boot and not self.raw_obs and self.obs_dim <= 64 and self.envs.obs.dim() == 2
-                and self.envs.obs.stride(1) == 1)
-
-    def _k14f_on(self, fuse=None):
-        """K8's post step runs inside the env-fused K14 launch (K14F): fused env step, deferred bootstraps."""
-        if fuse is None:
-            fuse = self._env_fused(self._rollout_mlp())
-        return bool(fuse and self.fuse_post and self.defer_boot and not self.raw_obs)
-
-    def _k14f_post(self, fuse):
+    def _k14f_post(self, plan):
         """K14F's post-step arguments (ops.rollout_policy_head_synthbox(post=)) — the deferred, normalised K8 call of
-        _post, with the next step's obs_rms.update where _rms_fold_ok — or None where K14F does not apply."""
-        if not self._k14f_on(fuse):
-            return None
-        rms = self._rms_fold_ok()
+        _post, with the next step's obs_rms.update where rms is "fold-K14F"."""
+        rms = plan.rms == "fold-K14F"
         if self._k14f_ws is None or self._k14f_ws[0] != rms:   # graph-capture safe: allocated on the first (eager) step
             self._k14f_ws = (rms, ops.rollout_step_workspace(self.n_envs, self.obs_dim, rms, self.device))
-        mem = self.memory
         return dict(slot_obs=self.slot_obs, slot_t=self.slot_t, overflow=self.slot_overflow,
-                    slot_from_next=self.boot_from_reset, obs_mean=self.obs_mean, obs_var=self.obs_var,
+                    slot_from_next=plan.mid == "slots-from-next", obs_mean=self.obs_mean, obs_var=self.obs_var,
                     obs_count=self.obs_count if rms else None, obs_clip=self._obs_clip(), boot_norm=self.boot_obs,
-                    ret_mean=self.ret_mean, ret_var=self.ret_var, ret_count=self.ret_count, returns=self.returns,
-                    buf_rew=mem.rewards, buf_term=mem.terminals, buf_closed=mem.closed, buf_boot=mem.boot,
-                    gamma=self.gamma, mask_returns=(self.algo == "ppo"), use_rewnorm=self.use_rewnorm,
-                    rew_range=self.rewnorm_range, atari_lifeloss=self.atari, workspace=self._k14f_ws[1])
+                    workspace=self._k14f_ws[1], **self._k8_args())
 
     def _rms_update(self, x):
         if self.sync_obs_rms:
@@ -441,37 +476,13 @@ class _OnPolicyAgent:
         self.obs_count.copy_(c)
         self._rms_c0 = None
 
-    def _small_rollout(self):
-        """K32's argument block (xpa_small_rollout_cartpole) when whole device env steps run as one launch: a CartPole
-        device env with deferred bootstraps, no per-step collective, and the small_policy_layers policy shape; else
-        None.  Rebuilt when the parameters are re-homed (the block holds their pointers)."""
-        if not self.fused_rollout or not self.device_env or self.device.type != "cuda":
-            return None
-        key = tuple(p.data_ptr() for p in self.policy.parameters()) + (self.memory.observations.data_ptr(),
-                                                                      self.memory.actions.data_ptr())
-        if self._k32_key != key:
-            self._k32_key, self._k32 = key, self._build_small_rollout()
-        return self._k32
-
     def _build_small_rollout(self):
-        env = self.envs
-        get = getattr(self.learner, "small_policy_layers", None)
-        layers = get() if get is not None else None
-        if (layers is None or getattr(env, "kind", None) != "cartpole" or not self.defer_boot or self.raw_obs
-                or self.sync_obs_rms or self.algo not in ("ppo", "a2c") or self.obs_dim != 4):
-            return None
-        (l0, l1, la, l2, lc), code, slope = layers
+        """K32's argument block (xpa_small_rollout_cartpole) for a plan whose driver is K32; plan() rebuilds it when the
+        parameters are re-homed (the block holds their pointers)."""
+        env, mem = self.envs, self.memory
+        (l0, l1, la, l2, lc), code, slope = self.learner.small_policy_layers()
         N, T, D = self.n_envs, self.n_steps, self.obs_dim
         h0, h1, h2, k = l0.out_features, l1.out_features, l2.out_features, la.out_features
-        if h0 not in (32, 64) or h1 not in (32, 64) or h2 not in (32, 64) or k != 2 or l0.in_features != D:
-            return None
-        lf = int(ops.lib().xpa_small_rollout_lds_floats(N, D, h0, h1, h2, k))
-        if not 0 < lf <= 16384:
-            return None
-        mem = self.memory
-        bufs = (mem.observations, mem.actions, mem.values, mem.rewards, mem.terminals, mem.boot)
-        if any(b.dtype != torch.float32 or not b.is_contiguous() for b in bufs) or not mem.closed.is_contiguous():
-            return None
         a = _lib.XpaSmallRolloutArgs()
         a.n_envs, a.horizon, a.steps, a.d_in, a.h0, a.h1, a.h2, a.k = N, T, 1, D, h0, h1, h2, k
         a.act_code, a.use_obsnorm, a.n_slots = int(code), int(self.use_obsnorm), int(self.n_slots)
@@ -502,53 +513,43 @@ class _OnPolicyAgent:
         a.cursor = p(self.cursor)
         return a
 
-    def _small_rollout_launch(self, a, steps):
-        a.steps = int(steps)
-        _lib.call(ops.lib().xpa_small_rollout_cartpole, ctypes.byref(a), ops._stream(self.device))
+    def _small_rollout_launch(self, steps):
+        self._k32.steps = int(steps)
+        _lib.call(ops.lib().xpa_small_rollout_cartpole, ctypes.byref(self._k32), ops._stream(self.device))
 
     def _rollout_step_device(self):
         env = self.envs
-        k32 = self._small_rollout()
-        if k32 is not None:
-            self._small_rollout_launch(k32, 1)
-            return
         x = env.obs
-        if self.raw_obs:
-            ops.store_column(x, self.memory.observations, self.cursor)
-            self._policy_in = x
-        else:
+        plan = self.plan(x)
+        if plan.driver == "K32":
+            self._small_rollout_launch(1)
+            return
+        if plan.rms is not None:
             if getattr(env, "resets", 0) != self._rms_resets:
                 self._rms_resets, self._rms_pending = getattr(env, "resets", 0), True
-            if self.use_obsnorm and (self._rms_pending or not self._rms_fold_ok()):
+            if self._rms_pending or plan.rms in ("standalone", "all-reduce"):
                 self._rms_update(x)
                 self._rms_pending = False
-            fm = self._rollout_mlp()
-            if fm is not None and fm.thin0 and x.stride(1) == 1:
-                fuse = self._env_fused(fm)
-                post = self._k14f_post(fuse)
-                # normalisation fused into the trunk's first layer
-                self._sample_into_buffer(raw_x=x, fuse_env=fuse, post=post)
-                if not fuse:
-                    env.step_device()
-                if post is None:
-                    self._post(env.rew, env.term, env.trunc, env.final_obs)
-                return
+        if plan.obs == "raw":
+            ops.store_column(x, self.memory.observations, self.cursor)
+            self._policy_in = x
+        elif plan.obs == "K5N":
             self._normalize_into(x, self.obs_norm, True)
-        fuse = self._env_fused(self._rollout_mlp())
-        post = self._k14f_post(fuse)
-        self._sample_into_buffer(fuse_env=fuse, post=post)
-        if not fuse:
+        elif plan.obs != "trunk":
+            _no_form("the observation store", plan.obs)
+        self._sample_into_buffer(plan, raw_x=x if plan.obs == "trunk" else None)
+        if plan.env != "in-head":
             env.step_device()
-        if post is None:
-            self._post(env.rew, env.term, env.trunc, env.final_obs)
+        if plan.post != "K14F":
+            self._post(plan, env.rew, env.term, env.trunc, env.final_obs)
 
     def _rollout_step_graph(self):
         """The device env step captured once into a hipGraph and replayed: every per-step argument
         (buffer column, RNG step) lives in the device cursor, so the same graph serves all steps."""
-        if self._small_rollout() is not None:   # one launch per step: nothing to capture
+        if self.plan().driver == "K32":   # one launch per step: nothing to capture
             self._rollout_step_device()
             return
-        key = tuple(p.data_ptr() for p in self.policy.parameters())
+        key = tuple(p.data_ptr() for p in self._params)
         if self._graph is not None and key != self._graph_key:
             self._graph = None  # parameters were re-homed (e.g. flat buffers attached): re-capture
         if self._graph is None:
@@ -566,11 +567,10 @@ class _OnPolicyAgent:
         """k consecutive device env steps captured into ONE hipGraph (k x 5 kernels) and replayed as a unit: a
         per-step replay leaves the GPU idle ~8 us between graphs while the host launches the next (r02 trace:
         127 such gaps = 1.0 ms of a 72 ms iteration).  Same replay invariance as _rollout_step_graph."""
-        k32 = self._small_rollout()
-        if k32 is not None:   # the k steps as one K32 launch
-            self._small_rollout_launch(k32, k)
+        if self.plan().driver == "K32":   # the k steps as one K32 launch
+            self._small_rollout_launch(k)
             return k
-        key = (k,) + tuple(p.data_ptr() for p in self.policy.parameters())
+        key = (k,) + tuple(p.data_ptr() for p in self._params)
         if self._chunk_graph is not None and key != self._chunk_key:
             self._chunk_graph = None
         if self._chunk_graph is None:
@@ -596,7 +596,7 @@ class _OnPolicyAgent:
           * done envs continue from infos[i]["reset_obs"]; with env_name "Atari" a life loss (terminal, not
             truncated) keeps the path and the observation (ppoclip_agent.py:93-94);
           * A2C's mid-rollout truncation bootstraps are V(norm(reset_obs)) (a2c_agent.py:88-95, boot_from_reset)."""
-        env, dev = self.envs, self.device
+        env, dev, plan = self.envs, self.device, self.plan()
         dt = np.uint8 if self.raw_obs else np.float32
         shape = (self.n_envs,) + (tuple(self.obs_shape) if self.raw_obs else (-1,))
         alias = None
@@ -605,14 +605,14 @@ class _OnPolicyAgent:
             if not self.use_obsnorm:
                 alias = env.buf_obs
         x = torch.as_tensor(self._host_obs, device=dev)
-        if self.raw_obs:
+        if plan.obs == "raw":
             ops.store_column(x.contiguous(), self.memory.observations, self.cursor)
             self._policy_in = x
         else:
-            if self.use_obsnorm:
+            if plan.rms is not None:
                 self._rms_update(x)
             self._normalize_into(x, self.obs_norm, True)
-        self._sample_into_buffer()
+        self._sample_into_buffer(plan)
         t = self._t
         acts = (self.memory.actions[:, t]).cpu().numpy()
         if self.discrete:
@@ -632,7 +632,7 @@ class _OnPolicyAgent:
         # K8 reads the bootstrap rows where a path closes: the final observations, except A2C's mid-rollout
         # truncations (reset_obs); the last step's closures use the final observations for every algorithm
         boot_src = obs if (self.boot_from_reset and t < self.n_steps - 1) else next_obs
-        self._post(torch.as_tensor(np.asarray(rews, np.float32), device=dev),
+        self._post(plan, torch.as_tensor(np.asarray(rews, np.float32), device=dev),
                    torch.as_tensor(np.asarray(terms, np.uint8), device=dev),
                    torch.as_tensor(np.asarray(truncs, np.uint8), device=dev), torch.as_tensor(boot_src, device=dev))
         self._host_obs = obs
@@ -650,22 +650,11 @@ class _OnPolicyAgent:
             self._perm_buf = torch.empty(n, dtype=torch.int64, device=self.device)
         return ops.random_permutation(n, self.seed, counter, out=self._perm_buf)
 
-    def _deferred_bootstraps(self, hidden_only=False):
-        """V([truncation slots; last-step final obs]) in one critic pass ([2N] values), or with hidden_only the
-        critic's hidden pre-activations ([2N, 256], for the value-fused scan xpa_gae_scan_value; None when the
-        policy has no fused critic)."""
-        x = self._boot_pair
-        fm = self._rollout_mlp()
-        if hidden_only:
-            return fm.rollout_value_hidden(x)
-        if fm is not None:
-            v = fm.rollout_value(x)
-        else:
-            with torch.no_grad():
-                v = policy_heads(self.policy, x)[2].contiguous()
-        return v.reshape(-1)
+    def _deferred_bootstraps(self, plan):
+        """V([truncation slots; last-step final obs]) in one critic pass ([(S + 1) N] values)."""
+        return self._values(plan, self._boot_pair).contiguous().reshape(-1)
 
-    def _raw_last_bootstraps(self):
+    def _raw_last_bootstraps(self, plan):
         """raw_defer: V(final frames of the last step) for the last column's bootstraps (0 where terminal), written
         by xpa_rollout_bootstrap_fixup; a mid-rollout non-terminal close (which would have needed its own value)
         contradicts the env's truncation_implies_terminal contract and raises."""
@@ -676,10 +665,10 @@ class _OnPolicyAgent:
             raise RuntimeError("a non-terminal truncation inside the rollout: the env breaks truncation_implies_"
                                "terminal; set config.defer_bootstrap = False")
         N = self.n_envs
-        if getattr(self, "_raw_vb", None) is None:
+        if self._raw_vb is None:
             self._raw_vb = torch.zeros((2 * N,), dtype=torch.float32, device=self.device)
             self._raw_slots = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self._raw_vb[N:].copy_(self._heads(self.envs.final_obs)[2])
+        self._raw_vb[N:].copy_(self._heads(plan.value_trunk, self.envs.final_obs)[2])
         ops.bootstrap_fixup(self._raw_vb, self._raw_slots, mem.terminals, mem.boot)
 
     def _raw_mid_from_next(self):
@@ -707,52 +696,77 @@ class _OnPolicyAgent:
         self._overflow_host.copy_(self.slot_overflow, non_blocking=True)
         self._overflow_event.record()
 
+    def _gathered_update(self, feed, obs_flat, idx, act_flat, adv_flat, ret_flat, logp_flat, use_advnorm, batches):
+        """One minibatch through K4's gather in the "epoch" (appended to batches, None returned), "slot" or "all-reduce"
+        feed; returns the update's loss scalars."""
+        # one (obs_mb, adv_part) pair per minibatch size: a ragged last minibatch keeps its own buffers, so
+        # the pointers the learner's slot graphs are keyed by stay stable across epochs
+        key = (idx.shape[0], obs_flat.dtype, tuple(obs_flat.shape[1:]))
+        bufs = self._mb_bufs.get(key)
+        if bufs is None:
+            bufs = self._mb_bufs[key] = (
+                torch.empty(key[:1] + key[2], dtype=obs_flat.dtype, device=self.device),
+                torch.empty((ops.gather_num_partials(key[0]), 2), dtype=torch.float64, device=self.device))
+        self.obs_mb, self.adv_part = bufs
+        part = self.adv_part if use_advnorm else None
+
+        def gather(idx=idx, obs_out=self.obs_mb):
+            return ops.gather_minibatch(idx, obs_flat, adv=adv_flat if use_advnorm else None, obs_out=obs_out,
+                                        adv_partials=part)
+        if feed == "epoch":
+            batches.append((self.obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat, part, gather))
+            return None
+        if feed == "slot":
+            # the gather rides in the learner's slot graph when the update is graphed (writes obs_mb / adv_part)
+            return self.learner.update_fused(self.obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat, part,
+                                             pre=gather)
+        obs_mb, part = gather()
+        if part is not None:
+            import torch.distributed as tdist
+            tdist.all_reduce(part, op=tdist.ReduceOp.SUM)   # (sum, sumsq) over all ranks' minibatches,
+            part.div_(self.world)                           # averaged: mean / var of the global minibatch
+        return self.learner.update_fused(obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat, part)
+
     def _update_phase(self):
-        mem = self.memory
+        plan, mem = self.plan(), self.memory
         mem.size = self.n_steps
-        if self.raw_defer:
-            self._raw_last_bootstraps()
-        elif self.raw_mid_next:
+        if plan.close == "raw-last":
+            self._raw_last_bootstraps(plan)
+        elif plan.close == "raw-mid-next":
             self._raw_mid_from_next()
-        zc = vk = None
-        one_slot = self.defer_boot and self.n_slots == 1   # the fused scans take one deferred truncation per env
-        if (one_slot and not self.atari and not mem._pending and self.fuse_value_gae and self.value_gemm
-                and self._rollout_mlp() is not None):
-            if getattr(self, "_vboot", None) is None:
-                self._vboot = torch.empty(self._boot_pair.shape[0], dtype=torch.float32, device=self.device)
-            vk = self._rollout_mlp().rollout_value_split(self._boot_pair, out=self._vboot)
-        if (vk is None and one_slot and not self.atari and not mem._pending and self.fuse_value_gae
-                and ops.gae_value_ok(self.n_steps) and self._rollout_mlp() is not None):
-            zc = self._deferred_bootstraps(hidden_only=True)
-        if vk is not None:
-            # K40V's values, then one launch: the fixup's bootstrap writes fused into the compact-closure GAE scan
-            ops.gae_scan_compact(mem.rewards, mem.values, mem.terminals, self.slot_t, vk, mem.gamma, mem.gae_lam,
-                                 mem.use_gae, adv=mem._advantages, ret=mem._returns, boot=mem.boot)
-            mem._dirty = False
-            self.gae_form = "compact"
-        elif zc is not None:
+        gae = plan.gae
+        if gae == "scan":
+            mem.compute_advantages()
+        elif gae == "value":
             # one launch: the critic's output layer, the fixup's bootstrap writes and the compact GAE scan
             fm = self._rollout_mlp()
             lin_co = fm.critic[-1][0]
             _, code, slope = fm.critic[-2]
+            zc = fm.rollout_value_hidden(self._boot_pair, trunk=plan.value_trunk)
             ops.gae_scan_value(mem.rewards, mem.values, mem.terminals, self.slot_t, zc, (code, slope), lin_co.weight,
                                lin_co.bias, mem.gamma, mem.gae_lam, mem.use_gae, adv=mem._advantages,
                                ret=mem._returns, boot=mem.boot)
             mem._dirty = False
             self.gae_form = "value"
-        elif self.defer_boot:
-            vboot = self._deferred_bootstraps()
-            if one_slot and not self.atari and not mem._pending:
+        elif gae in ("K40V+compact", "compact", "fixup+scan"):
+            if gae == "K40V+compact":   # the deferred bootstrap rows' critic on the split GEMM
+                if self._vboot is None:
+                    self._vboot = torch.empty(self._boot_pair.shape[0], dtype=torch.float32, device=self.device)
+                vboot = self._rollout_mlp().rollout_value_split(self._boot_pair, out=self._vboot,
+                                                                trunk=plan.value_trunk)
+            else:
+                vboot = self._deferred_bootstraps(plan)
+            if gae == "fixup+scan":
+                ops.bootstrap_fixup(vboot, self.slot_t, mem.terminals, mem.boot)
+                mem.compute_advantages()
+            else:
                 # one launch: the fixup's bootstrap writes fused into the compact-closure GAE scan
                 ops.gae_scan_compact(mem.rewards, mem.values, mem.terminals, self.slot_t, vboot, mem.gamma,
                                      mem.gae_lam, mem.use_gae, adv=mem._advantages, ret=mem._returns, boot=mem.boot)
                 mem._dirty = False
                 self.gae_form = "compact"
-            else:
-                ops.bootstrap_fixup(vboot, self.slot_t, mem.terminals, mem.boot)
-                mem.compute_advantages()
         else:
-            mem.compute_advantages()
+            _no_form("the advantage scan", gae)
         NT, B = self.buffer_size, self.batch_size
         obs_flat = mem.observations.reshape((NT,) + tuple(mem.observations.shape[2:]))
         act_flat = mem.actions.reshape(-1)
@@ -761,78 +775,44 @@ class _OnPolicyAgent:
         logp_flat = mem.auxiliary_infos["old_logp"].reshape(-1) if self.algo == "ppo" else None
         use_advnorm = mem.use_advnorm
         scalars = None
-        fm = self._rollout_mlp() if not self.global_advnorm else None
-        rows_path = fm is not None and self.fuse_gather and fm.rows_ok(obs_flat)
-        # graphed small-batch updates (C1): the epoch's minibatches go to the learner as one list, which replays them
-        # as one captured graph once every slot is captured (learners.update_epoch)
-        epoch_batches = (not rows_path and not self.global_advnorm and getattr(self.learner, "graph_updates", False)
-                         and hasattr(self.learner, "update_epoch"))
-        # K30: the whole small-MLP update (gather + forward + loss + backward + clip + Adam) in one launch per
-        # minibatch, an epoch of them one captured graph (learners.small_epoch)
-        small = (not rows_path and not self.global_advnorm and hasattr(self.learner, "small_update_ok")
-                 and self.learner.small_update_ok(obs_flat, B))
+        feed, log = plan.feed, self.update_log
+        if feed not in ("rows", "small", "epoch", "slot", "all-reduce"):
+            _no_form("the minibatch feed", feed)
         for _ in range(self.n_epoch):
             perm = self.epoch_permutation(NT)
-            if small:
+            if feed == "small":
+                # K30: the whole small-MLP update (gather + forward + loss + backward + clip + Adam) in one launch per
+                # minibatch, an epoch of them one captured graph (learners.small_epoch)
                 batches = [(perm[s:s + B], act_flat, adv_flat, ret_flat, logp_flat) for s in range(0, NT, B)]
-                outs = self.learner.small_epoch(obs_flat, batches, use_advnorm, keep_all=self.update_log is not None)
+                outs = self.learner.small_epoch(obs_flat, batches, use_advnorm, keep_all=log is not None)
                 scalars = outs[-1]
-                if self.update_log is not None:
-                    self.update_log.extend(outs)
+                if log is not None:
+                    log.extend(outs)
                 continue
             batches = []
             for start in range(0, NT, B):
                 idx = perm[start:start + B]
                 b = idx.shape[0]
-                if rows_path:
+                if feed == "rows":
                     # K4 folded into K13: the update reads the minibatch rows (and forms the adv moments) through idx
-                    parts = self.__dict__.setdefault("_adv_parts", {})
                     g = ops.gather_num_partials(b)
-                    if g not in parts:   # one per minibatch size (a ragged last minibatch keeps its own)
-                        parts[g] = torch.empty((g, 2), dtype=torch.float64, device=self.device)
-                    self.adv_part = parts[g]
-                    part = self.adv_part if use_advnorm else None
+                    if g not in self._adv_parts:   # one per minibatch size (a ragged last minibatch keeps its own)
+                        self._adv_parts[g] = torch.empty((g, 2), dtype=torch.float64, device=self.device)
+                    self.adv_part = self._adv_parts[g]
                     scalars = self.learner.update_fused(Rows(obs_flat, idx), idx, act_flat, adv_flat, ret_flat,
-                                                        logp_flat, part)
-                    if self.update_log is not None:
-                        self.update_log.append(scalars.clone())
-                    continue
-                # one (obs_mb, adv_part) pair per minibatch size: a ragged last minibatch keeps its own buffers, so
-                # the pointers the learner's slot graphs are keyed by stay stable across epochs
-                mbs = self.__dict__.setdefault("_mb_bufs", {})
-                bufs = mbs.get((b, obs_flat.dtype, tuple(obs_flat.shape[1:])))
-                if bufs is None:
-                    bufs = (torch.empty((b,) + tuple(obs_flat.shape[1:]), dtype=obs_flat.dtype, device=self.device),
-                            torch.empty((ops.gather_num_partials(b), 2), dtype=torch.float64, device=self.device))
-                    mbs[(b, obs_flat.dtype, tuple(obs_flat.shape[1:]))] = bufs
-                self.obs_mb, self.adv_part = bufs
-                def gather(idx=idx, obs_out=self.obs_mb, part=self.adv_part):
-                    return ops.gather_minibatch(idx, obs_flat, adv=adv_flat if use_advnorm else None,
-                                                obs_out=obs_out, adv_partials=part if use_advnorm else None)
-                if epoch_batches:
-                    batches.append((self.obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat,
-                                    self.adv_part if use_advnorm else None, gather))
-                    continue
-                if not self.global_advnorm:
-                    # the gather rides in the learner's slot graph when the update is graphed (writes obs_mb / adv_part)
-                    scalars = self.learner.update_fused(self.obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat,
-                                                        self.adv_part if use_advnorm else None, pre=gather)
-                    if self.update_log is not None:
-                        self.update_log.append(scalars.clone())
-                    continue
-                obs_mb, part = gather()
-                if part is not None:
-                    import torch.distributed as tdist
-                    tdist.all_reduce(part, op=tdist.ReduceOp.SUM)   # (sum, sumsq) over all ranks' minibatches,
-                    part.div_(self.world)                           # averaged: mean / var of the global minibatch
-                scalars = self.learner.update_fused(obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat, part)
-                if self.update_log is not None:
-                    self.update_log.append(scalars.clone())
+                                                        logp_flat, self.adv_part if use_advnorm else None)
+                else:
+                    scalars = self._gathered_update(feed, obs_flat, idx, act_flat, adv_flat, ret_flat, logp_flat,
+                                                    use_advnorm, batches)
+                if log is not None and scalars is not None:
+                    log.append(scalars.clone())
             if batches:
-                outs = self.learner.update_epoch(batches, keep_all=self.update_log is not None)
+                # graphed small-batch updates (C1): the epoch's minibatches go to the learner as one list, which replays
+                # them as one captured graph once every slot is captured (learners.update_epoch)
+                outs = self.learner.update_epoch(batches, keep_all=log is not None)
                 scalars = outs[-1]
-                if self.update_log is not None:
-                    self.update_log.extend(outs)
+                if log is not None:
+                    log.extend(outs)
         self.last_info = scalars
         self.iterations += 1
         if self.defer_boot:
@@ -856,12 +836,12 @@ class _OnPolicyAgent:
 
     # ---- public API (ppoclip_agent.py:59-111) -------------------------------------------------------------
     def train(self, train_steps, log=True):
-        if not self.device_env:
-            step_fn = self._rollout_step_host
+        plan = self.plan()
+        step_fn = {"host": self._rollout_step_host, "graph-chunk": self._rollout_step_graph,
+                   "graph-step": self._rollout_step_graph}.get(plan.driver, self._rollout_step_device)
+        if plan.driver == "host":
             self._host_obs = None   # every call starts from envs.buf_obs (ppoclip_agent.py:60)
-        else:
-            step_fn = self._rollout_step_graph if self.use_graph else self._rollout_step_device
-        chunk = self.graph_chunk if (self.device_env and self.use_graph) else 1
+        chunk = plan.chunk
         left = train_steps
         while left > 0:
             t0 = time.perf_counter()
@@ -871,9 +851,9 @@ class _OnPolicyAgent:
                 fc = self._rollout_cnn()
                 if fc is not None:
                     fc.refresh()   # outside any captured graph: the replays read the refreshed weight copy
-                fm = self._rollout_mlp()
-                if fm is not None:
-                    fm.rollout_refresh()   # K40R's weight planes for this rollout (same: outside the graphs)
+                pair = self.plan().pair
+                if pair is not None:
+                    self._rollout_mlp().rollout_refresh(pair)   # K40R's weight planes (same: outside the graphs)
             if chunk > 1 and left >= chunk and self._t % chunk == 0 and self.n_steps - self._t >= chunk:
                 k = self._rollout_chunk_graph(chunk)
             else:

@@ -72,6 +72,7 @@ class _Discrete:
 
 class SynthBoxVecEnv:
     """n_envs SynthBox(D, A) environments resident on one GPU."""
+    kind = "synthbox"   # the env's name in rollout_plan.RolloutFacts.env
 
     def __init__(self, n_envs, obs_dim, act_dim, seed=1, discrete=False, max_episode_steps=1000, device=None,
                  shard=0):
@@ -186,6 +187,7 @@ class SynthAtariVecEnv:
     (SynthAtariEnv); kernel: csrc/atari.hip (K15).  Same interface as SynthBoxVecEnv: obs, act_in,
     final_obs, rew/term/trunc, step_device(), host step() with the DummyVecEnv_Atari contract."""
 
+    kind = "synthatari"
     HW, STACK = 84, 4
 
     def __init__(self, n_envs, n_actions=6, seed=1, max_episode_steps=27000, device=None, shard=0):
@@ -294,7 +296,7 @@ class CartPoleVecEnv:
     input the rollout kernels write.  Same interface as SynthBoxVecEnv (obs, act_in, final_obs, rew / term /
     trunc, step_device(), host step() with DummyVecEnv_Gym's contract).  CPU checker:
     oracle/synth_env.CartPoleEnv."""
-    kind = "cartpole"   # agents._small_rollout: K32 steps this env inside the fused rollout step
+    kind = "cartpole"   # rollout_plan: K32 steps this env inside the fused rollout step
 
     def __init__(self, n_envs, seed=1, max_episode_steps=500, device=None, shard=0):
         self.num_envs, self.seed, self.max_episode_steps = int(n_envs), int(seed), int(max_episode_steps)

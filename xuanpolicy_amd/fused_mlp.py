@@ -26,6 +26,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .policies import Basic_Identical, _splitk_splits, policy_discrete
+from .rollout_plan import RolloutShape
 
 
 def _act_code(m):
@@ -113,7 +114,7 @@ def _vec4_rows(t):
 
 def _no_form(stage, form):
     """The one error of a stage handed a plan it cannot run (a raise, not an assert: python -O must not strip it)."""
-    raise RuntimeError("update plan: %s has no form %r" % (stage, form))
+    raise RuntimeError("plan: %s has no form %r" % (stage, form))
 
 
 _TRUNK_FWD = {   # UpdatePlan.trunk_fwd -> the entry points it launches
@@ -430,11 +431,9 @@ class FusedActorCritic:
             plan = self._plans[key] = self._make_plan(x, dz_ok)
         return plan
 
-    def _rep_forward(self, x, form=None, sign=None, norm=None, adv=None, adv_partials=None):
-        """The representation's forward in the given UpdatePlan.trunk_fwd form (sign: the plan's sign_bits); the
-        rollout-side callers give none and take the plain form for x."""
-        if form is None and norm is None:
-            form, sign = self._trunk_form(x, False)
+    def _rep_forward(self, x, form, sign=None, norm=None, adv=None, adv_partials=None):
+        """The representation's forward in the given form: an UpdatePlan.trunk_fwd (sign: the plan's sign_bits) or the
+        rollout's "K13-norm" (x RAW, normalised inside the first layer; norm: see below)."""
         if form in ("K40F-idx", "K40F-pitched"):
             return self._wide_forward(x, adv, adv_partials, form == "K40F-idx")
         if form in ("K13-gather", "K13-gather-sign", "K13-gather-only"):
@@ -464,11 +463,11 @@ class FusedActorCritic:
                       ops._p(adv_partials) if adv_partials is not None else None, ops._p(x.gathered), *sign_out,
                       ops._stream(x.device))
             return [h] + self._chain_forward(self.rep[1:], h)
-        if norm is not None:
+        if form == "K13-norm":
             # x RAW: observation normalisation fused into the first layer (xpa_thin_linear_act_fwd_norm);
             # norm = (mean, var, clip, xn_out, col, col_ld, cursor)
-            if not self.thin0:
-                raise ValueError("fused normalisation needs the thin first layer (K13)")
+            if not self.thin0 or norm is None:
+                _no_form("a trunk without the thin first layer (K13)", form)
             lin, code, slope = self.rep[0]
             mean, var, clip, xn, col, col_ld, cursor = norm
             h = torch.empty((x.shape[0], lin.out_features), dtype=torch.float32, device=x.device)
@@ -520,7 +519,7 @@ class FusedActorCritic:
 
     @torch.no_grad()
     def forward(self, x):
-        rep_outs = self._rep_forward(x)
+        rep_outs = self._rep_forward(x, self._trunk_form(x, False)[0])
         s = rep_outs[-1] if rep_outs else x
         a_outs = self._chain_forward(self.actor, s)
         c_outs = self._chain_forward(self.critic, s)
@@ -536,22 +535,37 @@ class FusedActorCritic:
     # the start of every rollout (rollout_refresh, outside any captured graph: the weights change only in the update)
     ROLLOUT_SPLIT = True
 
-    def rollout_refresh(self):
-        """Split the paired hidden layer's weights for K40R (one launch, before a rollout's first step); afterwards
-        rollout_act uses the planes until the next refresh.  A no-op (planes dropped) where K40R does not apply."""
-        lin_a, lin_c = self.actor[0][0], self.critic[0][0]
-        ok = (self.ROLLOUT_SPLIT and ops.S3_GEMMS and self.pair is not None and self.gemm_heads
-              and lin_a.in_features == 256 and lin_a.out_features == 256 and lin_c.out_features == 256)
-        if not ok:
-            self._roll_split = None
-            return
-        bufs = self._split_many([(lin_a.weight.t(), "roll_a"), (lin_c.weight.t(), "roll_c")])
-        self._roll_split = (bufs[0], bufs[1])
+    def rollout_shape(self):
+        """The policy shape the rollout's planner decides from (rollout_plan.RolloutShape)."""
+        lin_a, (lin_ch, _, _), lin_co = self.actor[0][0], self.critic[-2], self.critic[-1][0]
+        sq = lambda lin: lin.in_features == 256 and lin.out_features == 256   # noqa: E731
+        return RolloutShape(self.thin0, len(self.rep), self.rep[0][0].in_features if self.rep else 0,
+                            bool(self.gemm_heads and sq(lin_a) and self.critic[0][0].out_features == 256),
+                            len(self.critic) == 2 and lin_co.out_features == 1 and sq(lin_ch))
 
-    def _rollout_pair(self, s):
-        rs = self._roll_split
-        if rs is not None and s.dim() == 2 and s.shape[1] == 256 and _vec4_rows(s):
+    def rollout_refresh(self, pair):
+        """Before a rollout's first step, outside any captured graph.  pair "K40R": the paired hidden layer's weights
+        split into K40R's planes (one launch), which rollout_act and K40V read until the next refresh; any other
+        form drops them."""
+        self._roll_split = None
+        if pair == "K40R":
+            bufs = self._split_many([(self.actor[0][0].weight.t(), "roll_a"), (self.critic[0][0].weight.t(), "roll_c")])
+            self._roll_split = (bufs[0], bufs[1])
+
+    def _planes(self, stage, s=None):
+        """K40R's planes for a stage planned on them; s: the [n, 256] rows it reads as 16-B vectors."""
+        if self._roll_split is None:
+            raise RuntimeError("rollout plan: %s needs K40R's planes (rollout_refresh(\"K40R\"))" % stage)
+        if s is not None and not (s.dim() == 2 and s.shape[1] == 256 and _vec4_rows(s)):
+            raise RuntimeError("rollout plan: %s reads [n, 256] rows of 16-B vectors" % stage)
+        return self._roll_split
+
+    def _rollout_pair(self, s, pair):
+        if pair == "K40R":
+            rs = self._planes("the paired hidden layer", s)
             return ops.s3_gemm_rows_pair(s, rs[0], rs[1], self.pair[1])
+        if pair != "linear":
+            _no_form("the rollout's paired hidden layer", pair)
         return F.linear(s, self.pair[0], self.pair[1])
 
     # r06 (K40T, opt-in: XPA_ROLLOUT_TRUNK=1): with the normalisation fused (norm given), a one-layer thin trunk
@@ -560,29 +574,32 @@ class FusedActorCritic:
     ROLLOUT_TRUNK = os.environ.get("XPA_ROLLOUT_TRUNK", "0") == "1"
 
     def _rollout_trunk_pair(self, x, norm):
-        rs = self._roll_split
-        if (not self.ROLLOUT_TRUNK or norm is None or rs is None or not self.thin0 or len(self.rep) != 1
-                or x.dim() != 2 or x.dtype != torch.float32 or x.stride(1) != 1):
-            return None
+        """K40T: trunk and paired hidden layer in one launch."""
+        rs = self._planes("K40T")
+        if not self.thin0 or len(self.rep) != 1 or norm is None:
+            _no_form("a trunk that is not one thin layer", "K40T")
         lin, code, slope = self.rep[0]
-        if lin.in_features > 18 or lin.out_features != 256:
-            return None
         mean, var, clip, xn, col, col_ld, cursor = norm
         return ops.s3_gemm_rows_pair_trunk(x, lin.weight, lin.bias, code, slope, mean, var, clip, xn, col, col_ld,
                                            cursor, rs[0], rs[1], self.pair[1])
 
+    def _trunk_out(self, x, trunk, norm=None):
+        """The representation's output for a rollout-side pass over the tensor x (trunk None, a direct caller: the
+        plain form for x)."""
+        rep_outs = self._rep_forward(x, trunk or self._trunk_form(x, False)[0], norm=norm)
+        return rep_outs[-1] if rep_outs else x
+
     @torch.no_grad()
     def rollout_act(self, x, dist, cursor, seed, buf_act, buf_logp, buf_val, env_in, act_clip=1.0, norm=None,
-                    env=None, post=None):
-        """Policy step of the rollout: trunk, paired hidden GEMM, then K14 (heads + sample + store).
-        norm: see _rep_forward (x is then the raw observation).  env: a device SynthBox env whose step runs
-        inside the same K14 launch (ops.rollout_policy_head_synthbox; the caller skips env.step_device()).
-        post (with env, r06): K8's post step in that launch too (K14F; ops.rollout_policy_head_synthbox(post=))."""
-        z = self._rollout_trunk_pair(x, norm)
-        if z is None:
-            rep_outs = self._rep_forward(x, norm=norm)
-            s = rep_outs[-1] if rep_outs else x
-            z = self._rollout_pair(s)
+                    env=None, post=None, trunk=None, pair="linear"):
+        """Policy step of the rollout in the RolloutPlan's forms: trunk, paired hidden GEMM (pair), then K14 (heads +
+        sample + store).  trunk "K13-norm" / "K40T": x is the raw observation, norm = _rep_forward's.  env: a device
+        SynthBox env whose step runs inside the same K14 launch (K14E, ops.rollout_policy_head_synthbox; the caller
+        skips env.step_device()).  post (with env, r06): K8's post step in that launch too (K14F)."""
+        if trunk == "K40T":
+            z = self._rollout_trunk_pair(x, norm)
+        else:
+            z = self._rollout_pair(self._trunk_out(x, trunk, norm), pair)
         H = ops.HEAD_HIDDEN
         lin_ao = self.actor[-1][0]
         lin_co = self.critic[-1][0]
@@ -598,40 +615,30 @@ class FusedActorCritic:
                                 lin_co.bias, self.logstd, cursor, seed, buf_act, buf_logp, buf_val, env_in, act_clip)
 
     @torch.no_grad()
-    def rollout_value_hidden(self, x):
+    def rollout_value_hidden(self, x, trunk=None):
         """Critic up to its last hidden pre-activation [n, 256] (the value-fused GAE scan applies the
         activation and the output layer)."""
-        rep_outs = self._rep_forward(x)
-        s = rep_outs[-1] if rep_outs else x
         lin_ch = self.critic[-2][0]
-        return F.linear(s, lin_ch.weight, lin_ch.bias)
+        return F.linear(self._trunk_out(x, trunk), lin_ch.weight, lin_ch.bias)
 
     @torch.no_grad()
-    def rollout_value_split(self, x, out=None):
+    def rollout_value_split(self, x, out=None, trunk=None):
         """K40V (r06): the critic from x to its value in two launches — the trunk, then the critic's hidden layer on the
-        split GEMM (the rollout's planes of Wh_critic^T, rollout_refresh) with act . w_out + b_out in its epilogue — or
-        None where that form does not apply (no rollout planes, a critic deeper than one hidden layer)."""
-        rs = self._roll_split
-        if rs is None or len(self.critic) != 2:
-            return None
+        split GEMM (the rollout's planes of Wh_critic^T, rollout_refresh) with act . w_out + b_out in its epilogue.
+        The planner gives this form to RolloutShape.critic256 alone."""
         lin_ch, code, slope = self.critic[-2]
         lin_co = self.critic[-1][0]
-        if lin_co.out_features != 1 or lin_ch.in_features != 256 or lin_ch.out_features != 256:
-            return None
-        rep_outs = self._rep_forward(x)
-        s = rep_outs[-1] if rep_outs else x
-        if not (isinstance(s, torch.Tensor) and s.dim() == 2 and s.shape[1] == 256 and _vec4_rows(s)):
-            return None
-        return ops.s3_gemm_value(s, rs[1], 256, lin_ch.bias, code, slope, lin_co.weight.view(-1), lin_co.bias, out=out)
+        s = self._trunk_out(x, trunk)
+        rs = self._planes("K40V", s)
+        return ops.s3_gemm_value(s, rs[1], 256, lin_ch.bias, code, slope, lin_co.weight.view(-1),
+                                 lin_co.bias, out=out)
 
     @torch.no_grad()
-    def rollout_value(self, x, out=None):
+    def rollout_value(self, x, out=None, trunk=None):
         """Critic only (bootstrap values): trunk, critic hidden GEMM, K14 value head."""
-        rep_outs = self._rep_forward(x)
-        s = rep_outs[-1] if rep_outs else x
         lin_ch, code, slope = self.critic[-2]
         lin_co = self.critic[-1][0]
-        z = F.linear(s, lin_ch.weight, lin_ch.bias)
+        z = F.linear(self._trunk_out(x, trunk), lin_ch.weight, lin_ch.bias)
         return ops.value_head(z, (code, slope), lin_co.weight, lin_co.bias, out=out)
 
     @torch.no_grad()
