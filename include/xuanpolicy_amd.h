@@ -231,7 +231,21 @@ int xpa_cartpole_step(int64_t n_envs, const float *act_in, int64_t ld_act, doubl
                       int32_t *ep_step, uint32_t *ep_index, float *ep_score, float *ep_last_score,
                       int32_t *ep_last_len, uint32_t seed, int32_t max_episode_steps, xpa_stream_t stream);
 
-/* K32 — `steps` whole device env steps of a small-MLP Categorical PPO / A2C agent on CartPole in ONE launch (one
+/* K18P — Pendulum-v1 device env step (the env of the reference's classic_control/Pendulum-v1.yaml configs; g = 10,
+ * m = l = 1, dt = 0.05, max speed 8, max torque 2).  One thread per env, f64 state [n_envs, 2] = (th, thdot), every
+ * operation rounded on its own (no fma):
+ *   u = clamp((double)act_in[n * ld_act], -2, 2);  an = floor_mod(th + pi, 2 pi) - pi  (Python's %)
+ *   cost = an^2 + 0.1 thdot^2 + 0.001 u^2;  thdot' = clamp(thdot + (15 sin(th) + 3 u) * 0.05, -8, 8)
+ *   th' = th + thdot' * 0.05;  reward = (float)(-cost);  observation = (float)cos(th'), (float)sin(th'), (float)thdot'
+ * Never terminated; truncated at max_episode_steps; done envs auto-reset with hashed th0 = (2 u01 - 1) pi,
+ * thdot0 = 2 u01 - 1 (f32-exact uniforms, then f64).  final_obs [n_envs, 3], obs (row stride ld_obs), rew, term,
+ * trunc and the counters follow xpa_cartpole_step's contract. */
+int xpa_pendulum_step(int64_t n_envs, const float *act_in, int64_t ld_act, double *state, float *obs,
+                      int64_t ld_obs, float *final_obs, float *rew, uint8_t *term, uint8_t *trunc,
+                      int32_t *ep_step, uint32_t *ep_index, float *ep_score, float *ep_last_score,
+                      int32_t *ep_last_len, uint32_t seed, int32_t max_episode_steps, xpa_stream_t stream);
+
+/* K32— `steps` whole device env steps of a small-MLP Categorical PPO / A2C agent on CartPole in ONE launch (one
  * workgroup; the step loop of ppoclip_agent.py:43-101 / a2c_agent.py:42-98 with DummyVecEnv_Gym's auto-reset):
  * per step, obs_rms.update (xpa_rms_update's sums and merge, in its order), the normalisation into obs_norm and the
  * buffer column (xpa_obs_normalize), the policy forward — representation Linear(d_in, h0) + act, actor Linear(h0,
@@ -278,6 +292,12 @@ typedef struct XpaSmallRolloutArgs {
 } XpaSmallRolloutArgs;
 int64_t xpa_small_rollout_lds_floats(int64_t n_envs, int64_t d_in, int64_t h0, int64_t h1, int64_t h2, int64_t k);
 int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *args, xpa_stream_t stream);
+/* K32 for a Gaussian head on Pendulum (the same kernel, instantiated over the env / head pair): d_in == 3, k == 1 (Wa /
+ * ba the mu layer, A = 1), env_state [n_envs, 2], final_obs [n_envs, 3]; the sampler is xpa_rollout_sample's Gaussian
+ * arithmetic (Box-Muller draw, log-prob, the raw action into buf_act, the action clipped to +-act_clip into act_in)
+ * and the env K18P's step (xpa_pendulum_step) with the clipped action.  logstd: float [1]. */
+int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *args, const float *logstd, float act_clip,
+                               xpa_stream_t stream);
 
 /* K19 — PER-DQN TD target, loss, gradient and priorities (BASELINE.json configs[4]; replaces the tensor algebra
  * of PerDQN_Learner.update, xuance/torch/learners/qlearning_family/perdqn_learner.py:23-30, 48).
@@ -373,6 +393,15 @@ typedef struct XpaSmallMlpArgs {
 } XpaSmallMlpArgs;
 int64_t xpa_small_mlp_lds_floats(int64_t batch, int64_t d_in, int64_t h0, int64_t h1, int64_t h2, int64_t k);
 int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t stream);
+/* K30 for a Gaussian head (the same kernel with K2's Gaussian loss stage): args->k is the action dimension A,
+ * 1 <= A <= 16, Wa / ba the mu layer, actions float [n_rows, A]; logstd float [A].  The loss stage is
+ * xpa_policy_loss's Gaussian per-row arithmetic for PPO and A2C (log-prob summed over A, entropy, d mu, d logstd, the
+ * same scalars); d logstd is reduced over the rows in a fixed order into g_logstd [A], which must lie inside the flat
+ * gradient (args->grad, n floats), so that clip_grad_norm_ and Adam cover it; in the split form it goes through
+ * grad_part[g] at the same offset and the finalize sums it in g order.  xpa_small_mlp_lds_floats(..., k = A) gives
+ * the LDS budget. */
+int xpa_small_mlp_update_gauss(const XpaSmallMlpArgs *args, const float *logstd, float *g_logstd,
+                               xpa_stream_t stream);
 
 /* K10 — activation backward fused with bias-gradient column sums for one MLP layer (row-major
  * [rows, cols]).  Replaces the activation backward and the bias-gradient reduction torch autograd runs

@@ -157,6 +157,7 @@ class _OnPolicyAgent:
         self._perm_counter = 0
         self._perm_buf = None
         self.device_env = hasattr(envs, "step_device")
+        self._act_clip_v = None   # _act_clip's bound, read from the action space on first use
         # The switches below, read after construction too: plan() is their one reader (rollout_plan.plan_rollout)
         self.fuse_env_step = True   # device SynthBox env stepped inside K14 when possible (_env_fused)
         self.fuse_value_gae = True  # deferred bootstraps' value head inside the GAE scan (xpa_gae_scan_value)
@@ -278,6 +279,20 @@ class _OnPolicyAgent:
     def _obs_clip(self):
         return self.obsnorm_range if self.use_obsnorm else FLOAT_MAX
 
+    def _act_clip(self):
+        """The bound the samplers clip a Gaussian action to on its way into a device env's input: the action space's
+        (one symmetric bound for every dimension; _Box's default is 1).  A host env takes the raw actions and clips
+        them itself: its env input is scratch."""
+        if self.discrete or not self.device_env:
+            return 1.0
+        if self._act_clip_v is not None:
+            return self._act_clip_v
+        lo, hi = (np.asarray(getattr(self.action_space, k), np.float64).reshape(-1) for k in ("low", "high"))
+        assert hi.size and np.all(hi == hi[0]) and np.all(lo == -hi) and np.isfinite(hi[0]) and hi[0] > 0, \
+            "the device samplers clip to one symmetric bound: action_space low %r high %r" % (lo, hi)
+        self._act_clip_v = float(hi[0])
+        return self._act_clip_v
+
     def _normalize_into(self, x, out, to_buffer):
         mem = self.memory
         if to_buffer:
@@ -347,7 +362,7 @@ class _OnPolicyAgent:
             small_bufs=(all(b.dtype == torch.float32 and b.is_contiguous() for b in bufs)
                         and mem.closed.is_contiguous()),
             rows_ok=fm is not None and fm.rows_ok(obs_flat), small_update=L.small_update_ok(obs_flat, self.batch_size),
-            epoch_graphs=bool(L.graph_updates))
+            epoch_graphs=bool(L.graph_updates), dist=self.dist)
 
     def _env_fused(self, fm=None):
         """True when the device env's step runs inside the rollout's K14 launch (ops.rollout_policy_head_synthbox);
@@ -365,7 +380,7 @@ class _OnPolicyAgent:
         if plan.head == "K3":
             head, logstd, v = self._heads(plan.trunk, self._policy_in)
             ops.rollout_sample(self.dist, head.contiguous(), logstd, v.contiguous(), self.cursor, self.seed,
-                               mem.actions, logp_buf, mem.values, env_in, act_clip=1.0)
+                               mem.actions, logp_buf, mem.values, env_in, act_clip=self._act_clip())
             return
         if plan.head not in ("K14", "K14E", "K14F"):
             _no_form("the rollout's head", plan.head)
@@ -374,7 +389,7 @@ class _OnPolicyAgent:
             norm = (self.obs_mean, self.obs_var, self._obs_clip(), self.obs_norm, mem.observations,
                     self.n_steps * self.obs_dim, self.cursor)
         self._rollout_mlp().rollout_act(self._policy_in if raw_x is None else raw_x, self.dist, self.cursor, self.seed,
-                                        mem.actions, logp_buf, mem.values, env_in, act_clip=1.0, norm=norm,
+                                        mem.actions, logp_buf, mem.values, env_in, act_clip=self._act_clip(), norm=norm,
                                         env=self.envs if plan.head != "K14" else None,
                                         post=self._k14f_post(plan) if plan.head == "K14F" else None,
                                         trunk=plan.trunk, pair=plan.pair)
@@ -477,10 +492,11 @@ class _OnPolicyAgent:
         self._rms_c0 = None
 
     def _build_small_rollout(self):
-        """K32's argument block (xpa_small_rollout_cartpole) for a plan whose driver is K32; plan() rebuilds it when the
-        parameters are re-homed (the block holds their pointers)."""
+        """K32's argument block (xpa_small_rollout_cartpole / _pendulum) for a plan whose driver is K32; plan() rebuilds
+        it when the parameters are re-homed (the block holds their pointers)."""
         env, mem = self.envs, self.memory
-        (l0, l1, la, l2, lc), code, slope = self.learner.small_policy_layers()
+        (l0, l1, la, l2, lc), code, slope, self._k32_logstd = self.learner.small_policy_layers()
+        self._k32_entry, = self._plan.step_launches()
         N, T, D = self.n_envs, self.n_steps, self.obs_dim
         h0, h1, h2, k = l0.out_features, l1.out_features, l2.out_features, la.out_features
         a = _lib.XpaSmallRolloutArgs()
@@ -515,7 +531,13 @@ class _OnPolicyAgent:
 
     def _small_rollout_launch(self, steps):
         self._k32.steps = int(steps)
-        _lib.call(ops.lib().xpa_small_rollout_cartpole, ctypes.byref(self._k32), ops._stream(self.device))
+        if self._k32_entry == "xpa_small_rollout_cartpole":
+            _lib.call(ops.lib().xpa_small_rollout_cartpole, ctypes.byref(self._k32), ops._stream(self.device))
+        elif self._k32_entry == "xpa_small_rollout_pendulum":
+            _lib.call(ops.lib().xpa_small_rollout_pendulum, ctypes.byref(self._k32), ops._p(self._k32_logstd),
+                      self._act_clip(), ops._stream(self.device))
+        else:
+            _no_form("the one-launch rollout step", self._k32_entry)
 
     def _rollout_step_device(self):
         env = self.envs

@@ -37,3 +37,39 @@ XPA_API int xpa_cartpole_step(int64_t n_envs, const float *act_in, int64_t ld_ac
                        (hipStream_t)stream, n_envs, act_in, ld_act, e);
     return xpa_launch_status();
 }
+
+// K18P — Pendulum-v1 env step on device (the reference's configs/ppo|a2c/classic_control/Pendulum-v1.yaml).
+//
+// One thread owns one env, as K18: f64 state (th, thdot) in HBM, the observation (cos th, sin th, thdot) is its f32
+// image, the torque is the f32 env input the Gaussian rollout kernels write (already clipped; clamped again here), the
+// env never terminates and truncates at max_episode_steps, and the auto-reset draws th0 in [-pi, pi), thdot0 in
+// [-1, 1) from the counter hash (seed, env, episode, dim).
+#include "pendulum_body.h"
+
+namespace {
+__global__ __launch_bounds__(256) void pendulum_step_kernel(int64_t n_envs, const float *__restrict__ act_in,
+                                                            int64_t ld_act, XpaPendulumEnv e) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= n_envs) return;
+    pendulum::Local s = pendulum::load(e, n);
+    bool te, tr;
+    float o[3];
+    pendulum::step(e, n, act_in[n * ld_act], s, &te, &tr, o);
+    pendulum::store(e, n, s);
+}
+}  // namespace
+
+XPA_API int xpa_pendulum_step(int64_t n_envs, const float *act_in, int64_t ld_act, double *state, float *obs,
+                              int64_t ld_obs, float *final_obs, float *rew, uint8_t *term, uint8_t *trunc,
+                              int32_t *ep_step, uint32_t *ep_index, float *ep_score, float *ep_last_score,
+                              int32_t *ep_last_len, uint32_t seed, int32_t max_episode_steps, xpa_stream_t stream) {
+    if (n_envs <= 0 || !act_in || ld_act < 1 || !state || !obs || ld_obs < 3 || !final_obs || !rew || !term ||
+        !trunc || !ep_step || !ep_index || !ep_score || !ep_last_score || !ep_last_len || max_episode_steps <= 0)
+        return (int)hipErrorInvalidValue;
+    const XpaPendulumEnv e{state,    obs,           ld_obs,          final_obs, rew,
+                           term,     trunc,         (int *)ep_step,  ep_index,  ep_score,
+                           ep_last_score, (int *)ep_last_len, seed, (int)max_episode_steps};
+    hipLaunchKernelGGL(pendulum_step_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, n_envs, act_in, ld_act, e);
+    return xpa_launch_status();
+}

@@ -7,6 +7,7 @@
 // All per-step kernels read the buffer column from a device cursor so a whole env step can be
 // captured once in a hipGraph and replayed.
 #include "cartpole_body.h"
+#include "pendulum_body.h"
 
 namespace {
 
@@ -337,16 +338,14 @@ __global__ __launch_bounds__(256) void obs_normalize_kernel(const float *__restr
 // ---------------------------------------------------------------------------------------------
 // K3 sample + log-prob + store
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void gauss_sample_store(int64_t n, int A, int64_t T, const float *mu_row,
-                                                   const float *__restrict__ logstd, float v,
-                                                   const xpa_cursor_t *__restrict__ cur, uint32_t seed, float act_clip,
-                                                   float *__restrict__ buf_act, float *__restrict__ buf_logp,
-                                                   float *__restrict__ buf_val, float *__restrict__ env_in,
-                                                   int64_t ld_env) {
-    const int64_t t = cur->ptr;
-    const uint32_t step = cur->step;
+// Returns the clipped action of the last dimension (K32 steps its one-torque env with it: A = 1).
+__device__ __forceinline__ float gauss_sample_store_at(int64_t n, int A, int64_t T, int32_t t, uint32_t step,
+                                                       const float *mu_row, const float *__restrict__ logstd, float v,
+                                                       uint32_t seed, float act_clip, float *__restrict__ buf_act,
+                                                       float *__restrict__ buf_logp, float *__restrict__ buf_val,
+                                                       float *__restrict__ env_in, int64_t ld_env) {
     const int64_t cell = n * T + t;
-    float logp = 0.f;
+    float logp = 0.f, clipped = 0.f;
     for (int a = 0; a < A; ++a) {
         const uint32_t h1 = xpa_hash4(seed ^ kSaltAct, step, (uint32_t)n, (uint32_t)(2 * a));
         const uint32_t h2 = xpa_hash4(seed ^ kSaltAct, step, (uint32_t)n, (uint32_t)(2 * a + 1));
@@ -359,10 +358,22 @@ __device__ __forceinline__ void gauss_sample_store(int64_t n, int A, int64_t T, 
         const float diff = x - m;
         logp += -(diff * diff) / (2.0f * sc * sc) - logf(sc) - 0.91893853320467274178f;
         buf_act[cell * A + a] = x;
-        env_in[n * ld_env + a] = fminf(fmaxf(x, -act_clip), act_clip);
+        clipped = fminf(fmaxf(x, -act_clip), act_clip);
+        env_in[n * ld_env + a] = clipped;
     }
     buf_logp[cell] = logp;
     buf_val[cell] = v;
+    return clipped;
+}
+
+__device__ __forceinline__ void gauss_sample_store(int64_t n, int A, int64_t T, const float *mu_row,
+                                                   const float *__restrict__ logstd, float v,
+                                                   const xpa_cursor_t *__restrict__ cur, uint32_t seed, float act_clip,
+                                                   float *__restrict__ buf_act, float *__restrict__ buf_logp,
+                                                   float *__restrict__ buf_val, float *__restrict__ env_in,
+                                                   int64_t ld_env) {
+    gauss_sample_store_at(n, A, T, cur->ptr, cur->step, mu_row, logstd, v, seed, act_clip, buf_act, buf_logp, buf_val,
+                          env_in, ld_env);
 }
 
 // Returns the sampled action (K32 steps its env with it).
@@ -1107,24 +1118,71 @@ __device__ __forceinline__ float ro_act(float z, float slope) {
     return z;
 }
 
-template <int ACT, int H0>
-__global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaSmallRolloutArgs a) {
+// The env / head pair of a K32 instantiation: the observation width D, the output units at most KO (the head's k
+// + the value), the env's argument block, register state and step, and the sampler with what it takes beyond
+// XpaSmallRolloutArgs (Head).  act_step: K3's sample + stores at (t, step) from the output layers' z[0 .. k] (z[k] the
+// value), then the env's step with the sampled action; returns the reward.
+struct RoCartPoleCat {
+    static constexpr int D = 4, KO = 3;
+    using Env = XpaCartPoleEnv;
+    using Local = cartpole::Local;
+    struct Head {};
+    static __device__ __forceinline__ Env env(const XpaSmallRolloutArgs &a) {
+        return Env{a.env_state,   a.env_obs,   a.ld_obs,     a.final_obs,  a.env_rew,
+                   a.env_term,    a.env_trunc, a.ep_step,    a.ep_index,   a.ep_score,
+                   a.ep_last_score, a.ep_last_len, a.env_seed, a.max_episode_steps,
+                   cartpole::kThetaThreshold};
+    }
+    static __device__ __forceinline__ Local load(const Env &e, int n) { return cartpole::load(e, n); }
+    static __device__ __forceinline__ void store(const Env &e, int n, const Local &s) { cartpole::store(e, n, s); }
+    static __device__ __forceinline__ float act_step(const XpaSmallRolloutArgs &a, const Head &, const Env &e, int n,
+                                                     int K, int T, int32_t t, uint32_t step, const float *z, Local &es,
+                                                     bool *te, bool *tr, float *o) {
+        const int pick = cat_sample_store_at(n, K, T, t, step, z, z[K], a.seed, a.buf_act, a.buf_logp, a.buf_val,
+                                             a.act_in, a.ld_act);
+        return cartpole::step(e, n, pick, es, te, tr, o);
+    }
+};
+
+struct RoPendulumGauss {
+    static constexpr int D = 3, KO = 2;
+    using Env = XpaPendulumEnv;
+    using Local = pendulum::Local;
+    struct Head {
+        const float *logstd;
+        float act_clip;
+    };
+    static __device__ __forceinline__ Env env(const XpaSmallRolloutArgs &a) {
+        return Env{a.env_state, a.env_obs,  a.ld_obs,   a.final_obs,     a.env_rew,     a.env_term,  a.env_trunc,
+                   a.ep_step,   a.ep_index, a.ep_score, a.ep_last_score, a.ep_last_len, a.env_seed,
+                   a.max_episode_steps};
+    }
+    static __device__ __forceinline__ Local load(const Env &e, int n) { return pendulum::load(e, n); }
+    static __device__ __forceinline__ void store(const Env &e, int n, const Local &s) { pendulum::store(e, n, s); }
+    static __device__ __forceinline__ float act_step(const XpaSmallRolloutArgs &a, const Head &hd, const Env &e, int n,
+                                                     int K, int T, int32_t t, uint32_t step, const float *z, Local &es,
+                                                     bool *te, bool *tr, float *o) {
+        const float u = gauss_sample_store_at(n, K, T, t, step, z, hd.logstd, z[K], a.seed, hd.act_clip, a.buf_act,
+                                              a.buf_logp, a.buf_val, a.act_in, a.ld_act);
+        return pendulum::step(e, n, u, es, te, tr, o);  // K == 1: the one torque
+    }
+};
+
+template <class E, int ACT, int H0>
+__global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRolloutArgs a, typename E::Head hd) {
     extern __shared__ float lds[];
     __shared__ double s_sum[kRoThreads], s_sq[kRoThreads];
     __shared__ double s_red[kRoThreads / 64];
     __shared__ float s_mean[4], s_var[4];
-    __shared__ float s_obs[256 * 4];  // the raw observations of the step
+    __shared__ float s_obs[256 * E::D];  // the raw observations of the step
     __shared__ float s_rstd;
-    constexpr int D = 4;  // CartPole
+    constexpr int D = E::D, KO = E::KO;
     const int tid = threadIdx.x;
     const int N = a.n_envs, H1 = a.h1, H2 = a.h2, K = a.k, K1 = a.k + 1, U = a.h1 + a.h2;
     const int T = a.horizon;
     const RoLayout L = ro_layout(N, D, H0, H1, H2, K);
     float *sy = lds + L.sy, *sz = lds + L.sz, *sbo = lds + L.sbo;
-    const XpaCartPoleEnv env{a.env_state,   a.env_obs,   a.ld_obs,     a.final_obs,  a.env_rew,
-                             a.env_term,    a.env_trunc, a.ep_step,    a.ep_index,   a.ep_score,
-                             a.ep_last_score, a.ep_last_len, a.env_seed, a.max_episode_steps,
-                             cartpole::kThetaThreshold};
+    const typename E::Env env = E::env(a);
     if (tid < K1) sbo[tid] = tid < K ? a.ba[tid] : a.bc[0];
     // The forward on v_mfma_f32_16x16x4_f32: [16-row tile of envs] x [actor | critic hidden units], K = h0.  Wave w
     // owns the unit tiles w and w + 4 (16 units each) with their weight rows in VGPRs (B operand, loaded once per
@@ -1140,10 +1198,10 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
         const int k = 4 * kk + lq;
-        w0k[kk] = make_float4(a.W0[k * D], a.W0[k * D + 1], a.W0[k * D + 2], a.W0[k * D + 3]);
+        w0k[kk] = make_float4(a.W0[k * D], a.W0[k * D + 1], a.W0[k * D + 2], D > 3 ? a.W0[k * D + D - 1] : 0.f);
         b0k[kk] = a.b0[k];
     }
-    float bw[2][KK], b12[2], wo[2][3];
+    float bw[2][KK], b12[2], wo[2][KO];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int tile = wave + 4 * j;
@@ -1155,19 +1213,19 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
         for (int kk = 0; kk < KK; ++kk) bw[j][kk] = tok ? wr[4 * kk + lq] : 0.f;
         b12[j] = tok ? (actor ? a.b1[u] : a.b2[u - H1]) : 0.f;
 #pragma unroll
-        for (int o = 0; o < 3; ++o)
+        for (int o = 0; o < KO; ++o)
             wo[j][o] = !tok || o >= K1 ? 0.f : (o < K ? (actor ? a.Wa[o * H1 + u] : 0.f) : (actor ? 0.f : a.Wc[u - H1]));
     }
 
-    // state that lives across the steps of the launch: each env's CartPole state and running return (thread n),
+    // state that lives across the steps of the launch: each env's state and running return (thread n),
     // the raw observations and obs statistics (LDS), the obs count (every thread), the return statistics (thread 0)
-    cartpole::Local es{};
+    typename E::Local es{};
     float R = 0.f;
     if (tid < N) {
-        es = cartpole::load(env, tid);
+        es = E::load(env, tid);
         R = a.returns[tid];
 #pragma unroll
-        for (int d = 0; d < 4; ++d) s_obs[tid * 4 + d] = a.env_obs[tid * a.ld_obs + d];
+        for (int d = 0; d < D; ++d) s_obs[tid * D + d] = a.env_obs[tid * a.ld_obs + d];
     }
     if (tid < D) {
         s_mean[tid] = a.obs_mean[tid];
@@ -1195,7 +1253,8 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
     } while (0)
     __syncthreads();
     if (a.stamps && tid == 0) st_prev = st_t0 = (int64_t)__builtin_amdgcn_s_memtime();
-    constexpr int kGroups = kRoThreads / D;  // rms_partials_kernel<., 256>'s row groups at dim 4
+    // rms_partials_kernel<., 256>'s row groups at dim D (64; at dim 3, 85: thread 255 belongs to no group)
+    constexpr int kGroups = kRoThreads / D;
     for (int s = 0; s < a.steps; ++s) {
         const bool last = t == T - 1;
         // (a) obs_rms.update(obs): xpa_rms_update with one partial block
@@ -1208,7 +1267,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
 #pragma clang fp contract(off)
                     const float sh = s_mean[tid];
                     for (int r = 0; r < N; ++r) {
-                        const double v = (double)s_obs[r * 4 + tid] - (double)sh;
+                        const double v = (double)s_obs[r * D + tid] - (double)sh;
                         const double vv = v * v;
                         ts = ts + v;
                         tq = tq + vv;
@@ -1218,11 +1277,12 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
                 const int c = tid % D, gsub = tid / D;
                 double sm = 0.0, q = 0.0;
                 const float sh = s_mean[c];
-                for (int r = gsub; r < N; r += kGroups) {
-                    const double v = (double)s_obs[r * 4 + c] - (double)sh;
-                    sm += v;
-                    q += v * v;
-                }
+                if (gsub < kGroups)
+                    for (int r = gsub; r < N; r += kGroups) {
+                        const double v = (double)s_obs[r * D + c] - (double)sh;
+                        sm += v;
+                        q += v * v;
+                    }
                 s_sum[tid] = sm;
                 s_sq[tid] = q;
                 __syncthreads();
@@ -1258,7 +1318,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
         XPA_RO_STAMP(0);
         // (b) normalise into the policy input and buffer column t (obs_normalize_kernel's arithmetic)
         for (int e = tid; e < N * D; e += kRoThreads) {
-            const int r = e >> 2, d = e & 3;
+            const int r = e / D, d = e % D;
             const float y = obs_norm1(s_obs[e], s_mean[d], s_var[d], a.obs_clip);
             sy[e] = y;
             a.obs_norm[r * a.ld_norm + d] = y;
@@ -1269,7 +1329,11 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
         // (c)-(e) the forward, one 16-row tile of envs at a time
         for (int r0 = 0; r0 < N; r0 += 16) {
             const int ra = r0 + li < N ? r0 + li : N - 1;   // this lane's A row (rows past N: results unused)
-            const float4 y = *reinterpret_cast<const float4 *>(sy + ra * D);
+            float4 y;
+            if (D == 4)
+                y = *reinterpret_cast<const float4 *>(sy + ra * D);
+            else
+                y = make_float4(sy[ra * D], sy[ra * D + 1], sy[ra * D + 2], 0.f);
             float av[KK];
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
@@ -1277,7 +1341,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
                 z = fmaf(w0k[kk].x, y.x, z);
                 z = fmaf(w0k[kk].y, y.y, z);
                 z = fmaf(w0k[kk].z, y.z, z);
-                z = fmaf(w0k[kk].w, y.w, z);
+                if (D == 4) z = fmaf(w0k[kk].w, y.w, z);
                 av[kk] = ro_act<ACT>(z, a.slope);
             }
             ro_f32x4 acc[2];
@@ -1288,11 +1352,11 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bw[j][kk], acc[j], 0, 0, 0);
             // D element r of lane (q, i): row r0 + 4 q + r, unit 16 tile + i
-            float part[4][3];
+            float part[4][KO];
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int o = 0; o < 3; ++o) {
+                for (int o = 0; o < KO; ++o) {
                     float pv = 0.f;
 #pragma unroll
                     for (int j = 0; j < 2; ++j) pv = fmaf(wo[j][o], ro_act<ACT>(acc[j][r] + b12[j], a.slope), pv);
@@ -1311,22 +1375,20 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
         // (f) sample + store, env step, post step (one thread per env)
         double cnt = 0.0, sum = 0.0, sumsq = 0.0;
         if (tid < N) {
-            float z[3];
+            float z[KO];
             for (int o = 0; o < K1; ++o) {
                 float v = sbo[o];
                 for (int w = 0; w < 4; ++w) v += sz[(w * N + tid) * K1 + o];
                 z[o] = v;
             }
-            const int pick = cat_sample_store_at(tid, K, T, t, step, z, z[K], a.seed, a.buf_act, a.buf_logp,
-                                                 a.buf_val, a.act_in, a.ld_act);
             bool te, tr;
-            float o[4];
-            const float r = cartpole::step(env, tid, pick, es, &te, &tr, o);
+            float o[D];
+            const float r = E::act_step(a, hd, env, tid, K, T, t, step, z, es, &te, &tr, o);
 #pragma unroll
-            for (int d = 0; d < 4; ++d) s_obs[tid * 4 + d] = o[d];
+            for (int d = 0; d < D; ++d) s_obs[tid * D + d] = o[d];
             R = post_env<true, true>(tid, N, T, t, last, s_rstd, r, te, tr, 0.f, R, a.buf_rew, a.buf_term,
                                      a.buf_closed, a.buf_boot, a.gamma, a.mask_returns, a.use_rewnorm, a.rew_range,
-                                     0, a.final_obs, 4, D, a.slot_obs, a.slot_t, a.n_slots, a.overflow, s_mean, s_var,
+                                     0, a.final_obs, D, D, a.slot_obs, a.slot_t, a.n_slots, a.overflow, s_mean, s_var,
                                      a.obs_clip, a.boot_norm, a.ld_boot, cnt, sum, sumsq,
                                      a.slot_reset_obs ? a.env_obs : nullptr, a.ld_obs);
             a.returns[tid] = R;
@@ -1364,7 +1426,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_cartpole_kernel(XpaS
         for (int i = 0; i < 8; ++i) a.stamps[i] = st_acc[i];
         a.stamps[8] = (int64_t)__builtin_amdgcn_s_memtime() - st_t0;
     }
-    if (tid < N) cartpole::store(env, tid, es);
+    if (tid < N) E::store(env, tid, es);
     if (tid == 0) {
         a.cursor->ptr = t;
         a.cursor->step = step;
@@ -1835,11 +1897,14 @@ XPA_API int64_t xpa_small_rollout_lds_floats(int64_t n_envs, int64_t d_in, int64
     return ro_layout((int)n_envs, (int)d_in, (int)h0, (int)h1, (int)h2, (int)k).total;
 }
 
-XPA_API int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *a, xpa_stream_t stream) {
-    if (!a || a->n_envs <= 0 || a->n_envs > 256 || a->horizon <= 0 || a->steps <= 0 || a->d_in != 4 ||
-        (a->h0 != 32 && a->h0 != 64) || (a->h1 != 32 && a->h1 != 64) || (a->h2 != 32 && a->h2 != 64) || a->k != 2 ||
+namespace {
+// The checks and the launch shared by K32's entry points; E: the instantiation's env / head pair, k its head width.
+template <class E>
+int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head hd, xpa_stream_t stream) {
+    if (!a || a->n_envs <= 0 || a->n_envs > 256 || a->horizon <= 0 || a->steps <= 0 || a->d_in != E::D ||
+        (a->h0 != 32 && a->h0 != 64) || (a->h1 != 32 && a->h1 != 64) || (a->h2 != 32 && a->h2 != 64) || a->k != k ||
         a->act_code < 0 || a->act_code > 2 || a->n_slots < 1 || a->n_slots > a->horizon || a->max_episode_steps <= 0 ||
-        a->ld_norm < a->d_in || a->ld_obs < 4 || a->ld_act < 2 || a->ld_boot < a->d_in)
+        a->ld_norm < a->d_in || a->ld_obs < E::D || a->ld_act < k || a->ld_boot < a->d_in)
         return (int)hipErrorInvalidValue;
     if (!a->W0 || !a->b0 || !a->W1 || !a->b1 || !a->W2 || !a->b2 || !a->Wa || !a->ba || !a->Wc || !a->bc ||
         !a->obs_mean || !a->obs_var || !a->obs_count || !a->obs_norm || !a->buf_obs || !a->buf_act || !a->buf_logp ||
@@ -1853,7 +1918,7 @@ XPA_API int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *a, xpa_stream_
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
 #define XPA_RO_LAUNCH(ACT, H0) \
-    hipLaunchKernelGGL((small_rollout_cartpole_kernel<ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a)
+    hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a, hd)
     if (a->h0 == 64) {
         if (a->act_code == 0) XPA_RO_LAUNCH(0, 64);
         else if (a->act_code == 1) XPA_RO_LAUNCH(1, 64);
@@ -1865,4 +1930,15 @@ XPA_API int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *a, xpa_stream_
     }
 #undef XPA_RO_LAUNCH
     return xpa_launch_status();
+}
+}  // namespace
+
+XPA_API int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *a, xpa_stream_t stream) {
+    return small_rollout_launch<RoCartPoleCat>(a, 2, RoCartPoleCat::Head{}, stream);
+}
+
+XPA_API int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *a, const float *logstd, float act_clip,
+                                       xpa_stream_t stream) {
+    if (!logstd || !(act_clip > 0.f)) return (int)hipErrorInvalidValue;
+    return small_rollout_launch<RoPendulumGauss>(a, 1, RoPendulumGauss::Head{logstd, act_clip}, stream);
 }

@@ -78,12 +78,25 @@ __device__ __forceinline__ int sm_row(int r) { return (r & 3) + 8 * (r >> 2) + 4
         if (a.stamps && t == 0 && blockIdx.x == 0) a.stamps[i_] = (int64_t)__builtin_amdgcn_s_memtime(); \
     } while (0)
 
-template <int ACT, int ALGO>
-__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmallMlpArgs a) {
+constexpr float kSmLogSqrt2Pi = 0.91893853320467274178f;          // log(sqrt(2*pi))
+constexpr float kSmHalfLog2PiPlusHalf = 1.41893853320467274178f;  // 0.5 + 0.5*log(2*pi)
+constexpr int kSmActMax = 16;
+
+// What the Gaussian head takes beyond XpaSmallMlpArgs (both NULL for a Categorical head).
+struct SmGauss {
+    const float *logstd;   // [A]
+    float *g_logstd;       // [A], a view of the flat gradient a.grad
+};
+
+// GAUSS: a.k is the action dimension A, Wa / ba the mu layer, actions [n_rows, A]; the loss stage is
+// policy_loss_gauss_kernel's per-row arithmetic (loss.hip) and d logstd joins the gradient.
+template <int ACT, int ALGO, bool GAUSS>
+__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmallMlpArgs a, SmGauss hd) {
     __shared__ __attribute__((aligned(16))) float lds[kSmLds];
     __shared__ double s_red[kSmWaves * 6];
     __shared__ float s_stat[4];
     __shared__ float s_coef, s_step, s_inv;
+    __shared__ float s_gvar[kSmActMax], s_glsc[kSmActMax];   // GAUSS: std^2 and log(std) per action dimension
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, li = lane & 31;
     // Split form (G = gridDim.x > 1): workgroup g takes minibatch rows [32 g, 32 g + 32) and writes its partial
     // weight / bias gradients (sums over its rows) into grad_part[g] at the flat buffer's offsets and its loss sums
@@ -120,6 +133,11 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     XPA_SM_STAMP(0);
     // ---- staging: two global round trips in all — the row indices with every weight load, then the rows ----
     // (five dependent load / store rounds took ~21 k cycles before)
+    if (GAUSS && t < K) {
+        const float sc = expf(hd.logstd[t]);   // std = logstd.exp(); Normal.log_prob uses scale.log()
+        s_glsc[t] = logf(sc);
+        s_gvar[t] = sc * sc;
+    }
     const int n0 = H0 * D, na = K * H1, nm = n0 + na + H2 + H0 + H1 + H2 + K + 1;   // W0 | Wa | Wc | biases
     const int nw1 = H0 * H1, nw2 = H0 * H2;
     const bool fast = nm <= 2 * kSmThreads && nw1 <= 8 * kSmThreads && nw2 <= 8 * kSmThreads && BP <= kSmThreads &&
@@ -376,14 +394,54 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     const float mean_a = s_stat[0], inv_a = s_stat[1];
     for (int b = t; b < B; b += kSmThreads) {
         const int64_t row = idx[b];
-        if (!(row >= 0 && row < a.n_rows)) continue;   // out-of-range index: zero gradient (dlT / dvT stay 0)
-        const float *zr = logit + b * KP;
+        if (!(row >= 0 && row < a.n_rows)) {   // out-of-range index: zero gradient (dlT / dvT stay 0)
+            // GAUSS: the row hands back the ent_coef / B that d logstd's reduction subtracts for every row (K2)
+            if (GAUSS)
+                for (int k = 0; k < K; ++k) logit[b * KP + k] = a.ent_coef * inv_b;
+            continue;
+        }
+        float *zr = logit + b * KP;
         const float A_n = (rowf[2 * BP + b] - mean_a) * inv_a;
         const float vb = vrow[b];
         const float diffv = vb - rowf[3 * BP + b];
         sqe += diffv * diffv;
         vsum += vb;
         dvT[b] = a.vf_coef * 2.0f * diffv * inv_b;
+        if (GAUSS) {
+            // K2's Gaussian arithmetic (policy_loss_gauss_kernel): zr[k] = mu_k becomes x_k - mu_k, then the row's
+            // d logstd_k term (reduced over the rows with the bias gradients below)
+            float logp = 0.f, ent_g = 0.f;
+            for (int k = 0; k < K; ++k) {
+                const float diff = a.actions[row * K + k] - zr[k];
+                zr[k] = diff;
+                logp += -(diff * diff) / (2.0f * s_gvar[k]) - s_glsc[k] - kSmLogSqrt2Pi;
+                ent_g += kSmHalfLog2PiPlusHalf + s_glsc[k];
+            }
+            ent += ent_g;
+            float dlogp;
+            if (ALGO == XPA_ALGO_PPO) {
+                const float ratio = expf(logp - rowf[BP + b]);
+                const float lo = 1.0f - a.clip_range, hi = 1.0f + a.clip_range;
+                const float cr = fminf(fmaxf(ratio, lo), hi);
+                const float s1 = cr * A_n, s2 = A_n * ratio;
+                surr += fminf(s1, s2);
+                const bool inr = (ratio >= lo) && (ratio <= hi);
+                const float g1 = inr ? A_n : 0.f;
+                const float w1 = (s1 < s2) ? 1.f : ((s1 == s2) ? 0.5f : 0.f);
+                const float w2 = (s2 < s1) ? 1.f : ((s1 == s2) ? 0.5f : 0.f);
+                dlogp = -inv_b * (w1 * g1 + w2 * A_n) * ratio;
+                clipc += ((ratio < lo) || (ratio > hi)) ? 1.f : 0.f;
+            } else {
+                surr += A_n * logp;
+                dlogp = -A_n * inv_b;
+            }
+            for (int k = 0; k < K; ++k) {
+                const float diff = zr[k];
+                dlT[k * S + b] = dlogp * diff / s_gvar[k];
+                zr[k] = dlogp * (diff * diff / s_gvar[k] - 1.0f);
+            }
+            continue;
+        }
         float m = zr[0];
         for (int k = 1; k < K; ++k) m = fmaxf(m, zr[k]);
         float se = 0.f;
@@ -575,6 +633,24 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
             }
             const float s = (s0 + s1) + (s2 + s3);
             *dst = s;
+            sq += (double)s * s;
+        }
+        // GAUSS: d logstd_k = the rows' terms (left in the logit image by the loss stage) summed in a fixed order,
+        // minus ent_coef (K2's finalize; the split form's workgroup 0 takes it) — the last K threads, one each
+        if (GAUSS && t >= kSmThreads - K) {
+            const int k = kSmThreads - 1 - t;
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            int b = 0;
+            for (; b + 4 <= B; b += 4) {
+                s0 += logit[b * KP + k];
+                s1 += logit[(b + 1) * KP + k];
+                s2 += logit[(b + 2) * KP + k];
+                s3 += logit[(b + 3) * KP + k];
+            }
+            float s = (s0 + s1) + (s2 + s3);
+            for (; b < B; ++b) s += logit[b * KP + k];
+            if (gi == 0) s -= a.ent_coef;
+            gp(hd.g_logstd)[k] = s;
             sq += (double)s * s;
         }
     }
@@ -827,11 +903,15 @@ XPA_API int64_t xpa_small_mlp_lds_floats(int64_t batch, int64_t d_in, int64_t h0
            KP + 4 + 4 * BP + BP * KP + BP;
 }
 
-XPA_API int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t stream) {
+namespace {
+// The checks and launches shared by K30's entry points; GAUSS: hd holds the Gaussian head's logstd and its gradient.
+template <bool GAUSS>
+int small_mlp_launch(const XpaSmallMlpArgs *args, SmGauss hd, xpa_stream_t stream) {
     if (!args) return (int)hipErrorInvalidValue;
     const XpaSmallMlpArgs &a = *args;
     if (a.batch < 1 || a.d_in < 1 || a.d_in > 32 || a.h0 < 32 || a.h1 < 32 || a.h2 < 32 || a.h0 % 32 || a.h1 % 32 ||
-        a.h2 % 32 || a.h0 > 256 || a.h1 > 256 || a.h2 > 256 || a.k < 2 || a.k > 16 || a.act_code < 0 || a.act_code > 2 ||
+        a.h2 % 32 || a.h0 > 256 || a.h1 > 256 || a.h2 > 256 || a.k < (GAUSS ? 1 : 2) || a.k > kSmActMax ||
+        a.act_code < 0 || a.act_code > 2 ||
         (a.algo != XPA_ALGO_PPO && a.algo != XPA_ALGO_A2C) || (a.algo == XPA_ALGO_PPO && !a.old_logp) || !a.obs ||
         !a.idx || !a.actions || !a.adv || !a.ret || !a.param || !a.grad || !a.exp_avg || !a.exp_avg_sq || !a.sched ||
         !a.cursor || a.n_sched < 1 || !a.scalars || a.n < 1 || !a.W0 || !a.b0 || !a.W1 || !a.b1 || !a.W2 || !a.b2 ||
@@ -845,7 +925,8 @@ XPA_API int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t strea
     if (xpa_small_mlp_lds_floats(G > 1 ? 32 : a.batch, a.d_in, a.h0, a.h1, a.h2, a.k) > kSmLds)
         return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-#define XPA_SM(A_, G_) hipLaunchKernelGGL((small_mlp_update_kernel<A_, G_>), dim3(G), dim3(kSmThreads), 0, s, a)
+#define XPA_SM(A_, G_) \
+    hipLaunchKernelGGL((small_mlp_update_kernel<A_, G_, GAUSS>), dim3(G), dim3(kSmThreads), 0, s, a, hd)
     if (a.algo == XPA_ALGO_PPO) {
         if (a.act_code == 0) XPA_SM(0, XPA_ALGO_PPO);
         else if (a.act_code == 1) XPA_SM(1, XPA_ALGO_PPO);
@@ -863,4 +944,18 @@ XPA_API int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t strea
             hipLaunchKernelGGL((small_mlp_finalize_kernel<XPA_ALGO_A2C>), dim3(1), dim3(kSmThreads), 0, s, a);
     }
     return xpa_launch_status();
+}
+}  // namespace
+
+XPA_API int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t stream) {
+    return small_mlp_launch<false>(args, SmGauss{nullptr, nullptr}, stream);
+}
+
+XPA_API int xpa_small_mlp_update_gauss(const XpaSmallMlpArgs *args, const float *logstd, float *g_logstd,
+                                       xpa_stream_t stream) {
+    // g_logstd lies inside the flat gradient: clip and Adam cover it, and the split form's partials mirror its offset
+    if (!args || !logstd || !g_logstd || !args->grad || g_logstd < args->grad ||
+        g_logstd + args->k > args->grad + args->n)
+        return (int)hipErrorInvalidValue;
+    return small_mlp_launch<true>(args, SmGauss{logstd, g_logstd}, stream);
 }

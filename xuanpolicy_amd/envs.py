@@ -381,3 +381,113 @@ class CartPoleVecEnv:
 
     def close(self):
         pass
+
+
+# ---- Pendulum-v1 (the reference's configs/ppo|a2c/classic_control/Pendulum-v1.yaml) ------------------------------
+SALT_PENDULUM = 0x9E2D0105
+
+
+def pendulum_reset_states(seed, env_ids, episodes):
+    """[n, 2] f64 (th0, thdot0) = ((2 u - 1) pi, 2 u - 1) from the counter hash (f32-exact uniforms, then f64), as
+    K18P draws them."""
+    e = np.asarray(env_ids, np.uint32)[:, None]
+    ep = np.asarray(episodes, np.uint32)[:, None]
+    d = np.arange(2, dtype=np.uint32)[None, :]
+    c = 2.0 * _u01(_hash4(seed ^ SALT_PENDULUM, e, ep, d)).astype(np.float64) - 1.0
+    c[:, 0] = c[:, 0] * np.pi
+    return c
+
+
+class PendulumVecEnv:
+    """n_envs Pendulum-v1 envs resident on one GPU (K18P xpa_pendulum_step, csrc/classic.hip): the equations of the
+    header's K18P comment with TimeLimit(200), f64 state (th, thdot), f32 observations (cos th, sin th, thdot), one
+    torque in [-2, 2] read from the clipped env input the Gaussian rollout kernels write.  Same interface as
+    CartPoleVecEnv.  CPU checker: tests/_pendulum_ref.py."""
+    kind = "pendulum"   # rollout_plan: K32 steps this env inside the fused rollout step
+    MAX_SPEED, MAX_TORQUE = 8.0, 2.0
+
+    def __init__(self, n_envs, seed=1, max_episode_steps=200, device=None, shard=0):
+        self.num_envs, self.seed, self.max_episode_steps = int(n_envs), int(seed), int(max_episode_steps)
+        self.max_episode_length = self.max_episode_steps
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.shard = int(shard)
+        self.noise_seed = (self.seed ^ ((0x9E3779B9 * self.shard) & 0xFFFFFFFF)) & 0xFFFFFFFF
+        self.observation_space = _Box((3,))
+        self.observation_space.high = np.array([1.0, 1.0, self.MAX_SPEED], np.float32)
+        self.observation_space.low = -self.observation_space.high
+        self.action_space = _Box((1,))
+        self.action_space.high = np.full(1, self.MAX_TORQUE, np.float32)
+        self.action_space.low = -self.action_space.high
+        dev, N = self.device, self.num_envs
+        self.state = torch.zeros((N, 2), dtype=torch.float64, device=dev)
+        self._obs = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+        self._act = torch.zeros((N, 1), dtype=torch.float32, device=dev)
+        self.final_obs = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+        self.rew = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.term = torch.zeros((N,), dtype=torch.uint8, device=dev)
+        self.trunc = torch.zeros((N,), dtype=torch.uint8, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.ep_step, self.ep_index, self.ep_last_len = (torch.zeros((N,), **i32) for _ in range(3))
+        self.ep_score = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.ep_last_score = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.reset()
+
+    @property
+    def obs(self):
+        return self._obs
+
+    @property
+    def act_in(self):
+        """Env action input [N, 1]: the clipped torque (K3 / K14 / K32 write it)."""
+        return self._act
+
+    @property
+    def buf_obs(self):
+        return self._obs
+
+    def reset(self):
+        self.resets = getattr(self, "resets", 0) + 1   # agents re-arm a folded obs-RMS merge (K8R)
+        s0 = pendulum_reset_states(self.noise_seed, np.arange(self.num_envs), np.zeros(self.num_envs))
+        self.state.copy_(torch.as_tensor(s0, device=self.device))
+        o0 = np.stack([np.cos(s0[:, 0]), np.sin(s0[:, 0]), s0[:, 1]], axis=1).astype(np.float32)
+        self._obs.copy_(torch.as_tensor(o0, device=self.device))
+        for t in (self.ep_step, self.ep_index, self.ep_score, self.ep_last_score, self.ep_last_len, self.rew,
+                  self.term, self.trunc, self._act):
+            t.zero_()
+        return self._obs.clone(), [{} for _ in range(self.num_envs)]
+
+    def fusable_with_policy_step(self, dist):
+        return False
+
+    def step_device(self):
+        _lib.call(ops.lib().xpa_pendulum_step, self.num_envs, ops._p(self._act), self._act.stride(0),
+                  ops._p(self.state), ops._p(self._obs), self._obs.stride(0), ops._p(self.final_obs), ops._p(self.rew),
+                  ops._p(self.term), ops._p(self.trunc), ops._p(self.ep_step), ops._p(self.ep_index),
+                  ops._p(self.ep_score), ops._p(self.ep_last_score), ops._p(self.ep_last_len), self.noise_seed,
+                  self.max_episode_steps, ops._stream(self.device))
+
+    def step(self, actions):
+        """VecEnv contract (gym_vec_env.py:201-212): host copies of (obs, rew, term, trunc, infos)."""
+        a = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions,
+                            device=self.device)
+        self._act.copy_(torch.clamp(a.float().reshape(self.num_envs, 1), -self.MAX_TORQUE, self.MAX_TORQUE))
+        self.step_device()
+        obs = self.final_obs.cpu().numpy()
+        rew = self.rew.cpu().numpy()
+        term = self.term.cpu().numpy().astype(bool)
+        trunc = self.trunc.cpu().numpy().astype(bool)
+        nxt = self._obs.cpu().numpy()
+        lens, scores = self.ep_step.cpu().numpy(), self.ep_score.cpu().numpy()
+        last_len, last_score = self.ep_last_len.cpu().numpy(), self.ep_last_score.cpu().numpy()
+        infos = []
+        for i in range(self.num_envs):
+            done = term[i] or trunc[i]
+            info = {"episode_step": int(last_len[i] if done else lens[i]),
+                    "episode_score": float(last_score[i] if done else scores[i])}
+            if done:
+                info["reset_obs"] = nxt[i].copy()
+            infos.append(info)
+        return obs, rew, term, trunc, infos
+
+    def close(self):
+        pass

@@ -302,10 +302,11 @@ class _FusedPolicyGradient(Learner):
 
     # ---- K30: the whole small-MLP update in one launch (C1) ----------------------------------------------------
     def small_policy_layers(self):
-        """((l0, l1, la, l2, lc), code, slope) when the policy is a Categorical actor-critic of one representation
-        layer and one hidden layer per head, all with the same activation — the shape K30 (update) and K32 (rollout
-        step) take — else None."""
-        if self.dist != "categorical":
+        """((l0, l1, la, l2, lc), code, slope, logstd) when the policy is a Categorical or Gaussian actor-critic of one
+        representation layer and one hidden layer per head, all with the same activation — the shape K30 (update) and
+        K32 (rollout step) take — else None.  la: the logits layer, or the Gaussian's mu layer; logstd: the Gaussian's
+        parameter (None for a Categorical policy)."""
+        if self.dist not in ("categorical", "gaussian"):
             return None
         fm = self._fused_mlp()
         if fm is None or len(fm.rep) != 1 or len(fm.actor) != 2 or len(fm.critic) != 2:
@@ -314,24 +315,33 @@ class _FusedPolicyGradient(Learner):
                                                                               fm.critic[0], fm.critic[1])
         if not (c0 == c1 == c2 and s0 == s1 == s2 and ca == 0 and cc == 0 and lc.out_features == 1):
             return None
-        return (l0, l1, la, l2, lc), c0, s0
+        if (fm.logstd is None) != (self.dist == "categorical"):
+            return None
+        return (l0, l1, la, l2, lc), c0, s0, fm.logstd
 
     def small_update_ok(self, obs_flat, batch):
-        """True when a minibatch of `batch` rows of obs_flat [n_rows, d] can take K30 (xpa_small_mlp_update): the
-        small_policy_layers shape, flat parameters with the fused Adam, no data-parallel gradient sync, and the LDS
-        budget."""
+        """True when a minibatch of `batch` rows of obs_flat [n_rows, d] can take K30 (xpa_small_mlp_update, or
+        xpa_small_mlp_update_gauss for a Gaussian head): the small_policy_layers shape, flat parameters with the fused
+        Adam (a Gaussian's logstd gradient among them), no data-parallel gradient sync, and the LDS budget."""
         if not self.small_updates or self.grad_sync is not None:
             return False
         fused = self.fused_opt
         layers = self.small_policy_layers()
         if layers is None or fused is None or fused.fs.numel % 4:
             return False
+        logstd = layers[3]
+        if logstd is not None:   # d logstd is written where clip + Adam read it: inside the flat gradient
+            g, flat = logstd.grad, fused.fs.flat
+            if g is None or not g.is_contiguous() or not \
+                    0 <= g.data_ptr() - flat.data_ptr() <= 4 * (flat.numel() - g.numel()):
+                return False
         if not (isinstance(obs_flat, torch.Tensor) and obs_flat.is_cuda and obs_flat.dim() == 2
                 and obs_flat.dtype == torch.float32 and obs_flat.stride(1) == 1):
             return False
-        (l0, l1, la, l2, lc), _, _ = layers
+        (l0, l1, la, l2, lc) = layers[0]
         h0, h1, h2, k = l0.out_features, l1.out_features, l2.out_features, la.out_features
-        if any(h % 32 or h > 256 for h in (h0, h1, h2)) or not 2 <= k <= 16 or l0.in_features != obs_flat.shape[1] \
+        if any(h % 32 or h > 256 for h in (h0, h1, h2)) or not (2 if logstd is None else 1) <= k <= 16 \
+                or l0.in_features != obs_flat.shape[1] \
                 or l0.in_features > 32:
             return False
         rows = 32 if self.small_split and 32 < batch <= 512 else batch   # per workgroup
@@ -383,7 +393,11 @@ class _FusedPolicyGradient(Learner):
                 ws[G] = (torch.zeros((G, fused.fs.numel), dtype=torch.float32, device=obs_flat.device),
                          torch.zeros((G, 8), dtype=torch.float64, device=obs_flat.device))
             a.grad_part, a.loss_part = ws[G][0].data_ptr(), ws[G][1].data_ptr()
-        _lib.call(ops.lib().xpa_small_mlp_update, ctypes.byref(a), ops._stream(obs_flat.device))
+        if fm.logstd is None:
+            _lib.call(ops.lib().xpa_small_mlp_update, ctypes.byref(a), ops._stream(obs_flat.device))
+        else:   # Gaussian head: la is the mu layer, act [n_rows, A]
+            _lib.call(ops.lib().xpa_small_mlp_update_gauss, ctypes.byref(a), fm.logstd.data_ptr(),
+                      fm.logstd.grad.data_ptr(), ops._stream(obs_flat.device))
         return out
 
     def small_update(self, obs_flat, idx, act, adv, ret, old_logp=None, use_advnorm=True):

@@ -47,7 +47,7 @@ class RolloutFacts(NamedTuple):
     global_advnorm: bool
     pending: bool             # host closures (buffer.finish_path) wait for the scan
     # the env
-    env: str                  # "synthbox" | "synthatari" | "cartpole" | "device" (another device env) | "host"
+    env: str                  # "synthbox" | "synthatari" | "cartpole" | "pendulum" | "device" (another one) | "host"
     env_fusable: bool         # env.fusable_with_policy_step(dist)
     obs_rows: bool            # env.obs is [N, D] with unit column stride
     # the policy and the learner
@@ -58,6 +58,7 @@ class RolloutFacts(NamedTuple):
     rows_ok: bool             # the update takes fused_mlp.Rows of the flat observations
     small_update: bool        # learner.small_update_ok (K30)
     epoch_graphs: bool        # learner.graph_updates
+    dist: str = "categorical"  # the head's distribution: "categorical" | "gaussian" (K32's instantiation)
 
 
 _RMS = {None: (), "standalone": ("xpa_rms_update",), "all-reduce": ("xpa_rms_partials", "xpa_rms_merge"),
@@ -71,6 +72,12 @@ _HEAD = {"K14F": ("xpa_rollout_step_synthbox",), "K14E": ("xpa_rollout_policy_he
          "K14": ("xpa_rollout_policy_head",), "K3": ("xpa_rollout_sample",)}
 _ENV = {"in-head": (), "synthbox": ("xpa_synthbox_step",), "synthatari": ("xpa_synthatari_step",),
         "cartpole": ("xpa_cartpole_step",), "device": (), "host": ()}
+# step_launches' env table: _ENV (whose keys test_rollout_plan_cpu's invariants enumerate over its env kinds) and the
+# device envs added since
+_ENV_STEP = dict(_ENV, pendulum=("xpa_pendulum_step",))
+# K32's instantiations: (env, the head's distribution) -> (entry point, d_in, head width)
+_K32 = {("cartpole", "categorical"): ("xpa_small_rollout_cartpole", 4, 2),
+        ("pendulum", "gaussian"): ("xpa_small_rollout_pendulum", 3, 1)}
 _VALUE_HEAD = {"K13": ("xpa_value_head",), "chain": ("xpa_value_head",), "cnn": (), "policy": ()}
 _POST = {"K14F": (), "K8-deferred": ("xpa_rollout_post_deferred_norm",), "K8": ("xpa_rollout_post",)}
 _CLOSE = {None: (), "raw-last": ("xpa_rollout_bootstrap_fixup",), "raw-mid-next": ()}
@@ -90,7 +97,7 @@ class RolloutPlan(NamedTuple):
     value_trunk: str   # the critic-only passes' trunk: "K13" | "chain" | "cnn" | "policy"
     pair: object       # "K40R" | "linear" | None
     head: str          # "K14F" | "K14E" | "K14" | "K3"
-    env: str           # "in-head" | "synthbox" | "synthatari" | "cartpole" | "device" | "host"
+    env: str           # "in-head" | "synthbox" | "synthatari" | "cartpole" | "pendulum" | "device" | "host"
     post: str          # "K14F" | "K8-deferred" | "K8"
     boot: str          # "slots" | "per-step" | "zero"
     mid: object        # A2C's mid-rollout bootstraps: None | "critic" | "next-column" | "slots-from-next"
@@ -110,12 +117,12 @@ class RolloutPlan(NamedTuple):
         """The library entry points of one steady device env step, in order (hipBLASLt / torch launches are not
         counted).  pending: the step after a reset, which runs the standalone obs_rms update whatever the form."""
         if self.driver == "K32":
-            return ["xpa_small_rollout_cartpole"]
+            return [entry for (env, _), (entry, _, _) in _K32.items() if env == self.env]
         out = list(_RMS["standalone"] if pending and self.rms in ("fold-K8", "fold-K14F") else _RMS[self.rms])
         out += _OBS[self.obs] + _TRUNK[self.trunk]
         if self.trunk != "K40T":
             out += _PAIR[self.pair]
-        out += _HEAD[self.head] + _ENV[self.env]
+        out += _HEAD[self.head] + _ENV_STEP[self.env]
         if self.post == "K8":
             one = (() if self.obs == "raw" else _OBS["K5N"]) + self._values()
             out += (() if self.boot == "zero" else one) + (one if self.mid == "critic" else ())
@@ -140,13 +147,14 @@ def plan_rollout(f):
     sh = None if f.raw_obs else f.shape
     device = f.env != "host"
     collective = f.sync_obs_rms is True and f.world > 1 and f.use_obsnorm
-    # K32: a CartPole device env with deferred bootstraps, no per-step collective, the small_policy_layers shape
-    k32 = (f.fused_rollout and f.cuda and f.env == "cartpole" and f.defer_boot and not f.raw_obs and not collective
-           and f.algo in ("ppo", "a2c") and f.obs_dim == 4 and f.small is not None and f.small_bufs)
+    # K32: a CartPole (Categorical, 2 actions) or Pendulum (Gaussian, 1 torque) device env with deferred bootstraps, no
+    # per-step collective, the small_policy_layers shape
+    k32 = (f.fused_rollout and f.cuda and (f.env, f.dist) in _K32 and f.defer_boot and not f.raw_obs and not collective
+           and f.algo in ("ppo", "a2c") and f.small is not None and f.small_bufs)
     if k32:
         d_in, h0, h1, h2, k, lds = f.small
-        k32 = (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and k == 2 and d_in == f.obs_dim
-               and 0 < lds <= 16384)
+        k32 = (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and (d_in, k) == _K32[f.env, f.dist][1:]
+               and d_in == f.obs_dim and 0 < lds <= 16384)
     chunk = max(1, f.graph_chunk) if f.use_graph and device and not collective else 1
     driver = ("host" if not device else "K32" if k32 else "eager" if not (f.use_graph and not collective)
               else "graph-chunk" if chunk > 1 else "graph-step")
