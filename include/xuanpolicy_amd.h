@@ -299,6 +299,42 @@ int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *args, xpa_stream_t str
 int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *args, const float *logstd, float act_clip,
                                xpa_stream_t stream);
 
+/* Device evaluation (the reference's test loop, ppoclip_agent.py:113-165 / a2c_agent.py:109-160, without a host round
+ * trip per step): an episode log on the device and its two writers.
+ * The log is int32 [xpa_eval_log_ints(capacity, snap_dim)], 16-B aligned, zeroed by the host but for `target`:
+ *   [0] count    finished episodes so far (all of them, also those past capacity)
+ *   [1] target   the host's test_episode: logging stops after the first step with count >= target
+ *   [2] done     latched at that step; a writer that finds it set changes nothing
+ *   [3] steps_run   env steps logged;  [4] overflow  1 when an entry did not fit;  [5 .. 7] for the host (the allocator
+ *                keeps capacity and snap_dim there for its decoder)
+ *   [8 ..]       the statistics snapshot: obs_count f64, obs_mean f32 [snap_dim], obs_var f32 [snap_dim], padded to 16 B
+ *   then         capacity entries of (step i32, env i32, score f32, length i32): step-major, ascending env index within
+ *                a step, step counted from the log's first step — the order the reference's loop appends in
+ * A step adds at most n_envs entries, so capacity = target + n_envs cannot overflow; entries past capacity are not
+ * written.  Plain vector stores only. */
+int64_t xpa_eval_log_ints(int64_t capacity, int64_t snap_dim);
+/* K32E — K32's evaluation form (the same kernel, EVAL instantiation): up to args->steps env steps in one launch, each
+ * K32's obs_rms.update (use_obsnorm), normalisation, forward, sampler and env step, bit for bit; no buffer column, no
+ * post step, no ret_rms.  The sampler's stores go to scratch (float [3 * n_envs]); its RNG key is (args->seed,
+ * args->cursor->step), the evaluation's own stream.  After each step the finished episodes (terminated or truncated)
+ * are appended to the log in env order, and the launch ends after the first step with count >= target; then it writes
+ * the env state, count, steps_run, done and the cursor (ptr 0, step advanced by the steps run).  A launch that finds
+ * done set returns at once, so several may be queued before the host looks.  Only what this form reads is required of
+ * args (weights, obs statistics, act_in, the env's tensors, cursor); the buffer / return / slot pointers may be NULL. */
+int xpa_small_eval_cartpole(const XpaSmallRolloutArgs *args, int32_t *log, int64_t capacity, int64_t snap_dim,
+                            float *scratch, xpa_stream_t stream);
+int xpa_small_eval_pendulum(const XpaSmallRolloutArgs *args, const float *logstd, float act_clip, int32_t *log,
+                            int64_t capacity, int64_t snap_dim, float *scratch, xpa_stream_t stream);
+/* The generic tier's log writer, one launch per env step after the env's step kernel (one workgroup over all envs, so
+ * a step's entries land in env order): appends the envs with term || trunc (atari_lifeloss = 1: not those that did
+ * not truncate), steps_run += 1, cursor->step += 1 (ptr stays 0).  At the step where count first reaches target it
+ * latches done and, when obs_mean / obs_var / obs_count are given (all or none), copies them into the snapshot: the
+ * caller's later steps of the same chunk still update the statistics, and the host restores them from here. */
+int xpa_eval_post(int32_t *log, int64_t capacity, int64_t snap_dim, int64_t n_envs, const uint8_t *term,
+                  const uint8_t *trunc, const float *ep_last_score, const int32_t *ep_last_len, int atari_lifeloss,
+                  xpa_cursor_t *cursor, const float *obs_mean, const float *obs_var, const double *obs_count,
+                  xpa_stream_t stream);
+
 /* K19 — PER-DQN TD target, loss, gradient and priorities (BASELINE.json configs[4]; replaces the tensor algebra
  * of PerDQN_Learner.update, xuance/torch/learners/qlearning_family/perdqn_learner.py:23-30, 48).
  * y = rew + (gamma * (1 - term)) * max_a targetQ[b, a]; p = evalQ[b, act[b]]; dQ[b, :] = one-hot(act[b]) * 2 (p - y) / B

@@ -39,9 +39,11 @@ from .buffer import DummyOnPolicyBuffer, DummyOnPolicyBuffer_Atari
 from .fused_mlp import FusedActorCritic, Rows, _no_form
 from .learners import A2C_Learner, PerDQN_Learner, PPOCLIP_Learner
 from .policies import policy_discrete, policy_heads, space_shape
-from .rollout_plan import RolloutFacts, plan_rollout
+from .rollout_plan import EvalFacts, RolloutFacts, eval_entry, plan_rollout, plan_test
 
 FLOAT_MAX = 3.0e38
+# test_device's action stream: the counter hash keyed by seed ^ EVAL_SALT and a step counter of its own
+EVAL_SALT = 0x7E57E9A1
 
 
 def _cfg(config, name, default):
@@ -61,6 +63,14 @@ FUSE_POST = True
 # each streaming all of B, costs 25.6 us against the library GEMM's 15.1 for the value form: 30.9 vs 21.1 us per
 # iteration, so the value-fused scan (K1V) stays the default
 VALUE_GEMM = os.environ.get("XPA_VALUE_GEMM", "0") == "1"
+
+
+def _space_clip(space):
+    """The one symmetric bound of a Box action space (what the device samplers clip a Gaussian action to)."""
+    lo, hi = (np.asarray(getattr(space, k), np.float64).reshape(-1) for k in ("low", "high"))
+    assert hi.size and np.all(hi == hi[0]) and np.all(lo == -hi) and np.isfinite(hi[0]) and hi[0] > 0, \
+        "the device samplers clip to one symmetric bound: action_space low %r high %r" % (lo, hi)
+    return float(hi[0])
 
 
 def rms_rollout_sync(start, end, all_reduce_sum):
@@ -180,6 +190,8 @@ class _OnPolicyAgent:
         self.fused_rollout = bool(_cfg(config, "fused_rollout", True))
         self._k32 = None                      # K32's argument block, rebuilt with the plan
         self._plan = self._plan_key = None
+        self._eval_cursor = None              # test_device's step counter (made on first use; continues across calls)
+        self.last_test_log = None             # test_device's decoded episode log (ops.eval_log_decode)
         self._params = list(policy.parameters())   # re-homing (flat.FlatState) moves their data, not the objects
         self.current_step = 0
         self.current_episode = np.zeros((N,), np.int32)
@@ -937,10 +949,172 @@ class _OnPolicyAgent:
         ops.obs_normalize(x, self.obs_mean, self.obs_var, self._obs_clip(), out)
         return out
 
+    # ---- test on the device (config.device_test; DESIGN.md §3, "Evaluation on the device") ----------------------
+    def _eval_facts(self, test_envs):
+        """What plan_test decides from (rollout_plan.EvalFacts) for these test envs."""
+        device = hasattr(test_envs, "step_device")
+        n = int(test_envs.num_envs)
+        layers = self.learner.small_policy_layers()
+        small = None
+        if layers is not None:
+            l0, l1, la, l2, _ = layers[0]
+            dims = (l0.in_features, l0.out_features, l1.out_features, l2.out_features, la.out_features)
+            small = dims + (int(ops.lib().xpa_small_rollout_lds_floats(n, self.obs_dim, *dims[1:]))
+                            if self.device.type == "cuda" else 0,)
+        return EvalFacts(cuda=self.device.type == "cuda", env=getattr(test_envs, "kind", "device") if device else "host",
+                         dist=self.dist, small=small, n_envs=n, obs_dim=self.obs_dim, raw_obs=self.raw_obs,
+                         world=self.world, sync_obs_rms=True if self.sync_obs_rms else
+                         "rollout" if self.sync_obs_rms_rollout else False)
+
+    def _eval_stream(self, rng):
+        """(seed, cursor) of the evaluation's action stream: seed ^ EVAL_SALT and a step counter of its own that
+        continues across calls — the training stream (self.seed, self.cursor) is neither replayed nor advanced;
+        rng = (seed, step) replaces both for one call (tests)."""
+        if rng is not None:
+            cur = ops.new_cursor(self.device)
+            step = int(rng[1]) & 0xFFFFFFFF
+            cur[1] = step - (1 << 32) if step >= (1 << 31) else step   # the uint32 step counter's bits
+            return int(rng[0]) & 0xFFFFFFFF, cur
+        if self._eval_cursor is None:
+            self._eval_cursor = ops.new_cursor(self.device)
+        return (int(self.seed) ^ EVAL_SALT) & 0xFFFFFFFF, self._eval_cursor
+
+    def _build_small_eval(self, env, seed, cursor):
+        """K32E's argument block over the test envs: _build_small_rollout's weights, statistics and env fields; the
+        training-only pointers (buffer, returns, slots) stay NULL."""
+        (l0, l1, la, l2, lc), code, slope, logstd = self.learner.small_policy_layers()
+        a = _lib.XpaSmallRolloutArgs()
+        a.n_envs, a.horizon, a.steps, a.d_in = int(env.num_envs), 1, 1, self.obs_dim
+        a.h0, a.h1, a.h2, a.k = l0.out_features, l1.out_features, l2.out_features, la.out_features
+        a.act_code, a.use_obsnorm, a.max_episode_steps = int(code), int(self.use_obsnorm), int(env.max_episode_steps)
+        a.slope, a.obs_clip = float(slope), float(self._obs_clip())
+        a.seed, a.env_seed = int(seed) & 0xFFFFFFFF, int(env.noise_seed) & 0xFFFFFFFF
+        p = ops._p
+        a.W0, a.b0, a.W1, a.b1, a.W2, a.b2 = (p(l0.weight), p(l0.bias), p(l1.weight), p(l1.bias), p(l2.weight),
+                                              p(l2.bias))
+        a.Wa, a.ba, a.Wc, a.bc = p(la.weight), p(la.bias), p(lc.weight), p(lc.bias)
+        a.obs_mean, a.obs_var, a.obs_count = p(self.obs_mean), p(self.obs_var), p(self.obs_count)
+        a.act_in, a.ld_act = p(env.act_in), env.act_in.stride(0)
+        a.env_state, a.env_obs, a.ld_obs = p(env.state), p(env.obs), env.obs.stride(0)
+        a.final_obs, a.env_rew, a.env_term, a.env_trunc = p(env.final_obs), p(env.rew), p(env.term), p(env.trunc)
+        a.ep_step, a.ep_index, a.ep_score = p(env.ep_step), p(env.ep_index), p(env.ep_score)
+        a.ep_last_score, a.ep_last_len = p(env.ep_last_score), p(env.ep_last_len)
+        a.cursor = p(cursor)
+        return a, logstd
+
+    @torch.no_grad()
+    def _eval_step(self, env, ws, log, capacity, snap_dim, seed, cursor, act_clip):
+        """One evaluation step of the "steps" tier, eager on the current stream, no host synchronisation: the host
+        loop's obs_rms.update + normalise + policy forward, K3 with horizon 1 into scratch columns and the test envs'
+        action input, the env's step, xpa_eval_post."""
+        x = env.obs
+        stats = None
+        if not self.raw_obs:
+            if self.use_obsnorm:
+                ops.rms_update(x, self.obs_mean, self.obs_var, self.obs_count, partials=ws["part"], ticket=ws["ticket"])
+                stats = (self.obs_mean, self.obs_var, self.obs_count)
+            x = ops.obs_normalize(x, self.obs_mean, self.obs_var, self._obs_clip(), ws["norm"])
+        head, logstd, v = policy_heads(self.policy, x)
+        ops.rollout_sample(self.dist, head.contiguous(), logstd, v.contiguous(), cursor, seed, ws["act"], ws["logp"],
+                           ws["val"], env.act_in, act_clip=act_clip)
+        env.step_device()
+        ops.eval_post(log, capacity, snap_dim, env.term, env.trunc, env.ep_last_score, env.ep_last_len, self.atari,
+                      cursor, stats=stats)
+
+    def plan_test(self, test_envs):
+        """The tier test_device would evaluate these envs on: "K32E" | "steps" | "host" (rollout_plan.plan_test)."""
+        return plan_test(self._eval_facts(test_envs))
+
+    def test_device(self, test_envs, test_episode, chunk=None, rng=None):
+        """test()'s loop on the device: the scores of the episodes that end on test_envs, in the order the reference's
+        loop appends them (step-major, ascending env index), up to and including the first step at which test_episode
+        of them have ended; obs_rms ends as it stands after that many updates, and nothing else of the agent changes.
+        Actions come from the counter-hash sampler on the evaluation's own stream (_eval_stream).
+          tier "K32E"   xpa_small_eval_*: `chunk` steps per launch (default 128, a training K32 launch), the log's
+                        header read after each launch; the kernel stops at the completing step itself
+          tier "steps"  _eval_step, `chunk` steps (default 8) between header reads; steps past the completing one
+                        still update obs_rms, which is then restored from the log's snapshot.  The eager step is
+                        bound by the host's launch rate (~250 us at C2's nets), so a read every 8 steps waits for
+                        nothing and at most 7 steps run past the stop (with 32, a 34-step evaluation paid for 64)
+        A log that is not complete after (test_episode // N + 2) * max_episode_steps steps raises."""
+        f = self._eval_facts(test_envs)
+        tier = plan_test(f)
+        if tier == "host":
+            raise ValueError("test_device: these test envs plan the host loop (no step_device, a CPU device, or a "
+                             "per-step obs_rms collective); use test()")
+        env, dev = test_envs, self.device
+        N, target = int(env.num_envs), int(test_episode)
+        max_ep = int(getattr(env, "max_episode_steps", 0) or 0)
+        if target < 1 or max_ep < 1:
+            raise ValueError("test_device: test_episode >= 1 and time-limited test envs (max_episode_steps)")
+        env.reset()
+        seed, cursor = self._eval_stream(rng)
+        snap_dim = 0 if self.raw_obs or not self.use_obsnorm else self.obs_dim
+        capacity = target + N
+        log = ops.eval_log_new(target, N, snap_dim, dev)
+        bound = (target // N + 2) * max_ep
+        if tier == "K32E":
+            chunk = 128 if chunk is None else int(chunk)
+            args, logstd = self._build_small_eval(env, seed, cursor)
+            args.steps = chunk
+            scratch = torch.empty((3 * N,), dtype=torch.float32, device=dev)
+            act_clip = 1.0 if self.discrete else _space_clip(env.action_space)
+
+            def step():
+                ops.small_eval(eval_entry(f), args, log, capacity, snap_dim, scratch, logstd, act_clip)
+        else:
+            chunk = 8 if chunk is None else int(chunk)
+            A = env.act_in.shape[1]
+            f32 = dict(dtype=torch.float32, device=dev)
+            ws = {"act": torch.empty((N, 1, A) if not self.discrete else (N, 1), **f32),
+                  "logp": torch.empty((N, 1), **f32), "val": torch.empty((N, 1), **f32)}
+            if not self.raw_obs:
+                ws["norm"] = torch.empty((N, self.obs_dim), **f32)
+                ws["part"] = torch.empty((2 * ops.rms_num_partials(N), self.obs_dim), dtype=torch.float64, device=dev)
+                ws["ticket"] = torch.zeros((1,), dtype=torch.int32, device=dev)
+            act_clip = 1.0 if self.discrete else _space_clip(env.action_space)
+
+            def step():
+                for _ in range(chunk):
+                    self._eval_step(env, ws, log, capacity, snap_dim, seed, cursor, act_clip)
+        if chunk < 1:
+            raise ValueError("test_device: chunk >= 1")
+        issued = 0
+        while True:
+            step()
+            issued += chunk
+            h = ops.eval_log_header(log)
+            if h["overflow"]:
+                raise _lib.XpaError("test_device: the episode log overflowed (%d entries, capacity %d)"
+                                    % (h["count"], capacity))
+            if h["done"]:
+                break
+            if issued >= bound:
+                raise RuntimeError("test_device: %d of %d episodes ended in %d steps (bound %d = (test_episode // N + 2)"
+                                   " * max_episode_steps)" % (h["count"], target, h["steps_run"], bound))
+        if tier == "steps" and snap_dim and issued > h["steps_run"]:
+            cnt, mean, var = ops.eval_log_snapshot(log, snap_dim)   # obs_rms as it stood after steps_run updates
+            self.obs_count.copy_(cnt)
+            self.obs_mean.copy_(mean)
+            self.obs_var.copy_(var)
+        self.last_test_log = ops.eval_log_decode(log.cpu().numpy())
+        return [float(s) for s in self.last_test_log["score"]]
+
     def test(self, env_fn, test_episode):
         """Run the current policy (stochastic actions) on env_fn()'s envs until test_episode episodes have
-        ended; returns their scores (infos[i]['episode_score'])."""
+        ended; returns their scores (infos[i]['episode_score']).  config.device_test: on the device (test_device)
+        where plan_test allows it."""
         test_envs = env_fn()
+        if bool(_cfg(self.config, "device_test", False)) and self.plan_test(test_envs) != "host":
+            scores = self.test_device(test_envs, test_episode)
+            if bool(_cfg(self.config, "test_mode", False)):
+                for i, s in enumerate(scores):
+                    print("Episode: %d, Score: %.2f" % (i + 1, s))
+                print("Best Score: %.2f" % max(scores))
+            self.log_infos({"Test-Episode-Rewards/Mean-Score": float(np.mean(scores)),
+                            "Test-Episode-Rewards/Std-Score": float(np.std(scores))}, self.current_step)
+            test_envs.close()
+            return scores
         num_envs = test_envs.num_envs
         current_episode, scores, best_score = 0, [], -np.inf
         obs, _ = test_envs.reset()

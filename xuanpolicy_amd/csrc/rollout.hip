@@ -1168,8 +1168,41 @@ struct RoPendulumGauss {
     }
 };
 
-template <class E, int ACT, int H0>
-__global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRolloutArgs a, typename E::Head hd) {
+// ---- the episode log of the device evaluation (K32E, xpa_eval_post; layout: include/xuanpolicy_amd.h) ----------------
+constexpr int kLogCount = 0, kLogTarget = 1, kLogDone = 2, kLogSteps = 3, kLogOverflow = 4, kLogHeader = 8;
+// int32 index of the first entry: the header, then the snapshot padded to 16 B
+__host__ __device__ constexpr int64_t eval_log_entries(int64_t snap_dim) {
+    return kLogHeader + ((2 + 2 * snap_dim + 3) & ~3LL);
+}
+
+// entry i of the log: (step, env, score, length); past capacity nothing is written and the overflow word is set
+__device__ __forceinline__ void eval_log_put(int32_t *log, int64_t ent0, int64_t capacity, int64_t i, int32_t step,
+                                             int32_t env, float score, int32_t len) {
+    if (i < capacity) {
+        int32_t *e = log + ent0 + 4 * i;
+        e[0] = step;
+        e[1] = env;
+        e[2] = __builtin_bit_cast(int32_t, score);
+        e[3] = len;
+    } else {
+        log[kLogOverflow] = 1;
+    }
+}
+
+// K32E's arguments beyond XpaSmallRolloutArgs (whose cursor / seed are then the evaluation's own)
+struct RoEval {
+    int32_t *log;
+    int64_t capacity, ent0;
+};
+struct RoNoEval {};
+
+// EVAL (K32E): the evaluation form — the same obs-RMS update, normalisation, forward, sampler and env step; no buffer
+// column (the sampler's three stores go to [N] scratch columns: T = 1, t = 0), no post step, no ret_rms; each step's
+// finished episodes are compacted into the log in env order and the step loop ends after the first step at which the
+// log holds `target` episodes (the reference's test loop, ppoclip_agent.py:113-165).
+template <class E, int ACT, int H0, bool EVAL = false>
+__global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRolloutArgs a, typename E::Head hd,
+                                                                   std::conditional_t<EVAL, RoEval, RoNoEval> ev) {
     extern __shared__ float lds[];
     __shared__ double s_sum[kRoThreads], s_sq[kRoThreads];
     __shared__ double s_red[kRoThreads / 64];
@@ -1180,6 +1213,14 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     const int tid = threadIdx.x;
     const int N = a.n_envs, H1 = a.h1, H2 = a.h2, K = a.k, K1 = a.k + 1, U = a.h1 + a.h2;
     const int T = a.horizon;
+    [[maybe_unused]] int32_t e_count = 0, e_target = 0, e_steps = 0;
+    if constexpr (EVAL) {
+        // block-uniform: a launch queued behind the one that completed the log returns at once
+        if (ev.log[kLogDone] != 0) return;
+        e_count = ev.log[kLogCount];
+        e_target = ev.log[kLogTarget];
+        e_steps = ev.log[kLogSteps];
+    }
     const RoLayout L = ro_layout(N, D, H0, H1, H2, K);
     float *sy = lds + L.sy, *sz = lds + L.sz, *sbo = lds + L.sbo;
     const typename E::Env env = E::env(a);
@@ -1223,7 +1264,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     float R = 0.f;
     if (tid < N) {
         es = E::load(env, tid);
-        R = a.returns[tid];
+        if constexpr (!EVAL) R = a.returns[tid];
 #pragma unroll
         for (int d = 0; d < D; ++d) s_obs[tid * D + d] = a.env_obs[tid * a.ld_obs + d];
     }
@@ -1234,13 +1275,13 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     double ocount = *a.obs_count;
     float rmean = 0.f, rvar = 0.f;
     double rcount = 0.0;
-    if (tid == 0) {
+    if (!EVAL && tid == 0) {
         rmean = *a.ret_mean;
         rvar = *a.ret_var;
         rcount = *a.ret_count;
         s_rstd = fminf(fmaxf(sqrtf(rvar), 0.1f), 100.0f);
     }
-    int32_t t = a.cursor->ptr;
+    int32_t t = EVAL ? 0 : a.cursor->ptr;
     uint32_t step = a.cursor->step;
     int64_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0, st_t0 = 0;
 #define XPA_RO_STAMP(i_)                                                    \
@@ -1321,8 +1362,10 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
             const int r = e / D, d = e % D;
             const float y = obs_norm1(s_obs[e], s_mean[d], s_var[d], a.obs_clip);
             sy[e] = y;
-            a.obs_norm[r * a.ld_norm + d] = y;
-            a.buf_obs[((int64_t)r * T + t) * D + d] = y;
+            if constexpr (!EVAL) {
+                a.obs_norm[r * a.ld_norm + d] = y;
+                a.buf_obs[((int64_t)r * T + t) * D + d] = y;
+            }
         }
         __syncthreads();
         XPA_RO_STAMP(1);
@@ -1374,6 +1417,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
         XPA_RO_STAMP(4);
         // (f) sample + store, env step, post step (one thread per env)
         double cnt = 0.0, sum = 0.0, sumsq = 0.0;
+        [[maybe_unused]] bool fin = false;
         if (tid < N) {
             float z[KO];
             for (int o = 0; o < K1; ++o) {
@@ -1386,14 +1430,43 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
             const float r = E::act_step(a, hd, env, tid, K, T, t, step, z, es, &te, &tr, o);
 #pragma unroll
             for (int d = 0; d < D; ++d) s_obs[tid * D + d] = o[d];
-            R = post_env<true, true>(tid, N, T, t, last, s_rstd, r, te, tr, 0.f, R, a.buf_rew, a.buf_term,
-                                     a.buf_closed, a.buf_boot, a.gamma, a.mask_returns, a.use_rewnorm, a.rew_range,
-                                     0, a.final_obs, D, D, a.slot_obs, a.slot_t, a.n_slots, a.overflow, s_mean, s_var,
-                                     a.obs_clip, a.boot_norm, a.ld_boot, cnt, sum, sumsq,
-                                     a.slot_reset_obs ? a.env_obs : nullptr, a.ld_obs);
-            a.returns[tid] = R;
+            if constexpr (EVAL) {
+                fin = te || tr;
+                (void)r;
+            } else {
+                R = post_env<true, true>(tid, N, T, t, last, s_rstd, r, te, tr, 0.f, R, a.buf_rew, a.buf_term,
+                                         a.buf_closed, a.buf_boot, a.gamma, a.mask_returns, a.use_rewnorm,
+                                         a.rew_range, 0, a.final_obs, D, D, a.slot_obs, a.slot_t, a.n_slots,
+                                         a.overflow, s_mean, s_var, a.obs_clip, a.boot_norm, a.ld_boot, cnt, sum,
+                                         sumsq, a.slot_reset_obs ? a.env_obs : nullptr, a.ld_obs);
+                a.returns[tid] = R;
+            }
         }
         XPA_RO_STAMP(5);
+        if constexpr (EVAL) {
+            // the step's finished episodes into the log in env order: lane offset from the wave's ballot, wave offset
+            // from the four wave totals (every thread forms the same new count: the stop below is block-uniform)
+            __shared__ int s_wtot[kRoThreads / 64];
+            const unsigned long long m = __ballot(fin);
+            if (lane == 0) s_wtot[wave] = __popcll(m);
+            __syncthreads();
+            int before = 0, total = 0;
+            for (int w = 0; w < kRoThreads / 64; ++w) {
+                if (w < wave) before += s_wtot[w];
+                total += s_wtot[w];
+            }
+            if (fin) {
+                const int64_t i = (int64_t)e_count + before + __popcll(m & ((1ull << lane) - 1ull));
+                eval_log_put(ev.log, ev.ent0, ev.capacity, i, e_steps, tid, env.ep_last_score[tid],
+                             env.ep_last_len[tid]);
+            }
+            e_count += total;
+            e_steps += 1;
+            step += 1u;
+            __syncthreads();  // next observations and statistics visible to the next step; s_wtot free again
+            if (e_count >= e_target) break;
+            continue;
+        }
         // (g) ret_rms over the closed paths: K8's block sums (all envs in wave 0 when N <= 64: the other waves'
         // sums are +0), then its merge
         if (N <= 64) {
@@ -1430,6 +1503,65 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     if (tid == 0) {
         a.cursor->ptr = t;
         a.cursor->step = step;
+        if constexpr (EVAL) {
+            ev.log[kLogCount] = e_count;
+            ev.log[kLogSteps] = e_steps;
+            ev.log[kLogDone] = e_count >= e_target ? 1 : 0;
+        }
+    }
+}
+
+// xpa_eval_post: one workgroup walks the envs in passes of kEvalThreads, so a step's entries land in env order (lane
+// offset from the wave's ballot, wave offset from the pass's wave totals, pass offset carried along).
+constexpr int kEvalThreads = 1024;
+__global__ __launch_bounds__(kEvalThreads) void eval_post_kernel(
+    int32_t *__restrict__ log, int64_t capacity, int64_t ent0, int64_t n_envs, const uint8_t *__restrict__ term,
+    const uint8_t *__restrict__ trunc, const float *__restrict__ ep_last_score,
+    const int32_t *__restrict__ ep_last_len, int atari_lifeloss, xpa_cursor_t *__restrict__ cur,
+    const float *__restrict__ obs_mean, const float *__restrict__ obs_var, const double *__restrict__ obs_count,
+    int64_t snap_dim) {
+    __shared__ int s_wtot[kEvalThreads / 64];
+    if (log[kLogDone] != 0) return;   // block-uniform
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int32_t step = log[kLogSteps];
+    int64_t count = log[kLogCount];
+    const int32_t target = log[kLogTarget];
+    for (int64_t n0 = 0; n0 < n_envs; n0 += kEvalThreads) {
+        const int64_t n = n0 + tid;
+        bool fin = false;
+        if (n < n_envs) {
+            const bool te = term[n] != 0, tr = trunc[n] != 0;
+            fin = (te || tr) && !(atari_lifeloss && !tr);   // a life loss: the game goes on
+        }
+        const unsigned long long m = __ballot(fin);
+        if (lane == 0) s_wtot[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < kEvalThreads / 64; ++w) {
+            if (w < wave) before += s_wtot[w];
+            total += s_wtot[w];
+        }
+        if (fin)
+            eval_log_put(log, ent0, capacity, count + before + __popcll(m & ((1ull << lane) - 1ull)), step, (int32_t)n,
+                         ep_last_score[n], ep_last_len[n]);
+        count += total;
+        __syncthreads();   // s_wtot free for the next pass
+    }
+    const bool latch = count >= target;
+    if (latch && obs_count) {   // the statistics as they stand after this step's update (the host restores them)
+        float *snap = reinterpret_cast<float *>(log + kLogHeader);
+        for (int64_t d = tid; d < snap_dim; d += kEvalThreads) {
+            snap[2 + d] = obs_mean[d];
+            snap[2 + snap_dim + d] = obs_var[d];
+        }
+        if (tid == 0) *reinterpret_cast<double *>(snap) = *obs_count;
+    }
+    if (tid == 0) {
+        log[kLogCount] = (int32_t)count;
+        log[kLogSteps] = step + 1;
+        if (latch) log[kLogDone] = 1;
+        cur->ptr = 0;
+        cur->step = cur->step + 1u;
     }
 }
 
@@ -1899,6 +2031,48 @@ XPA_API int64_t xpa_small_rollout_lds_floats(int64_t n_envs, int64_t d_in, int64
 
 namespace {
 // The checks and the launch shared by K32's entry points; E: the instantiation's env / head pair, k its head width.
+// K32E's checks and launch: only what the evaluation form dereferences is required (the training-only pointers of
+// XpaSmallRolloutArgs may be null); horizon 1 and the sampler's three stores into scratch [3 * n_envs]
+template <class E>
+int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd, int32_t *log, int64_t capacity,
+                      int64_t snap_dim, float *scratch, xpa_stream_t stream) {
+    if (!a0 || !log || capacity <= 0 || capacity > 0x7fffffff || snap_dim < 0 || !scratch || ((uintptr_t)log % 16))
+        return (int)hipErrorInvalidValue;
+    XpaSmallRolloutArgs a = *a0;
+    if (a.n_envs <= 0 || a.n_envs > 256 || a.steps <= 0 || a.d_in != E::D || (a.h0 != 32 && a.h0 != 64) ||
+        (a.h1 != 32 && a.h1 != 64) || (a.h2 != 32 && a.h2 != 64) || a.k != k || a.act_code < 0 || a.act_code > 2 ||
+        a.max_episode_steps <= 0 || a.ld_obs < E::D || a.ld_act < k)
+        return (int)hipErrorInvalidValue;
+    if (!a.W0 || !a.b0 || !a.W1 || !a.b1 || !a.W2 || !a.b2 || !a.Wa || !a.ba || !a.Wc || !a.bc || !a.obs_mean ||
+        !a.obs_var || !a.obs_count || !a.act_in || !a.env_state || !a.env_obs || !a.final_obs || !a.env_rew ||
+        !a.env_term || !a.env_trunc || !a.ep_step || !a.ep_index || !a.ep_score || !a.ep_last_score || !a.ep_last_len ||
+        !a.cursor)
+        return (int)hipErrorInvalidValue;
+    const int64_t lf = xpa_small_rollout_lds_floats(a.n_envs, a.d_in, a.h0, a.h1, a.h2, a.k);
+    if (lf < 0 || lf > kRoLdsMax) return (int)hipErrorInvalidValue;
+    a.horizon = 1;
+    a.buf_act = scratch;
+    a.buf_logp = scratch + a.n_envs;
+    a.buf_val = scratch + 2 * a.n_envs;
+    a.stamps = nullptr;
+    const RoEval ev{log, capacity, eval_log_entries(snap_dim)};
+    const size_t bytes = (size_t)lf * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+#define XPA_RO_LAUNCH(ACT, H0) \
+    hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0, true>), dim3(1), dim3(kRoThreads), bytes, s, a, hd, ev)
+    if (a.h0 == 64) {
+        if (a.act_code == 0) XPA_RO_LAUNCH(0, 64);
+        else if (a.act_code == 1) XPA_RO_LAUNCH(1, 64);
+        else XPA_RO_LAUNCH(2, 64);
+    } else {
+        if (a.act_code == 0) XPA_RO_LAUNCH(0, 32);
+        else if (a.act_code == 1) XPA_RO_LAUNCH(1, 32);
+        else XPA_RO_LAUNCH(2, 32);
+    }
+#undef XPA_RO_LAUNCH
+    return xpa_launch_status();
+}
+
 template <class E>
 int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head hd, xpa_stream_t stream) {
     if (!a || a->n_envs <= 0 || a->n_envs > 256 || a->horizon <= 0 || a->steps <= 0 || a->d_in != E::D ||
@@ -1918,7 +2092,7 @@ int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head h
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
 #define XPA_RO_LAUNCH(ACT, H0) \
-    hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a, hd)
+    hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a, hd, RoNoEval{})
     if (a->h0 == 64) {
         if (a->act_code == 0) XPA_RO_LAUNCH(0, 64);
         else if (a->act_code == 1) XPA_RO_LAUNCH(1, 64);
@@ -1941,4 +2115,37 @@ XPA_API int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *a, const float
                                        xpa_stream_t stream) {
     if (!logstd || !(act_clip > 0.f)) return (int)hipErrorInvalidValue;
     return small_rollout_launch<RoPendulumGauss>(a, 1, RoPendulumGauss::Head{logstd, act_clip}, stream);
+}
+
+// ---- device evaluation: K32E and the generic tier's per-step log writer ---------------------------------------------
+XPA_API int64_t xpa_eval_log_ints(int64_t capacity, int64_t snap_dim) {
+    if (capacity <= 0 || capacity > 0x7fffffff || snap_dim < 0) return -1;
+    return eval_log_entries(snap_dim) + 4 * capacity;
+}
+
+XPA_API int xpa_small_eval_cartpole(const XpaSmallRolloutArgs *a, int32_t *log, int64_t capacity, int64_t snap_dim,
+                                    float *scratch, xpa_stream_t stream) {
+    return small_eval_launch<RoCartPoleCat>(a, 2, RoCartPoleCat::Head{}, log, capacity, snap_dim, scratch, stream);
+}
+
+XPA_API int xpa_small_eval_pendulum(const XpaSmallRolloutArgs *a, const float *logstd, float act_clip, int32_t *log,
+                                    int64_t capacity, int64_t snap_dim, float *scratch, xpa_stream_t stream) {
+    if (!logstd || !(act_clip > 0.f)) return (int)hipErrorInvalidValue;
+    return small_eval_launch<RoPendulumGauss>(a, 1, RoPendulumGauss::Head{logstd, act_clip}, log, capacity, snap_dim,
+                                              scratch, stream);
+}
+
+XPA_API int xpa_eval_post(int32_t *log, int64_t capacity, int64_t snap_dim, int64_t n_envs, const uint8_t *term,
+                          const uint8_t *trunc, const float *ep_last_score, const int32_t *ep_last_len,
+                          int atari_lifeloss, xpa_cursor_t *cursor, const float *obs_mean, const float *obs_var,
+                          const double *obs_count, xpa_stream_t stream) {
+    if (!log || ((uintptr_t)log % 16) || capacity <= 0 || capacity > 0x7fffffff || snap_dim < 0 || n_envs <= 0 ||
+        n_envs > 0x7fffffff || !term || !trunc || !ep_last_score || !ep_last_len || !cursor)
+        return (int)hipErrorInvalidValue;
+    if ((obs_count != nullptr) != (obs_mean != nullptr) || (obs_count != nullptr) != (obs_var != nullptr))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(eval_post_kernel, dim3(1), dim3(kEvalThreads), 0, (hipStream_t)stream, log, capacity,
+                       eval_log_entries(snap_dim), n_envs, term, trunc, ep_last_score, ep_last_len, atari_lifeloss,
+                       cursor, obs_mean, obs_var, obs_count, snap_dim);
+    return xpa_launch_status();
 }

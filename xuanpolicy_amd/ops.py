@@ -6,6 +6,7 @@ There is no CPU path: tensors must live on a ROCm device.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1510,3 +1511,109 @@ def dqn_td_loss(evalQ, targetQ, act, rew, term, gamma, dQ=None, td_abs=None, sca
     _lib.call(lib().xpa_dqn_td_loss, B, A, _p(evalQ), ld_e, _p(targetQ), ld_t, _p(act), _p(rew), _p(term), float(gamma),
               _p(dQ), A, _p(td_abs), _p(scalars), _p(err), _stream(evalQ.device))
     return dQ, td_abs, scalars
+
+
+# ------------------------------------------------------------------------------------------------
+# Device evaluation: the episode log (include/xuanpolicy_amd.h, "Device evaluation") and its writers
+EVAL_LOG_HEADER = 8   # int32 words: count, target, done, steps_run, overflow, (host: capacity, snap_dim, 0)
+
+
+def eval_log_layout(capacity, snap_dim):
+    """(first int32 of the entries, int32 words in all) of a log of `capacity` entries whose snapshot holds snap_dim
+    columns: xpa_eval_log_ints' arithmetic, on the host alone."""
+    ent0 = EVAL_LOG_HEADER + ((2 + 2 * int(snap_dim) + 3) & ~3)
+    return ent0, ent0 + 4 * int(capacity)
+
+
+def eval_log_new(target, n_envs, snap_dim, device, capacity=None, guard=0):
+    """A fresh log for `target` episodes over n_envs envs (capacity target + n_envs: a step adds at most n_envs
+    entries and logging stops at the first step with count >= target).  guard: int32 words kept behind the log, set
+    to -1 (tests); the log is the returned tensor's first eval_log_layout(...)[1] words."""
+    capacity = int(target) + int(n_envs) if capacity is None else int(capacity)
+    _, total = eval_log_layout(capacity, snap_dim)
+    if device.type == "cuda" and int(lib().xpa_eval_log_ints(capacity, int(snap_dim))) != total:
+        raise _lib.XpaError("eval log layout: the library and ops.eval_log_layout disagree")
+    host = np.zeros((total + int(guard),), np.int32)
+    host[1], host[5], host[6] = int(target), capacity, int(snap_dim)
+    host[total:] = -1
+    return torch.as_tensor(host, device=device)
+
+
+def eval_log_decode(words):
+    """The log's content from its int32 words (a numpy array; pure host code): count, target, done, steps_run,
+    overflow, the entries written — step / env / length int32, score float32, in log order — and the snapshot
+    (obs_count f64, obs_mean / obs_var f32 [snap_dim])."""
+    w = np.ascontiguousarray(np.asarray(words, np.int32).reshape(-1))
+    capacity, snap_dim = int(w[5]), int(w[6])
+    ent0, total = eval_log_layout(capacity, snap_dim)
+    if capacity <= 0 or w.size < total:
+        raise ValueError("eval log: %d words, capacity %d and snap_dim %d need %d"
+                         % (w.size, capacity, snap_dim, total))
+    n = min(int(w[0]), capacity)
+    ent = w[ent0:ent0 + 4 * n].reshape(n, 4)
+    snap = w[EVAL_LOG_HEADER:ent0]
+    return {"count": int(w[0]), "target": int(w[1]), "done": bool(w[2]), "steps_run": int(w[3]),
+            "overflow": bool(w[4]), "capacity": capacity, "step": ent[:, 0].copy(), "env": ent[:, 1].copy(),
+            "score": ent[:, 2].copy().view(np.float32), "length": ent[:, 3].copy(),
+            "obs_count": float(snap[:2].copy().view(np.float64)[0]),
+            "obs_mean": snap[2:2 + snap_dim].copy().view(np.float32),
+            "obs_var": snap[2 + snap_dim:2 + 2 * snap_dim].copy().view(np.float32)}
+
+
+def eval_log_header(log):
+    """The five header words of a device log as host ints (one 32-byte D2H copy: the evaluation's only sync)."""
+    h = log[:EVAL_LOG_HEADER].cpu().numpy()
+    return {"count": int(h[0]), "target": int(h[1]), "done": bool(h[2]), "steps_run": int(h[3]), "overflow": bool(h[4])}
+
+
+def eval_log_snapshot(log, snap_dim):
+    """Device views (obs_count f64 [1], obs_mean f32 [D], obs_var f32 [D]) of a log's statistics snapshot."""
+    D = int(snap_dim)
+    s = log[EVAL_LOG_HEADER:EVAL_LOG_HEADER + 2 + 2 * D]
+    return s[:2].view(torch.float64), s[2:2 + D].view(torch.float32), s[2 + D:].view(torch.float32)
+
+
+def _eval_log_dims(log, capacity, snap_dim):
+    _req(log, "log", torch.int32)
+    if log.dim() != 1 or log.numel() < eval_log_layout(capacity, snap_dim)[1]:
+        raise ValueError("log: int32 [>= %d] for capacity %d, snap_dim %d" % (eval_log_layout(capacity, snap_dim)[1],
+                                                                             capacity, snap_dim))
+
+
+def eval_post(log, capacity, snap_dim, term, trunc, ep_last_score, ep_last_len, atari_lifeloss, cursor, stats=None):
+    """xpa_eval_post: append the step's finished episodes to the log in env order, advance steps_run and the
+    evaluation cursor's step; stats = (obs_mean, obs_var, obs_count) are copied into the snapshot at the step that
+    completes the log."""
+    _eval_log_dims(log, capacity, snap_dim)
+    N = term.shape[0]
+    _req(term, "term", torch.uint8, (N,))
+    _req(trunc, "trunc", torch.uint8, (N,))
+    _req(ep_last_score, "ep_last_score", torch.float32, (N,))
+    _req(ep_last_len, "ep_last_len", torch.int32, (N,))
+    _req(cursor, "cursor", torch.int32, (4,))
+    mean = var = count = None
+    if stats is not None:
+        mean, var, count = stats
+        _req(mean, "obs_mean", torch.float32, (snap_dim,))
+        _req(var, "obs_var", torch.float32, (snap_dim,))
+        _req(count, "obs_count", torch.float64, (1,))
+    _lib.call(lib().xpa_eval_post, _p(log), int(capacity), int(snap_dim), N, _p(term), _p(trunc), _p(ep_last_score),
+              _p(ep_last_len), int(bool(atari_lifeloss)), _p(cursor), _p(mean), _p(var), _p(count), _stream(log.device))
+
+
+def small_eval(entry, args, log, capacity, snap_dim, scratch, logstd=None, act_clip=1.0):
+    """K32E (xpa_small_eval_cartpole / _pendulum): up to args.steps evaluation steps in one launch, the finished
+    episodes into the log.  args: an XpaSmallRolloutArgs whose seed / cursor are the evaluation's; scratch f32
+    [3 * n_envs]."""
+    _eval_log_dims(log, capacity, snap_dim)
+    _req(scratch, "scratch", torch.float32, (3 * int(args.n_envs),))
+    s = _stream(log.device)
+    if entry == "xpa_small_eval_cartpole":
+        _lib.call(lib().xpa_small_eval_cartpole, ctypes.byref(args), _p(log), int(capacity), int(snap_dim),
+                  _p(scratch), s)
+    elif entry == "xpa_small_eval_pendulum":
+        _req(logstd, "logstd", torch.float32, (1,))
+        _lib.call(lib().xpa_small_eval_pendulum, ctypes.byref(args), _p(logstd), float(act_clip), _p(log),
+                  int(capacity), int(snap_dim), _p(scratch), s)
+    else:
+        raise _lib.XpaError("no one-launch evaluation entry point named %r" % (entry,))

@@ -199,3 +199,39 @@ def plan_rollout(f):
                 else "epoch" if f.epoch_graphs else "slot")
     return RolloutPlan(driver, chunk, obs, rms, trunk, value_trunk, pair, head, "host" if not device else
                        "in-head" if fused else f.env, post, boot, mid, close, gae, feed)
+
+
+# ---- evaluation (agent.test) ------------------------------------------------------------------------------------------
+# K32's evaluation form (K32E): the entry point of each of K32's instantiations
+_K32E = {("cartpole", "categorical"): "xpa_small_eval_cartpole", ("pendulum", "gaussian"): "xpa_small_eval_pendulum"}
+
+
+class EvalFacts(NamedTuple):
+    """What plan_test decides from.  _OnPolicyAgent._eval_facts gathers it for one set of test envs."""
+    cuda: bool
+    env: str                  # the test envs' kind ("cartpole", ...), "device" (another one) or "host" (no step_device)
+    dist: str                 # the head's distribution: "categorical" | "gaussian"
+    small: object             # K32's shape (d_in, h0, h1, h2, k, LDS floats at the test envs' count), or None
+    n_envs: int               # test_envs.num_envs
+    obs_dim: int
+    raw_obs: bool
+    world: int
+    sync_obs_rms: object      # as RolloutFacts.sync_obs_rms
+
+
+def plan_test(f):
+    """The tier agent.test_device evaluates on: "K32E" (whole steps in one launch: xpa_small_eval_*), "steps" (the
+    multi-kernel step, eager, + xpa_eval_post) or "host" (the reference's Python loop).  The only place it is decided."""
+    if not f.cuda or f.env == "host" or (f.sync_obs_rms is True and f.world > 1):   # the per-step collective
+        return "host"
+    if (f.env, f.dist) in _K32E and not f.raw_obs and 0 < f.n_envs <= 256 and f.small is not None:
+        d_in, h0, h1, h2, k, lds = f.small
+        if (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and (d_in, k) == _K32[f.env, f.dist][1:]
+                and d_in == f.obs_dim and 0 < lds <= 16384):
+            return "K32E"
+    return "steps"
+
+
+def eval_entry(f):
+    """K32E's entry point for facts that plan "K32E"."""
+    return _K32E[f.env, f.dist]
