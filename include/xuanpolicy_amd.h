@@ -245,6 +245,42 @@ int xpa_pendulum_step(int64_t n_envs, const float *act_in, int64_t ld_act, doubl
                       int32_t *ep_step, uint32_t *ep_index, float *ep_score, float *ep_last_score,
                       int32_t *ep_last_len, uint32_t seed, int32_t max_episode_steps, xpa_stream_t stream);
 
+/* K18A — Acrobot-v1 device env step (the env of the reference's classic_control/Acrobot-v1.yaml configs).  One thread
+ * per env, f64 state [n_envs, 4] = (th1, th2, thdot1, thdot2), every operation rounded on its own (no fma); action =
+ * the index of the one-hot row act_in[n * ld_act + 0..2] (torque a = action - 1); m1 = m2 = l1 = I1 = I2 = 1,
+ * lc1 = lc2 = 0.5, g = 9.8, dt = 0.2.  The "book" derivative f(th1, th2, thdot1, thdot2), in this operation order:
+ *   d1   = m1 lc1^2 + m2 (l1^2 + lc2^2 + 2 l1 lc2 cos th2) + I1 + I2;   d2 = m2 (lc2^2 + l1 lc2 cos th2) + I2
+ *   phi2 = m2 lc2 g cos(th1 + th2 - pi / 2)
+ *   phi1 = -m2 l1 lc2 thdot2^2 sin th2 - 2 m2 l1 lc2 thdot2 thdot1 sin th2 + (m1 lc1 + m2 l1) g cos(th1 - pi / 2) + phi2
+ *   dd2  = (a + d2 / d1 phi1 - m2 l1 lc2 thdot1^2 sin th2 - phi2) / (m2 lc2^2 + I2 - d2^2 / d1)
+ *   dd1  = -(d2 dd2 + phi1) / d1;   f = (thdot1, thdot2, dd1, dd2)
+ * One classic RK4 step over [0, dt] (y' = y + dt / 6 (((k1 + 2 k2) + 2 k3) + k4)), th1 / th2 wrapped into [-pi, pi] by
+ * repeated -+ 2 pi (an angle that is not finite or lies beyond +-1e6, which no step from a clamped state reaches, is
+ * left as it is: the wrap loops end on any input), thdot1 / thdot2 clamped to +-4 pi / +-9 pi; terminated = -cos th1 - cos(th2 + th1) > 1 on the new
+ * state, reward 0 when terminated, else -1; truncated at max_episode_steps; done envs auto-reset with every state dim
+ * hashed 0.2 u01 - 0.1 (f32-exact uniforms, then f64).  Observation (f32): cos th1, sin th1, cos th2, sin th2, thdot1,
+ * thdot2; final_obs [n_envs, 6], obs (row stride ld_obs >= 6), rew, term, trunc and the counters follow
+ * xpa_cartpole_step's contract. */
+int xpa_acrobot_step(int64_t n_envs, const float *act_in, int64_t ld_act, double *state, float *obs,
+                     int64_t ld_obs, float *final_obs, float *rew, uint8_t *term, uint8_t *trunc,
+                     int32_t *ep_step, uint32_t *ep_index, float *ep_score, float *ep_last_score,
+                     int32_t *ep_last_len, uint32_t seed, int32_t max_episode_steps, xpa_stream_t stream);
+
+/* K18M — MountainCar-v0 device env step behind the reference's MountainCar wrapper (gym_env.py:52-85: the last four
+ * (position, velocity) frames, oldest first).  One thread per env, f64 state [n_envs, 2] = (position, velocity), every
+ * operation rounded on its own; action = the index of the one-hot row act_in[n * ld_act + 0..2]:
+ *   velocity += (action - 1) * 0.001 + cos(3 position) * (-0.0025);  velocity = clamp(velocity, -0.07, 0.07)
+ *   position += velocity;  position = clamp(position, -1.2, 0.6);  if position == -1.2 and velocity < 0: velocity = 0
+ *   terminated = position >= 0.5 and velocity >= 0;  reward = -1
+ * Truncated at max_episode_steps; done envs auto-reset with hashed position = 0.2 u01 - 0.6, velocity = 0.  The frame
+ * stack lives in the env's observation row (row stride ld_obs >= 8): a step moves obs[2..7] down to [0..5] and appends
+ * its (float) frame; final_obs [n_envs, 8] is that stack, and after a done obs is the reset frame four times.  rew,
+ * term, trunc and the counters follow xpa_cartpole_step's contract. */
+int xpa_mountaincar_step(int64_t n_envs, const float *act_in, int64_t ld_act, double *state, float *obs,
+                         int64_t ld_obs, float *final_obs, float *rew, uint8_t *term, uint8_t *trunc,
+                         int32_t *ep_step, uint32_t *ep_index, float *ep_score, float *ep_last_score,
+                         int32_t *ep_last_len, uint32_t seed, int32_t max_episode_steps, xpa_stream_t stream);
+
 /* K32— `steps` whole device env steps of a small-MLP Categorical PPO / A2C agent on CartPole in ONE launch (one
  * workgroup; the step loop of ppoclip_agent.py:43-101 / a2c_agent.py:42-98 with DummyVecEnv_Gym's auto-reset):
  * per step, obs_rms.update (xpa_rms_update's sums and merge, in its order), the normalisation into obs_norm and the
@@ -298,6 +334,12 @@ int xpa_small_rollout_cartpole(const XpaSmallRolloutArgs *args, xpa_stream_t str
  * and the env K18P's step (xpa_pendulum_step) with the clipped action.  logstd: float [1]. */
 int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *args, const float *logstd, float act_clip,
                                xpa_stream_t stream);
+/* K32 for a Categorical head of 3 actions on Acrobot (d_in == 6, k == 3, env_state [n_envs, 4], final_obs [n_envs, 6],
+ * K18A's step) and on MountainCar (d_in == 8, k == 3, env_state [n_envs, 2], final_obs [n_envs, 8], K18M's step with the
+ * frame stack in env_obs): the kernel takes any observation width 1 .. 8 of an instantiation (the first layer, the
+ * normalised row and the obs-RMS row groups 256 / d_in are loops over d_in, accumulated in ascending d). */
+int xpa_small_rollout_acrobot(const XpaSmallRolloutArgs *args, xpa_stream_t stream);
+int xpa_small_rollout_mountaincar(const XpaSmallRolloutArgs *args, xpa_stream_t stream);
 
 /* Device evaluation (the reference's test loop, ppoclip_agent.py:113-165 / a2c_agent.py:109-160, without a host round
  * trip per step): an episode log on the device and its two writers.
@@ -325,6 +367,10 @@ int xpa_small_eval_cartpole(const XpaSmallRolloutArgs *args, int32_t *log, int64
                             float *scratch, xpa_stream_t stream);
 int xpa_small_eval_pendulum(const XpaSmallRolloutArgs *args, const float *logstd, float act_clip, int32_t *log,
                             int64_t capacity, int64_t snap_dim, float *scratch, xpa_stream_t stream);
+int xpa_small_eval_acrobot(const XpaSmallRolloutArgs *args, int32_t *log, int64_t capacity, int64_t snap_dim,
+                           float *scratch, xpa_stream_t stream);
+int xpa_small_eval_mountaincar(const XpaSmallRolloutArgs *args, int32_t *log, int64_t capacity, int64_t snap_dim,
+                               float *scratch, xpa_stream_t stream);
 /* The generic tier's log writer, one launch per env step after the env's step kernel (one workgroup over all envs, so
  * a step's entries land in env order): appends the envs with term || trunc (atari_lifeloss = 1: not those that did
  * not truncate), steps_run += 1, cursor->step += 1 (ptr stays 0).  At the step where count first reaches target it

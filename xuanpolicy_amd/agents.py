@@ -504,7 +504,7 @@ class _OnPolicyAgent:
         self._rms_c0 = None
 
     def _build_small_rollout(self):
-        """K32's argument block (xpa_small_rollout_cartpole / _pendulum) for a plan whose driver is K32; plan() rebuilds
+        """K32's argument block (xpa_small_rollout_<env>) for a plan whose driver is K32; plan() rebuilds
         it when the parameters are re-homed (the block holds their pointers)."""
         env, mem = self.envs, self.memory
         (l0, l1, la, l2, lc), code, slope, self._k32_logstd = self.learner.small_policy_layers()
@@ -543,8 +543,9 @@ class _OnPolicyAgent:
 
     def _small_rollout_launch(self, steps):
         self._k32.steps = int(steps)
-        if self._k32_entry == "xpa_small_rollout_cartpole":
-            _lib.call(ops.lib().xpa_small_rollout_cartpole, ctypes.byref(self._k32), ops._stream(self.device))
+        if self._k32_entry in ("xpa_small_rollout_cartpole", "xpa_small_rollout_acrobot",
+                               "xpa_small_rollout_mountaincar"):   # Categorical heads: the block alone
+            _lib.call(getattr(ops.lib(), self._k32_entry), ctypes.byref(self._k32), ops._stream(self.device))
         elif self._k32_entry == "xpa_small_rollout_pendulum":
             _lib.call(ops.lib().xpa_small_rollout_pendulum, ctypes.byref(self._k32), ops._p(self._k32_logstd),
                       self._act_clip(), ops._stream(self.device))

@@ -6,7 +6,9 @@
 //   K8 xpa_rollout_post      reward norm, return tracker, ret_rms, path closures (ppoclip_agent.py:68-101)
 // All per-step kernels read the buffer column from a device cursor so a whole env step can be
 // captured once in a hipGraph and replayed.
+#include "acrobot_body.h"
 #include "cartpole_body.h"
+#include "mountaincar_body.h"
 #include "pendulum_body.h"
 
 namespace {
@@ -1047,7 +1049,8 @@ __global__ __launch_bounds__(kPostThreads) void rollout_post_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// K32 — `steps` device env steps of a small-MLP Categorical agent on CartPole in one launch (one workgroup):
+// K32 — `steps` device env steps of a small-MLP agent on a classic-control env (the E trait: observation width 1..8)
+// in one launch (one workgroup):
 // obs RMS (K5) -> normalise (obs_normalize) -> MLP forward -> K3 sample/store -> K18 env step -> K8 (deferred,
 // NORM).  The RMS sums, the merge, the normalisation, the sampler, the env and the post step are the multi-kernel
 // path's own code or arithmetic (one RMS partial block: rows summed per (row group, column) and the groups in
@@ -1062,7 +1065,7 @@ __host__ __device__ constexpr int ro_r4(int x) { return (x + 3) & ~3; }
 struct RoLayout {
     int sy, sz, sbo, total;
 };
-// sy: the normalised observations [N][4]; sz: the output layers' partial sums [wave][N][K + 1]; sbo: biases
+// sy: the normalised observations [N][D]; sz: the output layers' partial sums [wave][N][K + 1]; sbo: biases
 __host__ __device__ inline RoLayout ro_layout(int N, int D, int H0, int H1, int H2, int K) {
     RoLayout l;
     const int K1 = K + 1;
@@ -1168,6 +1171,49 @@ struct RoPendulumGauss {
     }
 };
 
+// Acrobot-v1 / MountainCar-v0 with a Categorical head of 3 actions: K3's categorical sampler, then the env's step
+struct RoAcrobotCat {
+    static constexpr int D = 6, KO = 4;
+    using Env = XpaAcrobotEnv;
+    using Local = acrobot::Local;
+    struct Head {};
+    static __device__ __forceinline__ Env env(const XpaSmallRolloutArgs &a) {
+        return Env{a.env_state, a.env_obs,  a.ld_obs,   a.final_obs,     a.env_rew,     a.env_term,  a.env_trunc,
+                   a.ep_step,   a.ep_index, a.ep_score, a.ep_last_score, a.ep_last_len, a.env_seed,
+                   a.max_episode_steps};
+    }
+    static __device__ __forceinline__ Local load(const Env &e, int n) { return acrobot::load(e, n); }
+    static __device__ __forceinline__ void store(const Env &e, int n, const Local &s) { acrobot::store(e, n, s); }
+    static __device__ __forceinline__ float act_step(const XpaSmallRolloutArgs &a, const Head &, const Env &e, int n,
+                                                     int K, int T, int32_t t, uint32_t step, const float *z, Local &es,
+                                                     bool *te, bool *tr, float *o) {
+        const int pick = cat_sample_store_at(n, K, T, t, step, z, z[K], a.seed, a.buf_act, a.buf_logp, a.buf_val,
+                                             a.act_in, a.ld_act);
+        return acrobot::step(e, n, pick, es, te, tr, o);
+    }
+};
+
+struct RoMountainCarCat {
+    static constexpr int D = 8, KO = 4;
+    using Env = XpaMountainCarEnv;
+    using Local = mountaincar::Local;
+    struct Head {};
+    static __device__ __forceinline__ Env env(const XpaSmallRolloutArgs &a) {
+        return Env{a.env_state, a.env_obs,  a.ld_obs,   a.final_obs,     a.env_rew,     a.env_term,  a.env_trunc,
+                   a.ep_step,   a.ep_index, a.ep_score, a.ep_last_score, a.ep_last_len, a.env_seed,
+                   a.max_episode_steps};
+    }
+    static __device__ __forceinline__ Local load(const Env &e, int n) { return mountaincar::load(e, n); }
+    static __device__ __forceinline__ void store(const Env &e, int n, const Local &s) { mountaincar::store(e, n, s); }
+    static __device__ __forceinline__ float act_step(const XpaSmallRolloutArgs &a, const Head &, const Env &e, int n,
+                                                     int K, int T, int32_t t, uint32_t step, const float *z, Local &es,
+                                                     bool *te, bool *tr, float *o) {
+        const int pick = cat_sample_store_at(n, K, T, t, step, z, z[K], a.seed, a.buf_act, a.buf_logp, a.buf_val,
+                                             a.act_in, a.ld_act);
+        return mountaincar::step(e, n, pick, es, te, tr, o);
+    }
+};
+
 // ---- the episode log of the device evaluation (K32E, xpa_eval_post; layout: include/xuanpolicy_amd.h) ----------------
 constexpr int kLogCount = 0, kLogTarget = 1, kLogDone = 2, kLogSteps = 3, kLogOverflow = 4, kLogHeader = 8;
 // int32 index of the first entry: the header, then the snapshot padded to 16 B
@@ -1206,10 +1252,11 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     extern __shared__ float lds[];
     __shared__ double s_sum[kRoThreads], s_sq[kRoThreads];
     __shared__ double s_red[kRoThreads / 64];
-    __shared__ float s_mean[4], s_var[4];
+    __shared__ float s_mean[ro_r4(E::D)], s_var[ro_r4(E::D)];
     __shared__ float s_obs[256 * E::D];  // the raw observations of the step
     __shared__ float s_rstd;
     constexpr int D = E::D, KO = E::KO;
+    static_assert(D >= 1 && D <= 8, "K32's observation widths");
     const int tid = threadIdx.x;
     const int N = a.n_envs, H1 = a.h1, H2 = a.h2, K = a.k, K1 = a.k + 1, U = a.h1 + a.h2;
     const int T = a.horizon;
@@ -1234,12 +1281,13 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     const int li = lane & 15, lq = lane >> 4;
     constexpr int KK = H0 / 4;
     const int UT = U >> 4;   // unit tiles (4, 6 or 8)
-    float4 w0k[KK];
+    float w0k[KK][D];   // the representation layer's rows 4 kk + q: D x h0 / 4 registers per lane
     float b0k[KK];
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
         const int k = 4 * kk + lq;
-        w0k[kk] = make_float4(a.W0[k * D], a.W0[k * D + 1], a.W0[k * D + 2], D > 3 ? a.W0[k * D + D - 1] : 0.f);
+#pragma unroll
+        for (int d = 0; d < D; ++d) w0k[kk][d] = a.W0[k * D + d];
         b0k[kk] = a.b0[k];
     }
     float bw[2][KK], b12[2], wo[2][KO];
@@ -1294,7 +1342,8 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     } while (0)
     __syncthreads();
     if (a.stamps && tid == 0) st_prev = st_t0 = (int64_t)__builtin_amdgcn_s_memtime();
-    // rms_partials_kernel<., 256>'s row groups at dim D (64; at dim 3, 85: thread 255 belongs to no group)
+    // rms_partials_kernel<., 256>'s row groups at dim D (64 at dim 4, 42 at 6, 32 at 8; at dim 3, 85: thread 255
+    // belongs to no group; at 6, threads 252 .. 255)
     constexpr int kGroups = kRoThreads / D;
     for (int s = 0; s < a.steps; ++s) {
         const bool last = t == T - 1;
@@ -1372,19 +1421,26 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
         // (c)-(e) the forward, one 16-row tile of envs at a time
         for (int r0 = 0; r0 < N; r0 += 16) {
             const int ra = r0 + li < N ? r0 + li : N - 1;   // this lane's A row (rows past N: results unused)
-            float4 y;
-            if (D == 4)
-                y = *reinterpret_cast<const float4 *>(sy + ra * D);
-            else
-                y = make_float4(sy[ra * D], sy[ra * D + 1], sy[ra * D + 2], 0.f);
+            float y[D];   // the lane's normalised row (16-B LDS reads where the row pitch keeps them aligned)
+            if constexpr (D % 4 == 0) {
+#pragma unroll
+                for (int d = 0; d < D; d += 4) {
+                    const float4 y4 = *reinterpret_cast<const float4 *>(sy + ra * D + d);
+                    y[d] = y4.x;
+                    y[d + 1] = y4.y;
+                    y[d + 2] = y4.z;
+                    y[d + 3] = y4.w;
+                }
+            } else {
+#pragma unroll
+                for (int d = 0; d < D; ++d) y[d] = sy[ra * D + d];
+            }
             float av[KK];
 #pragma unroll
             for (int kk = 0; kk < KK; ++kk) {
                 float z = b0k[kk];
-                z = fmaf(w0k[kk].x, y.x, z);
-                z = fmaf(w0k[kk].y, y.y, z);
-                z = fmaf(w0k[kk].z, y.z, z);
-                if (D == 4) z = fmaf(w0k[kk].w, y.w, z);
+#pragma unroll
+                for (int d = 0; d < D; ++d) z = fmaf(w0k[kk][d], y[d], z);   // ascending d
                 av[kk] = ro_act<ACT>(z, a.slope);
             }
             ro_f32x4 acc[2];
@@ -2117,6 +2173,14 @@ XPA_API int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *a, const float
     return small_rollout_launch<RoPendulumGauss>(a, 1, RoPendulumGauss::Head{logstd, act_clip}, stream);
 }
 
+XPA_API int xpa_small_rollout_acrobot(const XpaSmallRolloutArgs *a, xpa_stream_t stream) {
+    return small_rollout_launch<RoAcrobotCat>(a, 3, RoAcrobotCat::Head{}, stream);
+}
+
+XPA_API int xpa_small_rollout_mountaincar(const XpaSmallRolloutArgs *a, xpa_stream_t stream) {
+    return small_rollout_launch<RoMountainCarCat>(a, 3, RoMountainCarCat::Head{}, stream);
+}
+
 // ---- device evaluation: K32E and the generic tier's per-step log writer ---------------------------------------------
 XPA_API int64_t xpa_eval_log_ints(int64_t capacity, int64_t snap_dim) {
     if (capacity <= 0 || capacity > 0x7fffffff || snap_dim < 0) return -1;
@@ -2133,6 +2197,17 @@ XPA_API int xpa_small_eval_pendulum(const XpaSmallRolloutArgs *a, const float *l
     if (!logstd || !(act_clip > 0.f)) return (int)hipErrorInvalidValue;
     return small_eval_launch<RoPendulumGauss>(a, 1, RoPendulumGauss::Head{logstd, act_clip}, log, capacity, snap_dim,
                                               scratch, stream);
+}
+
+XPA_API int xpa_small_eval_acrobot(const XpaSmallRolloutArgs *a, int32_t *log, int64_t capacity, int64_t snap_dim,
+                                   float *scratch, xpa_stream_t stream) {
+    return small_eval_launch<RoAcrobotCat>(a, 3, RoAcrobotCat::Head{}, log, capacity, snap_dim, scratch, stream);
+}
+
+XPA_API int xpa_small_eval_mountaincar(const XpaSmallRolloutArgs *a, int32_t *log, int64_t capacity, int64_t snap_dim,
+                                       float *scratch, xpa_stream_t stream) {
+    return small_eval_launch<RoMountainCarCat>(a, 3, RoMountainCarCat::Head{}, log, capacity, snap_dim, scratch,
+                                               stream);
 }
 
 XPA_API int xpa_eval_post(int32_t *log, int64_t capacity, int64_t snap_dim, int64_t n_envs, const uint8_t *term,

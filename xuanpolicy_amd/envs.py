@@ -491,3 +491,159 @@ class PendulumVecEnv:
 
     def close(self):
         pass
+
+
+# ---- Acrobot-v1 and MountainCar-v0 (the reference's configs/ppo|a2c/classic_control/{Acrobot-v1,MountainCar-v0}.yaml) --
+SALT_ACROBOT = 0xAC20B075
+SALT_MOUNTAINCAR = 0x30CA2005
+
+
+def acrobot_reset_states(seed, env_ids, episodes):
+    """[n, 4] f64 (th1, th2, thdot1, thdot2), each 0.2 u - 0.1 from the counter hash (f32-exact uniforms, then f64), as
+    K18A draws them."""
+    e = np.asarray(env_ids, np.uint32)[:, None]
+    ep = np.asarray(episodes, np.uint32)[:, None]
+    d = np.arange(4, dtype=np.uint32)[None, :]
+    return 0.2 * _u01(_hash4(seed ^ SALT_ACROBOT, e, ep, d)).astype(np.float64) - 0.1
+
+
+def mountaincar_reset_states(seed, env_ids, episodes):
+    """[n, 2] f64 (position, velocity) = (0.2 u - 0.6, 0) from the counter hash (f32-exact uniform, then f64), as K18M
+    draws them."""
+    e = np.asarray(env_ids, np.uint32)
+    ep = np.asarray(episodes, np.uint32)
+    p = 0.2 * _u01(_hash4(seed ^ SALT_MOUNTAINCAR, e, ep, np.uint32(0))).astype(np.float64) - 0.6
+    return np.stack([p, np.zeros_like(p)], axis=1)
+
+
+class _Discrete3VecEnv:
+    """What AcrobotVecEnv and MountainCarVecEnv share: n_envs envs resident on one GPU with an f64 state, f32
+    observations, Discrete(3) actions read from the one-hot env input [N, 3] the Categorical rollout kernels write, and
+    a step kernel of K18's contract.  Same interface as CartPoleVecEnv.  A subclass names its kind, step entry point,
+    state width, spaces, default time limit, hashed reset states and their observation."""
+
+    def __init__(self, n_envs, seed=1, max_episode_steps=None, device=None, shard=0):
+        self.num_envs, self.seed = int(n_envs), int(seed)
+        self.max_episode_steps = int(self.TIME_LIMIT if max_episode_steps is None else max_episode_steps)
+        self.max_episode_length = self.max_episode_steps
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.shard = int(shard)
+        self.noise_seed = (self.seed ^ ((0x9E3779B9 * self.shard) & 0xFFFFFFFF)) & 0xFFFFFFFF
+        self.observation_space = self._observation_space()
+        self.action_space = _Discrete(3)
+        dev, N, D = self.device, self.num_envs, self.observation_space.shape[0]
+        self.state = torch.zeros((N, self.STATE_DIM), dtype=torch.float64, device=dev)
+        self._obs = torch.zeros((N, D), dtype=torch.float32, device=dev)
+        self._act = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+        self.final_obs = torch.zeros((N, D), dtype=torch.float32, device=dev)
+        self.rew = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.term = torch.zeros((N,), dtype=torch.uint8, device=dev)
+        self.trunc = torch.zeros((N,), dtype=torch.uint8, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.ep_step, self.ep_index, self.ep_last_len = (torch.zeros((N,), **i32) for _ in range(3))
+        self.ep_score = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.ep_last_score = torch.zeros((N,), dtype=torch.float32, device=dev)
+        self.reset()
+
+    @property
+    def obs(self):
+        return self._obs
+
+    @property
+    def act_in(self):
+        """Env action input [N, 3]: the one-hot of the sampled action (K3 / K14 / K32 write it)."""
+        return self._act
+
+    @property
+    def buf_obs(self):
+        return self._obs
+
+    def reset(self):
+        self.resets = getattr(self, "resets", 0) + 1   # agents re-arm a folded obs-RMS merge (K8R)
+        s0 = self.reset_states(self.noise_seed, np.arange(self.num_envs), np.zeros(self.num_envs))
+        self.state.copy_(torch.as_tensor(s0, device=self.device))
+        self._obs.copy_(torch.as_tensor(self.obs_of_reset(s0), device=self.device))
+        for t in (self.ep_step, self.ep_index, self.ep_score, self.ep_last_score, self.ep_last_len, self.rew,
+                  self.term, self.trunc, self._act):
+            t.zero_()
+        return self._obs.clone(), [{} for _ in range(self.num_envs)]
+
+    def fusable_with_policy_step(self, dist):
+        return False
+
+    def step_device(self):
+        _lib.call(getattr(ops.lib(), self.STEP), self.num_envs, ops._p(self._act), self._act.stride(0),
+                  ops._p(self.state), ops._p(self._obs), self._obs.stride(0), ops._p(self.final_obs), ops._p(self.rew),
+                  ops._p(self.term), ops._p(self.trunc), ops._p(self.ep_step), ops._p(self.ep_index),
+                  ops._p(self.ep_score), ops._p(self.ep_last_score), ops._p(self.ep_last_len), self.noise_seed,
+                  self.max_episode_steps, ops._stream(self.device))
+
+    def step(self, actions):
+        """VecEnv contract (gym_vec_env.py:201-212): host copies of (obs, rew, term, trunc, infos)."""
+        a = torch.as_tensor(np.asarray(actions) if not isinstance(actions, torch.Tensor) else actions,
+                            device=self.device).long().reshape(-1, 1)
+        self._act.zero_()
+        self._act.scatter_(1, a, 1.0)
+        self.step_device()
+        obs = self.final_obs.cpu().numpy()
+        rew = self.rew.cpu().numpy()
+        term = self.term.cpu().numpy().astype(bool)
+        trunc = self.trunc.cpu().numpy().astype(bool)
+        nxt = self._obs.cpu().numpy()
+        lens, scores = self.ep_step.cpu().numpy(), self.ep_score.cpu().numpy()
+        last_len, last_score = self.ep_last_len.cpu().numpy(), self.ep_last_score.cpu().numpy()
+        infos = []
+        for i in range(self.num_envs):
+            done = term[i] or trunc[i]
+            info = {"episode_step": int(last_len[i] if done else lens[i]),
+                    "episode_score": float(last_score[i] if done else scores[i])}
+            if done:
+                info["reset_obs"] = nxt[i].copy()
+            infos.append(info)
+        return obs, rew, term, trunc, infos
+
+    def close(self):
+        pass
+
+
+class AcrobotVecEnv(_Discrete3VecEnv):
+    """n_envs Acrobot-v1 envs (K18A xpa_acrobot_step, csrc/classic.hip): the equations of the header's K18A comment
+    ("book" dynamics, one RK4 step of dt 0.2) with TimeLimit(500), f64 state (th1, th2, thdot1, thdot2), f32
+    observations (cos th1, sin th1, cos th2, sin th2, thdot1, thdot2), torque action - 1.  CPU checker:
+    tests/_acrobot_ref.py."""
+    kind = "acrobot"   # rollout_plan: K32 steps this env inside the fused rollout step
+    STEP, STATE_DIM, TIME_LIMIT = "xpa_acrobot_step", 4, 500
+    MAX_VEL_1, MAX_VEL_2 = 4 * np.pi, 9 * np.pi
+    reset_states = staticmethod(acrobot_reset_states)
+
+    def _observation_space(self):
+        box = _Box((6,))
+        box.high = np.array([1.0, 1.0, 1.0, 1.0, self.MAX_VEL_1, self.MAX_VEL_2], np.float32)
+        box.low = -box.high
+        return box
+
+    @staticmethod
+    def obs_of_reset(s):
+        return np.stack([np.cos(s[:, 0]), np.sin(s[:, 0]), np.cos(s[:, 1]), np.sin(s[:, 1]), s[:, 2], s[:, 3]],
+                        axis=1).astype(np.float32)
+
+
+class MountainCarVecEnv(_Discrete3VecEnv):
+    """n_envs MountainCar-v0 envs behind the reference's MountainCar wrapper (K18M xpa_mountaincar_step,
+    csrc/classic.hip): the equations of the header's K18M comment with TimeLimit(200), f64 state (position, velocity),
+    and the observation the wrapper gives (gym_env.py:52-85) — the last four f32 (position, velocity) frames, oldest
+    first, the reset frame four times after a reset.  The stack lives in `obs` itself.  CPU checker:
+    tests/_mountaincar_ref.py."""
+    kind = "mountaincar"   # rollout_plan: K32 steps this env inside the fused rollout step
+    STEP, STATE_DIM, TIME_LIMIT = "xpa_mountaincar_step", 2, 200
+    reset_states = staticmethod(mountaincar_reset_states)
+
+    def _observation_space(self):
+        box = _Box((8,))
+        box.low = np.array([-1.2, -0.07] * 4, np.float32)
+        box.high = np.array([0.6, 0.07] * 4, np.float32)
+        return box
+
+    @staticmethod
+    def obs_of_reset(s):
+        return np.tile(s.astype(np.float32), (1, 4))

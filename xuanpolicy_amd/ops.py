@@ -1602,15 +1602,14 @@ def eval_post(log, capacity, snap_dim, term, trunc, ep_last_score, ep_last_len, 
 
 
 def small_eval(entry, args, log, capacity, snap_dim, scratch, logstd=None, act_clip=1.0):
-    """K32E (xpa_small_eval_cartpole / _pendulum): up to args.steps evaluation steps in one launch, the finished
+    """K32E (xpa_small_eval_<env>): up to args.steps evaluation steps in one launch, the finished
     episodes into the log.  args: an XpaSmallRolloutArgs whose seed / cursor are the evaluation's; scratch f32
     [3 * n_envs]."""
     _eval_log_dims(log, capacity, snap_dim)
     _req(scratch, "scratch", torch.float32, (3 * int(args.n_envs),))
     s = _stream(log.device)
-    if entry == "xpa_small_eval_cartpole":
-        _lib.call(lib().xpa_small_eval_cartpole, ctypes.byref(args), _p(log), int(capacity), int(snap_dim),
-                  _p(scratch), s)
+    if entry in ("xpa_small_eval_cartpole", "xpa_small_eval_acrobot", "xpa_small_eval_mountaincar"):
+        _lib.call(getattr(lib(), entry), ctypes.byref(args), _p(log), int(capacity), int(snap_dim), _p(scratch), s)
     elif entry == "xpa_small_eval_pendulum":
         _req(logstd, "logstd", torch.float32, (1,))
         _lib.call(lib().xpa_small_eval_pendulum, ctypes.byref(args), _p(logstd), float(act_clip), _p(log),

@@ -47,7 +47,8 @@ class RolloutFacts(NamedTuple):
     global_advnorm: bool
     pending: bool             # host closures (buffer.finish_path) wait for the scan
     # the env
-    env: str                  # "synthbox" | "synthatari" | "cartpole" | "pendulum" | "device" (another one) | "host"
+    env: str                  # "synthbox" | "synthatari" | "cartpole" | "pendulum" | "acrobot" | "mountaincar" |
+                              # "device" (another one) | "host"
     env_fusable: bool         # env.fusable_with_policy_step(dist)
     obs_rows: bool            # env.obs is [N, D] with unit column stride
     # the policy and the learner
@@ -74,10 +75,13 @@ _ENV = {"in-head": (), "synthbox": ("xpa_synthbox_step",), "synthatari": ("xpa_s
         "cartpole": ("xpa_cartpole_step",), "device": (), "host": ()}
 # step_launches' env table: _ENV (whose keys test_rollout_plan_cpu's invariants enumerate over its env kinds) and the
 # device envs added since
-_ENV_STEP = dict(_ENV, pendulum=("xpa_pendulum_step",))
+_ENV_STEP = dict(_ENV, pendulum=("xpa_pendulum_step",), acrobot=("xpa_acrobot_step",),
+                 mountaincar=("xpa_mountaincar_step",))
 # K32's instantiations: (env, the head's distribution) -> (entry point, d_in, head width)
 _K32 = {("cartpole", "categorical"): ("xpa_small_rollout_cartpole", 4, 2),
-        ("pendulum", "gaussian"): ("xpa_small_rollout_pendulum", 3, 1)}
+        ("pendulum", "gaussian"): ("xpa_small_rollout_pendulum", 3, 1),
+        ("acrobot", "categorical"): ("xpa_small_rollout_acrobot", 6, 3),
+        ("mountaincar", "categorical"): ("xpa_small_rollout_mountaincar", 8, 3)}
 _VALUE_HEAD = {"K13": ("xpa_value_head",), "chain": ("xpa_value_head",), "cnn": (), "policy": ()}
 _POST = {"K14F": (), "K8-deferred": ("xpa_rollout_post_deferred_norm",), "K8": ("xpa_rollout_post",)}
 _CLOSE = {None: (), "raw-last": ("xpa_rollout_bootstrap_fixup",), "raw-mid-next": ()}
@@ -97,7 +101,8 @@ class RolloutPlan(NamedTuple):
     value_trunk: str   # the critic-only passes' trunk: "K13" | "chain" | "cnn" | "policy"
     pair: object       # "K40R" | "linear" | None
     head: str          # "K14F" | "K14E" | "K14" | "K3"
-    env: str           # "in-head" | "synthbox" | "synthatari" | "cartpole" | "pendulum" | "device" | "host"
+    env: str           # "in-head" | "synthbox" | "synthatari" | "cartpole" | "pendulum" | "acrobot" | "mountaincar" |
+                       # "device" | "host"
     post: str          # "K14F" | "K8-deferred" | "K8"
     boot: str          # "slots" | "per-step" | "zero"
     mid: object        # A2C's mid-rollout bootstraps: None | "critic" | "next-column" | "slots-from-next"
@@ -147,8 +152,8 @@ def plan_rollout(f):
     sh = None if f.raw_obs else f.shape
     device = f.env != "host"
     collective = f.sync_obs_rms is True and f.world > 1 and f.use_obsnorm
-    # K32: a CartPole (Categorical, 2 actions) or Pendulum (Gaussian, 1 torque) device env with deferred bootstraps, no
-    # per-step collective, the small_policy_layers shape
+    # K32: a CartPole (Categorical, 2 actions), Pendulum (Gaussian, 1 torque), Acrobot or MountainCar (Categorical, 3
+    # actions) device env with deferred bootstraps, no per-step collective, the small_policy_layers shape
     k32 = (f.fused_rollout and f.cuda and (f.env, f.dist) in _K32 and f.defer_boot and not f.raw_obs and not collective
            and f.algo in ("ppo", "a2c") and f.small is not None and f.small_bufs)
     if k32:
@@ -203,7 +208,9 @@ def plan_rollout(f):
 
 # ---- evaluation (agent.test) ------------------------------------------------------------------------------------------
 # K32's evaluation form (K32E): the entry point of each of K32's instantiations
-_K32E = {("cartpole", "categorical"): "xpa_small_eval_cartpole", ("pendulum", "gaussian"): "xpa_small_eval_pendulum"}
+_K32E = {("cartpole", "categorical"): "xpa_small_eval_cartpole", ("pendulum", "gaussian"): "xpa_small_eval_pendulum",
+         ("acrobot", "categorical"): "xpa_small_eval_acrobot",
+         ("mountaincar", "categorical"): "xpa_small_eval_mountaincar"}
 
 
 class EvalFacts(NamedTuple):

@@ -17,7 +17,8 @@ import torch
 import yaml
 
 from . import agents
-from .envs import CartPoleVecEnv, PendulumVecEnv, SynthAtariVecEnv, SynthBoxVecEnv
+from .envs import (AcrobotVecEnv, CartPoleVecEnv, MountainCarVecEnv, PendulumVecEnv, SynthAtariVecEnv,
+                   SynthBoxVecEnv)
 from .policies import (AC_CNN_Atari, ActivationFunctions, Basic_MLP, REGISTRY as REGISTRY_Policy,
                        REGISTRY_Representation)
 
@@ -87,12 +88,19 @@ def make_envs(config, device=None, shard=0):
     if config.env_name == "Classic Control" and str(getattr(config, "env_id", "")) == "Pendulum-v1":
         return PendulumVecEnv(config.parallels, seed=config.seed,
                               max_episode_steps=getattr(config, "max_episode_steps", 200), device=device, shard=shard)
+    if config.env_name == "Classic Control" and str(getattr(config, "env_id", "")) == "Acrobot-v1":
+        return AcrobotVecEnv(config.parallels, seed=config.seed,
+                             max_episode_steps=getattr(config, "max_episode_steps", 500), device=device, shard=shard)
+    if config.env_name == "Classic Control" and str(getattr(config, "env_id", "")) == "MountainCar-v0":
+        return MountainCarVecEnv(config.parallels, seed=config.seed,
+                                 max_episode_steps=getattr(config, "max_episode_steps", 200), device=device,
+                                 shard=shard)
     if config.env_name == "Atari" and str(getattr(config, "env_id", "")).startswith("SynthAtari"):
         return SynthAtariVecEnv(config.parallels, getattr(config, "n_actions", 6), seed=config.seed,
                                 max_episode_steps=getattr(config, "max_episode_steps", 27000), device=device,
                                 shard=shard)
     raise NotImplementedError("env_name %r: only the device-resident SynthBox / SynthAtari / CartPole-v1 / "
-                              "Pendulum-v1 envs are built in; pass "
+                              "Pendulum-v1 / Acrobot-v1 / MountainCar-v0 envs are built in; pass "
                               "any VecEnv with the reference's step contract to the agent directly" % config.env_name)
 
 
@@ -176,6 +184,23 @@ def build_pendulum_ppo(n_envs=8, n_steps=128, hidden=64, seed=1, device="cuda:0"
     """PPO-Clip (or agent="A2C") on the device Pendulum-v1 (<method>/classic_control/Pendulum-v1.yaml keys) at C1's
     shape: 8 envs x 128 steps, [64] hidden layers for the representation, actor and critic, Gaussian heads."""
     cfg = get_arguments("ppo" if agent == "PPO_Clip" else "a2c", "classic_control", "Pendulum-v1")
+    cfg.agent = agent
+    cfg.parallels, cfg.n_steps, cfg.seed = n_envs, n_steps, seed
+    cfg.representation_hidden_size = cfg.actor_hidden_size = cfg.critic_hidden_size = [hidden]
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    torch.manual_seed(seed)
+    return build_agent(cfg, device)
+
+
+def build_classic_control(env_id, agent="PPO_Clip", n_envs=8, n_steps=128, hidden=64, seed=1, device="cuda:0",
+                          **overrides):
+    """PPO-Clip (or agent="A2C") on a device classic-control env by its id (<method>/classic_control/<env_id>.yaml
+    keys: CartPole-v1 for PPO, Pendulum-v1, Acrobot-v1, MountainCar-v0) at C1's shape: 8 envs x 128 steps, [hidden]
+    layers for the representation, actor and critic — the shape the one-launch small path takes."""
+    cfg = get_arguments("ppo" if agent == "PPO_Clip" else "a2c", "classic_control", env_id)
+    if getattr(cfg, "env_name", None) != "Classic Control" or getattr(cfg, "env_id", None) != env_id:
+        raise ValueError("no %s config for the classic-control env %r" % (agent, env_id))
     cfg.agent = agent
     cfg.parallels, cfg.n_steps, cfg.seed = n_envs, n_steps, seed
     cfg.representation_hidden_size = cfg.actor_hidden_size = cfg.critic_hidden_size = [hidden]
