@@ -291,7 +291,10 @@ int xpa_mountaincar_step(int64_t n_envs, const float *act_in, int64_t ld_act, do
  * but the forward is the multi-kernel path's arithmetic bit for bit (the forward's dot products are f32 fma chains
  * in a fixed order).  Replaces ~10 launches per env step of the C1 configuration.  Limits: n_envs <= 256,
  * d_in == 4 (CartPole), h0 in {32, 64}, h1, h2 in {32, 64}, k == 2, xpa_small_rollout_lds_floats(...) <= 16384.
- * use_obsnorm = 0: the statistics are read, not updated (the agent's use_obsnorm False). */
+ * use_obsnorm = 0: the statistics are read, not updated (the agent's use_obsnorm False).
+ * K32W — the same entry points at h0 == h1 == h2 == 128 (no other width beside K32's): the forward keeps one
+ * representation row per thread and four 16-unit tiles of hidden weight rows per wave, and forms h0 of a 16-env tile
+ * once into LDS; every other stage is K32's code.  The evaluation form (xpa_small_eval_*) takes K32's widths only. */
 typedef struct XpaSmallRolloutArgs {
     int n_envs, horizon, steps, d_in, h0, h1, h2, k, act_code, use_obsnorm, n_slots, mask_returns, use_rewnorm;
     int max_episode_steps;
@@ -474,6 +477,11 @@ typedef struct XpaSmallMlpArgs {
     double *loss_part;
 } XpaSmallMlpArgs;
 int64_t xpa_small_mlp_lds_floats(int64_t batch, int64_t d_in, int64_t h0, int64_t h1, int64_t h2, int64_t k);
+/* The one-image form's budget: where xpa_small_mlp_lds_floats(rows per workgroup, ...) > 40704 and rows per workgroup
+ * <= 32 (batch <= 32, or the split form), W1 and W2 go through one LDS image one after the other (forward: the actor's
+ * hidden layer, then the critic's; backward: the two halves of dh0, summed as the resident form sums them) and this
+ * is the limit that holds: xpa_small_mlp_one_image_lds_floats(...) <= 40704 (h0 = h1 = h2 = 128 at d_in <= 32). */
+int64_t xpa_small_mlp_one_image_lds_floats(int64_t batch, int64_t d_in, int64_t h0, int64_t h1, int64_t h2, int64_t k);
 int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t stream);
 /* K30 for a Gaussian head (the same kernel with K2's Gaussian loss stage): args->k is the action dimension A,
  * 1 <= A <= 16, Wa / ba the mu layer, actions float [n_rows, A]; logstd float [A].  The loss stage is

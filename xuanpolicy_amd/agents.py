@@ -39,7 +39,7 @@ from .buffer import DummyOnPolicyBuffer, DummyOnPolicyBuffer_Atari
 from .fused_mlp import FusedActorCritic, Rows, _no_form
 from .learners import A2C_Learner, PerDQN_Learner, PPOCLIP_Learner
 from .policies import policy_discrete, policy_heads, space_shape
-from .rollout_plan import EvalFacts, RolloutFacts, eval_entry, plan_rollout, plan_test
+from .rollout_plan import K32_DRIVERS, EvalFacts, RolloutFacts, eval_entry, plan_rollout, plan_test
 
 FLOAT_MAX = 3.0e38
 # test_device's action stream: the counter hash keyed by seed ^ EVAL_SALT and a step counter of its own
@@ -340,7 +340,7 @@ class _OnPolicyAgent:
                *[p.data_ptr() for p in self._params])
         if key != self._plan_key:
             self._plan = plan_rollout(self._facts(fm, F, obs))
-            self._k32 = self._build_small_rollout() if self._plan.driver == "K32" else None
+            self._k32 = self._build_small_rollout() if self._plan.driver in K32_DRIVERS else None
             self._plan_key = key
         return self._plan
 
@@ -504,7 +504,7 @@ class _OnPolicyAgent:
         self._rms_c0 = None
 
     def _build_small_rollout(self):
-        """K32's argument block (xpa_small_rollout_<env>) for a plan whose driver is K32; plan() rebuilds
+        """K32's argument block (xpa_small_rollout_<env>) for a plan whose driver is K32 / K32W; plan() rebuilds
         it when the parameters are re-homed (the block holds their pointers)."""
         env, mem = self.envs, self.memory
         (l0, l1, la, l2, lc), code, slope, self._k32_logstd = self.learner.small_policy_layers()
@@ -556,7 +556,7 @@ class _OnPolicyAgent:
         env = self.envs
         x = env.obs
         plan = self.plan(x)
-        if plan.driver == "K32":
+        if plan.driver in K32_DRIVERS:
             self._small_rollout_launch(1)
             return
         if plan.rms is not None:
@@ -581,7 +581,7 @@ class _OnPolicyAgent:
     def _rollout_step_graph(self):
         """The device env step captured once into a hipGraph and replayed: every per-step argument
         (buffer column, RNG step) lives in the device cursor, so the same graph serves all steps."""
-        if self.plan().driver == "K32":   # one launch per step: nothing to capture
+        if self.plan().driver in K32_DRIVERS:   # one launch per step: nothing to capture
             self._rollout_step_device()
             return
         key = tuple(p.data_ptr() for p in self._params)
@@ -602,7 +602,7 @@ class _OnPolicyAgent:
         """k consecutive device env steps captured into ONE hipGraph (k x 5 kernels) and replayed as a unit: a
         per-step replay leaves the GPU idle ~8 us between graphs while the host launches the next (r02 trace:
         127 such gaps = 1.0 ms of a 72 ms iteration).  Same replay invariance as _rollout_step_graph."""
-        if self.plan().driver == "K32":   # the k steps as one K32 launch
+        if self.plan().driver in K32_DRIVERS:   # the k steps as one K32 launch
             self._small_rollout_launch(k)
             return k
         key = (k,) + tuple(p.data_ptr() for p in self._params)

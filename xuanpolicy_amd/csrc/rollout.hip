@@ -1063,19 +1063,24 @@ constexpr int kRoLdsMax = 16384;  // floats of dynamic LDS (64 KiB: no attribute
 __host__ __device__ constexpr int ro_r4(int x) { return (x + 3) & ~3; }
 
 struct RoLayout {
-    int sy, sz, sbo, total;
+    int sy, sz, sbo, sh, total;
 };
-// sy: the normalised observations [N][D]; sz: the output layers' partial sums [wave][N][K + 1]; sbo: biases
+constexpr int kRoWide = 128;           // K32W's width: h0 == h1 == h2 == 128
+constexpr int kRoWideQ = 32 + 4;       // K32W's h0 tile: floats per (row, k & 3) group (32 + a 16-B pad)
+constexpr int kRoWideP = 4 * kRoWideQ;  // ... and per row
+// sy: the normalised observations [N][D]; sz: the output layers' partial sums [wave][N][K + 1]; sbo: biases; sh
+// (K32W only): h0 of one 16-env tile, element (row, k) at row kRoWideP + (k & 3) kRoWideQ + (k >> 2)
 __host__ __device__ inline RoLayout ro_layout(int N, int D, int H0, int H1, int H2, int K) {
     RoLayout l;
     const int K1 = K + 1;
-    (void)H0;
     (void)H1;
     (void)H2;
     l.sy = 0;
     l.sz = ro_r4(N * D);
     l.sbo = ro_r4(l.sz + 4 * N * K1);
     l.total = ro_r4(l.sbo + K1);
+    l.sh = l.total;
+    if (H0 == kRoWide) l.total += 16 * kRoWideP;
     return l;
 }
 
@@ -1277,22 +1282,28 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
     // launch); lane (q, i) forms the A operand itself — h0[row i][4 kk + q] of the representation layer, from the
     // normalised row in LDS — so h0 never goes through LDS; the output layers are per-lane partial dot products over
     // the lane's units, summed over the 16 lanes of a DPP row and then over the waves (LDS, fixed order).
+    // WIDE (K32W, h0 = h1 = h2 = 128): that layout would take D x 32 + 2 x 32 registers for the first layer alone and
+    // form every h0 element once per wave.  Here wave w owns the four unit tiles w, w + 4, w + 8, w + 12 (128
+    // registers of weight rows); thread t keeps only row t & 127 of the representation layer, the 16-env tile's h0 is
+    // formed once by the whole block into LDS (sh, stored so that a lane's A operands of four k-steps are one 16-B
+    // read) and every wave takes its A operands from there.
+    constexpr bool WIDE = H0 == kRoWide;
     const int wave = tid >> 6, lane = tid & 63;
     const int li = lane & 15, lq = lane >> 4;
-    constexpr int KK = H0 / 4;
-    const int UT = U >> 4;   // unit tiles (4, 6 or 8)
-    float w0k[KK][D];   // the representation layer's rows 4 kk + q: D x h0 / 4 registers per lane
-    float b0k[KK];
+    constexpr int KK = H0 / 4, J = WIDE ? 4 : 2, KW = WIDE ? 1 : KK;
+    const int UT = U >> 4;   // unit tiles (4, 6 or 8; WIDE: 16)
+    float w0k[KW][D];   // the representation layer's rows 4 kk + q: D x h0 / 4 registers per lane (WIDE: row t & 127)
+    float b0k[KW];
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-        const int k = 4 * kk + lq;
+    for (int kk = 0; kk < KW; ++kk) {
+        const int k = WIDE ? (tid & (kRoWide - 1)) : 4 * kk + lq;
 #pragma unroll
         for (int d = 0; d < D; ++d) w0k[kk][d] = a.W0[k * D + d];
         b0k[kk] = a.b0[k];
     }
-    float bw[2][KK], b12[2], wo[2][KO];
+    float bw[J][KK], b12[J], wo[J][KO];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < J; ++j) {
         const int tile = wave + 4 * j;
         const bool tok = tile < UT;
         const int u = tok ? 16 * tile + li : 0;
@@ -1420,36 +1431,67 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
         XPA_RO_STAMP(1);
         // (c)-(e) the forward, one 16-row tile of envs at a time
         for (int r0 = 0; r0 < N; r0 += 16) {
-            const int ra = r0 + li < N ? r0 + li : N - 1;   // this lane's A row (rows past N: results unused)
-            float y[D];   // the lane's normalised row (16-B LDS reads where the row pitch keeps them aligned)
-            if constexpr (D % 4 == 0) {
+            ro_f32x4 acc[J];
 #pragma unroll
-                for (int d = 0; d < D; d += 4) {
-                    const float4 y4 = *reinterpret_cast<const float4 *>(sy + ra * D + d);
-                    y[d] = y4.x;
-                    y[d + 1] = y4.y;
-                    y[d + 2] = y4.z;
-                    y[d + 3] = y4.w;
+            for (int j = 0; j < J; ++j) acc[j] = ro_f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (WIDE) {
+                float *sh = lds + L.sh;
+                if (r0 > 0) __syncthreads();   // the previous tile's A operands are read
+                // h0 of the tile: thread t forms unit t & 127 of the rows (t >> 7) + 2 i (rows past N: row N - 1's,
+                // results unused)
+                const int u = tid & (kRoWide - 1), rh = tid >> 7;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int row = rh + 2 * i;
+                    const float *yr = sy + (r0 + row < N ? r0 + row : N - 1) * D;
+                    float z = b0k[0];
+#pragma unroll
+                    for (int d = 0; d < D; ++d) z = fmaf(w0k[0][d], yr[d], z);   // ascending d
+                    sh[row * kRoWideP + (u & 3) * kRoWideQ + (u >> 2)] = ro_act<ACT>(z, a.slope);
+                }
+                __syncthreads();
+                // lane (q, i)'s A operand of k-step kk is h0[row i][4 kk + q] = sh[i][q][kk]
+                const float *ap = sh + li * kRoWideP + lq * kRoWideQ;
+#pragma unroll
+                for (int k4 = 0; k4 < KK; k4 += 4) {
+                    const float4 a4 = *reinterpret_cast<const float4 *>(ap + k4);
+                    const float av[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+#pragma unroll
+                        for (int j = 0; j < J; ++j)
+                            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], bw[j][k4 + c], acc[j], 0, 0, 0);
                 }
             } else {
+                const int ra = r0 + li < N ? r0 + li : N - 1;   // this lane's A row (rows past N: results unused)
+                float y[D];   // the lane's normalised row (16-B LDS reads where the row pitch keeps them aligned)
+                if constexpr (D % 4 == 0) {
 #pragma unroll
-                for (int d = 0; d < D; ++d) y[d] = sy[ra * D + d];
+                    for (int d = 0; d < D; d += 4) {
+                        const float4 y4 = *reinterpret_cast<const float4 *>(sy + ra * D + d);
+                        y[d] = y4.x;
+                        y[d + 1] = y4.y;
+                        y[d + 2] = y4.z;
+                        y[d + 3] = y4.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) y[d] = sy[ra * D + d];
+                }
+                float av[KK];
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    float z = b0k[kk];
+#pragma unroll
+                    for (int d = 0; d < D; ++d) z = fmaf(w0k[kk][d], y[d], z);   // ascending d
+                    av[kk] = ro_act<ACT>(z, a.slope);
+                }
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+                    for (int j = 0; j < J; ++j)
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bw[j][kk], acc[j], 0, 0, 0);
             }
-            float av[KK];
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk) {
-                float z = b0k[kk];
-#pragma unroll
-                for (int d = 0; d < D; ++d) z = fmaf(w0k[kk][d], y[d], z);   // ascending d
-                av[kk] = ro_act<ACT>(z, a.slope);
-            }
-            ro_f32x4 acc[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[j] = ro_f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bw[j][kk], acc[j], 0, 0, 0);
             // D element r of lane (q, i): row r0 + 4 q + r, unit 16 tile + i
             float part[4][KO];
 #pragma unroll
@@ -1458,7 +1500,7 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
                 for (int o = 0; o < KO; ++o) {
                     float pv = 0.f;
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) pv = fmaf(wo[j][o], ro_act<ACT>(acc[j][r] + b12[j], a.slope), pv);
+                    for (int j = 0; j < J; ++j) pv = fmaf(wo[j][o], ro_act<ACT>(acc[j][r] + b12[j], a.slope), pv);
                     part[r][o] = ro_row_sum16(pv);
                 }
             if (li == 0)
@@ -2079,13 +2121,20 @@ XPA_API int xpa_rollout_step_synthbox(
 // ---- K32 -------------------------------------------------------------------------------------------
 XPA_API int64_t xpa_small_rollout_lds_floats(int64_t n_envs, int64_t d_in, int64_t h0, int64_t h1, int64_t h2,
                                              int64_t k) {
-    if (n_envs <= 0 || n_envs > 256 || d_in <= 0 || d_in > 32 || h0 <= 0 || h0 > 64 || h1 <= 0 || h1 > 64 ||
-        h2 <= 0 || h2 > 64 || k <= 0 || k > 16)
+    const bool wide = h0 == kRoWide && h1 == kRoWide && h2 == kRoWide;   // K32W
+    if (n_envs <= 0 || n_envs > 256 || d_in <= 0 || d_in > 32 || k <= 0 || k > 16 ||
+        (!wide && (h0 <= 0 || h0 > 64 || h1 <= 0 || h1 > 64 || h2 <= 0 || h2 > 64)))
         return -1;
     return ro_layout((int)n_envs, (int)d_in, (int)h0, (int)h1, (int)h2, (int)k).total;
 }
 
 namespace {
+// K32's widths (each of 32, 64) or K32W's (all 128)
+bool ro_widths_ok(int64_t h0, int64_t h1, int64_t h2) {
+    if (h0 == kRoWide) return h1 == kRoWide && h2 == kRoWide;
+    return (h0 == 32 || h0 == 64) && (h1 == 32 || h1 == 64) && (h2 == 32 || h2 == 64);
+}
+
 // The checks and the launch shared by K32's entry points; E: the instantiation's env / head pair, k its head width.
 // K32E's checks and launch: only what the evaluation form dereferences is required (the training-only pointers of
 // XpaSmallRolloutArgs may be null); horizon 1 and the sampler's three stores into scratch [3 * n_envs]
@@ -2132,7 +2181,7 @@ int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd,
 template <class E>
 int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head hd, xpa_stream_t stream) {
     if (!a || a->n_envs <= 0 || a->n_envs > 256 || a->horizon <= 0 || a->steps <= 0 || a->d_in != E::D ||
-        (a->h0 != 32 && a->h0 != 64) || (a->h1 != 32 && a->h1 != 64) || (a->h2 != 32 && a->h2 != 64) || a->k != k ||
+        !ro_widths_ok(a->h0, a->h1, a->h2) || a->k != k ||
         a->act_code < 0 || a->act_code > 2 || a->n_slots < 1 || a->n_slots > a->horizon || a->max_episode_steps <= 0 ||
         a->ld_norm < a->d_in || a->ld_obs < E::D || a->ld_act < k || a->ld_boot < a->d_in)
         return (int)hipErrorInvalidValue;
@@ -2149,7 +2198,11 @@ int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head h
     hipStream_t s = (hipStream_t)stream;
 #define XPA_RO_LAUNCH(ACT, H0) \
     hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a, hd, RoNoEval{})
-    if (a->h0 == 64) {
+    if (a->h0 == kRoWide) {   // K32W
+        if (a->act_code == 0) XPA_RO_LAUNCH(0, kRoWide);
+        else if (a->act_code == 1) XPA_RO_LAUNCH(1, kRoWide);
+        else XPA_RO_LAUNCH(2, kRoWide);
+    } else if (a->h0 == 64) {
         if (a->act_code == 0) XPA_RO_LAUNCH(0, 64);
         else if (a->act_code == 1) XPA_RO_LAUNCH(1, 64);
         else XPA_RO_LAUNCH(2, 64);

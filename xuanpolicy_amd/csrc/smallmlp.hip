@@ -90,7 +90,11 @@ struct SmGauss {
 
 // GAUSS: a.k is the action dimension A, Wa / ba the mu layer, actions [n_rows, A]; the loss stage is
 // policy_loss_gauss_kernel's per-row arithmetic (loss.hip) and d logstd joins the gradient.
-template <int ACT, int ALGO, bool GAUSS>
+// ONE (at most 32 rows per workgroup, where the two hidden-weight images do not fit: 128-wide layers): W1 and W2 go
+// through ONE LDS image, one after the other — transposed for the actor's and then the critic's hidden layer in the
+// forward, row-major for the two halves of dh0 = dh1 W1 + dh2 W2 in the backward (the W1 half kept in the tile's
+// accumulator registers while W2 is staged, then summed as the resident form sums them).
+template <int ACT, int ALGO, bool GAUSS, bool ONE = false>
 __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmallMlpArgs a, SmGauss hd) {
     __shared__ __attribute__((aligned(16))) float lds[kSmLds];
     __shared__ double s_red[kSmWaves * 6];
@@ -123,8 +127,9 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     // W1T / W2T: row stride H1 + 1 / H2 + 1, so that the coalesced (source-order) staging writes are conflict-free
     const int H1P = H1 + 1, H2P = H2 + 1;
     float *W1T = W0T + DP * H0;            // [H0][H1P], after the forward W1 row-major [H1][H0]
-    float *W2T = W1T + H0 * H1P;           // [H0][H2P], after the forward W2 row-major [H2][H0] (at W1T + H1 H0)
-    float *WaT = W2T + H0 * H2P;           // [H1][KP]
+    // ONE: W2T is W1T's image (sized for the wider of the two)
+    float *W2T = ONE ? W1T : W1T + H0 * H1P;   // [H0][H2P], after the forward W2 row-major [H2][H0] (at W1T + H1 H0)
+    float *WaT = ONE ? W1T + H0 * max(H1P, H2P) : W2T + H0 * H2P;   // [H1][KP]
     float *Wcv = WaT + H1 * KP;            // [H2]
     float *b0s = Wcv + H2, *b1s = b0s + H0, *b2s = b1s + H1, *bas = b2s + H2, *bcs = bas + KP;
     float *rowf = bcs + 4;                 // action, old_logp, adv, ret: [4][BP]
@@ -140,8 +145,8 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     }
     const int n0 = H0 * D, na = K * H1, nm = n0 + na + H2 + H0 + H1 + H2 + K + 1;   // W0 | Wa | Wc | biases
     const int nw1 = H0 * H1, nw2 = H0 * H2;
-    const bool fast = nm <= 2 * kSmThreads && nw1 <= 8 * kSmThreads && nw2 <= 8 * kSmThreads && BP <= kSmThreads &&
-                      Btot <= kSmThreads;
+    const bool fast = !ONE && nm <= 2 * kSmThreads && nw1 <= 8 * kSmThreads && nw2 <= 8 * kSmThreads &&
+                      BP <= kSmThreads && Btot <= kSmThreads;
     float adv_all = 0.f;   // split form: the advantage of minibatch row t (the moments are over every row)
     // element e of the small-tensor range: its source (loads) and LDS destination (stores)
     auto msrc_of = [&](int e, int &off) -> const float * {
@@ -268,7 +273,7 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
             }
         };
         stage_T(a.W1, H1, H0, W1T, H1P);
-        stage_T(a.W2, H2, H0, W2T, H2P);
+        if (!ONE) stage_T(a.W2, H2, H0, W2T, H2P);
     }
     double adv_s0 = 0.0, adv_q0 = 0.0;
     for (int b = t; b < BP; b += kSmThreads) {
@@ -354,7 +359,38 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
             h0T[(j0 + li) * S + b0 + sm_row(r)] = sm_act<ACT>(acc[r] + b0s[j0 + li], slope);
     }
     __syncthreads();
-    {
+    if constexpr (ONE) {
+        // the actor's hidden layer from the image (W1), then the image re-staged with W2 for the critic's
+        for (int tl = w; tl < MB * (H1 / 32); tl += kSmWaves) {
+            const int b0 = 32 * (tl % MB), j0 = 32 * (tl / MB);
+            const f32x16 acc = sm_tile(h0T + b0, 1, S, 32, W1T + j0, H1P, 1, 32, H0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                h1T[(j0 + li) * S + b0 + sm_row(r)] = sm_act<ACT>(acc[r] + b1s[j0 + li], slope);
+        }
+        __syncthreads();
+        for (int e0 = t; e0 < H2 * H0; e0 += 8 * kSmThreads) {   // stage_T's walk (source order, odd row stride)
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + u * kSmThreads;
+                v[u] = e < H2 * H0 ? a.W2[e] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + u * kSmThreads;
+                if (e < H2 * H0) W2T[(e % H0) * H2P + e / H0] = v[u];
+            }
+        }
+        __syncthreads();
+        for (int tl = w; tl < MB * (H2 / 32); tl += kSmWaves) {
+            const int b0 = 32 * (tl % MB), j0 = 32 * (tl / MB);
+            const f32x16 acc = sm_tile(h0T + b0, 1, S, 32, W2T + j0, H2P, 1, 32, H0);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                h2T[(j0 + li) * S + b0 + sm_row(r)] = sm_act<ACT>(acc[r] + b2s[j0 + li], slope);
+        }
+    } else {
         const int n1 = MB * (H1 / 32), n2 = MB * (H2 / 32);
         for (int tl = w; tl < n1 + n2; tl += kSmWaves) {
             const bool two = tl >= n1;
@@ -517,7 +553,7 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     // the hidden weights row-major ([j][i], over the transposed forward copies) for dh0: loads issued now, stored
     // below (the forward is the last reader of the transposed images)
     {
-        const int n1 = H1 * H0, n2 = H2 * H0;
+        const int n1 = H1 * H0, n2 = ONE ? 0 : H2 * H0;   // ONE: W1 alone (W2 follows it through the image at dh0)
         for (int e0 = t; e0 < n1 + n2; e0 += 8 * kSmThreads) {
             float v[8];
 #pragma unroll
@@ -587,14 +623,45 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     __syncthreads();
     XPA_SM_STAMP(7);
     // dh0 = (dh1 W1 + dh2 W2) act'(h0), in place over h0
-    for (int tl = w; tl < MB * (H0 / 32); tl += kSmWaves) {
-        const int b0 = 32 * (tl % MB), i0 = 32 * (tl / MB);
-        f32x16 acc = sm_tile(h1T + b0, 1, S, 32, W1T + i0, H0, 1, 32, H1);
-        const f32x16 acc2 = sm_tile(h2T + b0, 1, S, 32, W1T + H1 * H0 + i0, H0, 1, 32, H2);
+    if constexpr (ONE) {
+        // MB == 1 and H0 / 32 <= kSmWaves: wave w holds tile w's W1 half across the re-staging of the image with W2
+        const bool mine = w < H0 / 32;
+        const int i0 = 32 * w;
+        f32x16 acc = {};
+        if (mine) acc = sm_tile(h1T, 1, S, 32, W1T + i0, H0, 1, 32, H1);
+        __syncthreads();
+        for (int e0 = t; e0 < H2 * H0; e0 += 8 * kSmThreads) {
+            float v[8];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float *p = h0T + (i0 + li) * S + b0 + sm_row(r);
-            *p = (acc[r] + acc2[r]) * sm_grad<ACT>(*p, slope);
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + u * kSmThreads;
+                v[u] = e < H2 * H0 ? a.W2[e] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + u * kSmThreads;
+                if (e < H2 * H0) W1T[e] = v[u];
+            }
+        }
+        __syncthreads();
+        if (mine) {
+            const f32x16 acc2 = sm_tile(h2T, 1, S, 32, W1T + i0, H0, 1, 32, H2);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float *p = h0T + (i0 + li) * S + sm_row(r);
+                *p = (acc[r] + acc2[r]) * sm_grad<ACT>(*p, slope);
+            }
+        }
+    } else {
+        for (int tl = w; tl < MB * (H0 / 32); tl += kSmWaves) {
+            const int b0 = 32 * (tl % MB), i0 = 32 * (tl / MB);
+            f32x16 acc = sm_tile(h1T + b0, 1, S, 32, W1T + i0, H0, 1, 32, H1);
+            const f32x16 acc2 = sm_tile(h2T + b0, 1, S, 32, W1T + H1 * H0 + i0, H0, 1, 32, H2);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float *p = h0T + (i0 + li) * S + b0 + sm_row(r);
+                *p = (acc[r] + acc2[r]) * sm_grad<ACT>(*p, slope);
+            }
         }
     }
     __syncthreads();
@@ -903,6 +970,12 @@ XPA_API int64_t xpa_small_mlp_lds_floats(int64_t batch, int64_t d_in, int64_t h0
            KP + 4 + 4 * BP + BP * KP + BP;
 }
 
+// The one-image form's carve (the template's ONE): the wider of the two hidden-weight images once
+XPA_API int64_t xpa_small_mlp_one_image_lds_floats(int64_t batch, int64_t d_in, int64_t h0, int64_t h1, int64_t h2,
+                                                   int64_t k) {
+    return xpa_small_mlp_lds_floats(batch, d_in, h0, h1, h2, k) - h0 * ((h1 < h2 ? h1 : h2) + 1);
+}
+
 namespace {
 // The checks and launches shared by K30's entry points; GAUSS: hd holds the Gaussian head's logstd and its gradient.
 template <bool GAUSS>
@@ -922,11 +995,20 @@ int small_mlp_launch(const XpaSmallMlpArgs *args, SmGauss hd, xpa_stream_t strea
     const int G = a.n_groups < 1 ? 1 : a.n_groups;
     if (G > 1 && (G > 16 || G != (a.batch + 31) / 32 || !a.grad_part || !a.loss_part || (uintptr_t)a.grad_part % 16))
         return (int)hipErrorInvalidValue;
-    if (xpa_small_mlp_lds_floats(G > 1 ? 32 : a.batch, a.d_in, a.h0, a.h1, a.h2, a.k) > kSmLds)
+    // the one-image form only where the resident layout does not fit: at most 32 rows per workgroup
+    const int64_t rows = G > 1 ? 32 : a.batch;
+    const bool one = xpa_small_mlp_lds_floats(rows, a.d_in, a.h0, a.h1, a.h2, a.k) > kSmLds;
+    if (one && (rows > 32 || xpa_small_mlp_one_image_lds_floats(rows, a.d_in, a.h0, a.h1, a.h2, a.k) > kSmLds))
         return (int)hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-#define XPA_SM(A_, G_) \
-    hipLaunchKernelGGL((small_mlp_update_kernel<A_, G_, GAUSS>), dim3(G), dim3(kSmThreads), 0, s, a, hd)
+#define XPA_SM(A_, G_)                                                                                             \
+    do {                                                                                                           \
+        if (one)                                                                                                   \
+            hipLaunchKernelGGL((small_mlp_update_kernel<A_, G_, GAUSS, true>), dim3(G), dim3(kSmThreads), 0, s, a, \
+                               hd);                                                                                \
+        else                                                                                                       \
+            hipLaunchKernelGGL((small_mlp_update_kernel<A_, G_, GAUSS>), dim3(G), dim3(kSmThreads), 0, s, a, hd);  \
+    } while (0)
     if (a.algo == XPA_ALGO_PPO) {
         if (a.act_code == 0) XPA_SM(0, XPA_ALGO_PPO);
         else if (a.act_code == 1) XPA_SM(1, XPA_ALGO_PPO);

@@ -345,7 +345,11 @@ class _FusedPolicyGradient(Learner):
                 or l0.in_features > 32:
             return False
         rows = 32 if self.small_split and 32 < batch <= 512 else batch   # per workgroup
-        return int(ops.lib().xpa_small_mlp_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704
+        if int(ops.lib().xpa_small_mlp_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704:
+            return True
+        # the one-image form (128-wide layers): at most 32 rows per workgroup, which the kernel selects by the budget
+        return rows <= 32 and \
+            int(ops.lib().xpa_small_mlp_one_image_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704
 
     def _small_launch(self, obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars=None):
         """One K30 launch (capturable): reads lr / Adam step at the schedule cursor and advances it.  scalars: the

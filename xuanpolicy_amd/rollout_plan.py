@@ -82,6 +82,7 @@ _K32 = {("cartpole", "categorical"): ("xpa_small_rollout_cartpole", 4, 2),
         ("pendulum", "gaussian"): ("xpa_small_rollout_pendulum", 3, 1),
         ("acrobot", "categorical"): ("xpa_small_rollout_acrobot", 6, 3),
         ("mountaincar", "categorical"): ("xpa_small_rollout_mountaincar", 8, 3)}
+K32_DRIVERS = ("K32", "K32W")   # the one-launch rollout's drivers: the same entry points, run the same way
 _VALUE_HEAD = {"K13": ("xpa_value_head",), "chain": ("xpa_value_head",), "cnn": (), "policy": ()}
 _POST = {"K14F": (), "K8-deferred": ("xpa_rollout_post_deferred_norm",), "K8": ("xpa_rollout_post",)}
 _CLOSE = {None: (), "raw-last": ("xpa_rollout_bootstrap_fixup",), "raw-mid-next": ()}
@@ -92,8 +93,9 @@ _FEED = {"rows": (), "small": (), "epoch": (), "slot": (), "all-reduce": ("xpa_g
 
 
 class RolloutPlan(NamedTuple):
-    """One iteration's forms.  With driver "K32" the step fields name the multi-kernel step the one launch stands for."""
-    driver: str        # "K32" | "graph-chunk" | "graph-step" | "eager" | "host"
+    """One iteration's forms.  With driver "K32" / "K32W" the step fields name the multi-kernel step the one launch
+    stands for."""
+    driver: str        # "K32" | "K32W" (K32 at 128-wide layers) | "graph-chunk" | "graph-step" | "eager" | "host"
     chunk: int         # device env steps per replayed graph, or per K32 launch under use_graph (1: single steps)
     obs: str           # "raw" (store_column) | "K5N" (normalise + column store) | "trunk" (inside the first layer)
     rms: object        # None | "standalone" | "all-reduce" | "fold-K8" | "fold-K14F"
@@ -121,7 +123,7 @@ class RolloutPlan(NamedTuple):
     def step_launches(self, pending=False):
         """The library entry points of one steady device env step, in order (hipBLASLt / torch launches are not
         counted).  pending: the step after a reset, which runs the standalone obs_rms update whatever the form."""
-        if self.driver == "K32":
+        if self.driver in K32_DRIVERS:
             return [entry for (env, _), (entry, _, _) in _K32.items() if env == self.env]
         out = list(_RMS["standalone"] if pending and self.rms in ("fold-K8", "fold-K14F") else _RMS[self.rms])
         out += _OBS[self.obs] + _TRUNK[self.trunk]
@@ -156,13 +158,15 @@ def plan_rollout(f):
     # actions) device env with deferred bootstraps, no per-step collective, the small_policy_layers shape
     k32 = (f.fused_rollout and f.cuda and (f.env, f.dist) in _K32 and f.defer_boot and not f.raw_obs and not collective
            and f.algo in ("ppo", "a2c") and f.small is not None and f.small_bufs)
+    wide = False
     if k32:
         d_in, h0, h1, h2, k, lds = f.small
-        k32 = (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and (d_in, k) == _K32[f.env, f.dist][1:]
-               and d_in == f.obs_dim and 0 < lds <= 16384)
+        wide = (h0, h1, h2) == (128, 128, 128)   # K32W: the forward's own layout, everything else K32's
+        k32 = ((wide or (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64)))
+               and (d_in, k) == _K32[f.env, f.dist][1:] and d_in == f.obs_dim and 0 < lds <= 16384)
     chunk = max(1, f.graph_chunk) if f.use_graph and device and not collective else 1
-    driver = ("host" if not device else "K32" if k32 else "eager" if not (f.use_graph and not collective)
-              else "graph-chunk" if chunk > 1 else "graph-step")
+    driver = ("host" if not device else ("K32W" if wide else "K32") if k32
+              else "eager" if not (f.use_graph and not collective) else "graph-chunk" if chunk > 1 else "graph-step")
     fused = sh is not None and device and f.fuse_env_step and f.env_fusable
     k14f = fused and f.fuse_post and f.defer_boot
     head = "K3" if sh is None else "K14F" if k14f else "K14E" if fused else "K14"
