@@ -37,7 +37,9 @@ typedef struct ihipStream_t *xpa_stream_t; /* == hipStream_t */
  * V(norm(reset_obs)); the last step's closures use v_boot). */
 /* ABI 4 (round 6): the batched column-sum finalizes that take a ticket (xpa_colsum_finalize_batch_sq / _sq_loss / _map)
  * need int32 [XPA_COLSUM_TICKET_INTS] there, zero-initialised and left at zero (two ticket levels on separate lines:
- * ~300 blocks counting on one int serialised their atomics). */
+ * ~300 blocks counting on one int serialised their atomics).
+ * Added since without a version change (new entry points only, no existing signature or struct touched): the
+ * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch. */
 #define XPA_ABI_VERSION 4
 #define XPA_COLSUM_TICKET_INTS 4096
 
@@ -169,6 +171,11 @@ int xpa_policy_loss_finalize_sq(int algo, int dist, int64_t batch, int64_t act_d
  * ppoclip_agent.py:76-81): out = a pseudo-random permutation of [0, n) keyed by (seed, counter)
  * (4-round Feistel over 2h >= log2(n) bits with cycle walking), n <= 2^31. */
 int xpa_random_permutation(int64_t n, uint32_t seed, uint32_t counter, int64_t *out, xpa_stream_t stream);
+/* The same for P agents in one launch (grid (blocks, P)): row p of out [P, n] is xpa_random_permutation(n, seeds[p],
+ * counters[p]), element for element; seeds / counters: uint32 [P] in device memory.  1 <= n_agents <= 65535 (the
+ * grid's y extent). */
+int xpa_random_permutation_batch(int64_t n, int64_t n_agents, const uint32_t *seeds, const uint32_t *counters,
+                                 int64_t *out, xpa_stream_t stream);
 
 /* K5 — RunningMeanStd over observations (xuance/common/statistic_tools.py:63-112) and observation
  * normalisation (xuance/torch/agents/agent.py:104-116).
@@ -343,6 +350,27 @@ int xpa_small_rollout_pendulum(const XpaSmallRolloutArgs *args, const float *log
  * normalised row and the obs-RMS row groups 256 / d_in are loops over d_in, accumulated in ascending d). */
 int xpa_small_rollout_acrobot(const XpaSmallRolloutArgs *args, xpa_stream_t stream);
 int xpa_small_rollout_mountaincar(const XpaSmallRolloutArgs *args, xpa_stream_t stream);
+/* K32 / K32W for a population: P agents side by side in ONE launch, workgroup p = agent p (the training form only).
+ * Each workgroup loads its own XpaSmallRolloutArgs from dev_blocks[p] (device memory; the address is wave-uniform)
+ * and, for a Gaussian head (XPA_ENV_PENDULUM), its XpaSmallRolloutHead from dev_heads[p]; from there on it is the
+ * single-agent kernel's body, so agent p's tensors end bit for bit as xpa_small_rollout_<env>(&host_blocks[p]) leaves
+ * them.  No workgroup reads or waits on what another writes: P is bounded by the grid alone, not by the CU count.
+ * host_blocks / host_heads: the host's copy of the same arrays.  Every check runs on it before any HIP call: each
+ * block passes the single-agent checks, and every block equals block 0 (which picks the instantiation, the LDS size
+ * and the step count) in every non-pointer field except seed and env_seed; else, or with n_agents < 1, an error is
+ * returned and nothing is launched.  host_heads / dev_heads: NULL for the Categorical envs. */
+#define XPA_ENV_CARTPOLE 0
+#define XPA_ENV_PENDULUM 1
+#define XPA_ENV_ACROBOT 2
+#define XPA_ENV_MOUNTAINCAR 3
+typedef struct XpaSmallRolloutHead {
+    const float *logstd; /* float [1] */
+    float act_clip;
+    int pad_;
+} XpaSmallRolloutHead;
+int xpa_small_rollout_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                            const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
+                            const XpaSmallRolloutHead *dev_heads, xpa_stream_t stream);
 
 /* Device evaluation (the reference's test loop, ppoclip_agent.py:113-165 / a2c_agent.py:109-160, without a host round
  * trip per step): an episode log on the device and its two writers.
@@ -491,6 +519,21 @@ int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t stream);
  * grad_part[g] at the same offset and the finalize sums it in g order.  xpa_small_mlp_lds_floats(..., k = A) gives
  * the LDS budget. */
 int xpa_small_mlp_update_gauss(const XpaSmallMlpArgs *args, const float *logstd, float *g_logstd,
+                               xpa_stream_t stream);
+/* K30 for a population: one minibatch update of each of P agents in ONE launch, grid (G, P) with agent = blockIdx.y
+ * (and, in the split form, the finalize over grid (1, P)); every form of the single-agent entry points (one
+ * workgroup, split, resident and one-image layouts).  Agent p's block is loaded from dev_blocks[p] and, for Gaussian
+ * heads, its (logstd, g_logstd) from dev_heads[p]; schedule cursor, partials and flat buffers stay per agent, and
+ * agent p's tensors end bit for bit as xpa_small_mlp_update[_gauss](&host_blocks[p], ...) leaves them.  No workgroup
+ * waits on another agent's.  host_heads / dev_heads: both NULL for Categorical heads, both given for Gaussian ones.
+ * The checks run on the host copies before any HIP call: each block passes the single-agent checks and equals block 0
+ * in every non-pointer field; else, or with n_agents < 1 or > 65535 (the grid's y extent), an error and no launch. */
+typedef struct XpaSmallMlpGauss {
+    const float *logstd; /* [A] */
+    float *g_logstd;     /* [A], inside the agent's flat gradient */
+} XpaSmallMlpGauss;
+int xpa_small_mlp_update_batch(int64_t n_agents, const XpaSmallMlpArgs *host_blocks, const XpaSmallMlpArgs *dev_blocks,
+                               const XpaSmallMlpGauss *host_heads, const XpaSmallMlpGauss *dev_heads,
                                xpa_stream_t stream);
 
 /* K10 — activation backward fused with bias-gradient column sums for one MLP layer (row-major

@@ -762,7 +762,9 @@ class _OnPolicyAgent:
             part.div_(self.world)                           # averaged: mean / var of the global minibatch
         return self.learner.update_fused(obs_mb, idx, act_flat, adv_flat, ret_flat, logp_flat, part)
 
-    def _update_phase(self):
+    def _close_rollout(self):
+        """The end of a full rollout, up to the first minibatch: the bootstrap values (one critic pass over the
+        deferred rows) and the advantage scan, in the plan's forms."""
         plan, mem = self.plan(), self.memory
         mem.size = self.n_steps
         if plan.close == "raw-last":
@@ -802,12 +804,25 @@ class _OnPolicyAgent:
                 self.gae_form = "compact"
         else:
             _no_form("the advantage scan", gae)
-        NT, B = self.buffer_size, self.batch_size
+
+    def _flat_rows(self):
+        """The closed rollout as the minibatch updates read it: (obs, act, adv, ret, old_logp) flat over env x step."""
+        mem, NT = self.memory, self.buffer_size
         obs_flat = mem.observations.reshape((NT,) + tuple(mem.observations.shape[2:]))
         act_flat = mem.actions.reshape(-1)
         adv_flat = mem.advantages.reshape(-1)
         ret_flat = mem.returns.reshape(-1)
         logp_flat = mem.auxiliary_infos["old_logp"].reshape(-1) if self.algo == "ppo" else None
+        return obs_flat, act_flat, adv_flat, ret_flat, logp_flat
+
+    def _update_phase(self):
+        self._close_rollout()
+        if self.phase_events is not None:   # measurement hook: closing | epochs split of the update
+            self.phase_events.append(("close_end", torch.cuda.Event(enable_timing=True)))
+            self.phase_events[-1][1].record()
+        plan, mem = self.plan(), self.memory
+        NT, B = self.buffer_size, self.batch_size
+        obs_flat, act_flat, adv_flat, ret_flat, logp_flat = self._flat_rows()
         use_advnorm = mem.use_advnorm
         scalars = None
         feed, log = plan.feed, self.update_log
@@ -848,6 +863,10 @@ class _OnPolicyAgent:
                 scalars = outs[-1]
                 if log is not None:
                     log.extend(outs)
+        self._end_update(scalars)
+
+    def _end_update(self, scalars):
+        """After an iteration's last minibatch update is enqueued; scalars: that update's loss scalars."""
         self.last_info = scalars
         self.iterations += 1
         if self.defer_boot:
@@ -881,24 +900,14 @@ class _OnPolicyAgent:
         while left > 0:
             t0 = time.perf_counter()
             if self._t == 0:
-                if self.sync_obs_rms_rollout:   # the common statistics every rank starts this rollout from
-                    self._rms_c0 = (self.obs_mean.clone(), self.obs_var.clone(), self.obs_count.clone())
-                fc = self._rollout_cnn()
-                if fc is not None:
-                    fc.refresh()   # outside any captured graph: the replays read the refreshed weight copy
-                pair = self.plan().pair
-                if pair is not None:
-                    self._rollout_mlp().rollout_refresh(pair)   # K40R's weight planes (same: outside the graphs)
+                self._begin_rollout()
             if chunk > 1 and left >= chunk and self._t % chunk == 0 and self.n_steps - self._t >= chunk:
                 k = self._rollout_chunk_graph(chunk)
             else:
                 step_fn()
                 k = 1
             left -= k
-            self._t += k
-            self.memory.ptr = self._t % self.n_steps
-            self.memory.size = min(self.memory.size + k, self.n_steps)
-            self.current_step += self.n_envs * k
+            self._advance(k)
             t1 = time.perf_counter()
             self.timers["rollout"] += t1 - t0
             if self._t == self.n_steps:
@@ -911,13 +920,35 @@ class _OnPolicyAgent:
                 if self.phase_events is not None:
                     self.phase_events.append(("update_end", torch.cuda.Event(enable_timing=True)))
                     self.phase_events[-1][1].record()
-                self._t = 0
-                self.memory.ptr, self.memory.size = 0, 0
-                if log:
-                    info = self._host_info()
-                    self.infos.append(info)
-                    self.log_infos(info, self.current_step)
+                self._end_iteration(log)
                 self.timers["update"] += time.perf_counter() - t1
+
+    def _begin_rollout(self):
+        """Ahead of a rollout's first step, outside any captured graph."""
+        if self.sync_obs_rms_rollout:   # the common statistics every rank starts this rollout from
+            self._rms_c0 = (self.obs_mean.clone(), self.obs_var.clone(), self.obs_count.clone())
+        fc = self._rollout_cnn()
+        if fc is not None:
+            fc.refresh()   # outside any captured graph: the replays read the refreshed weight copy
+        pair = self.plan().pair
+        if pair is not None:
+            self._rollout_mlp().rollout_refresh(pair)   # K40R's weight planes (same: outside the graphs)
+
+    def _advance(self, k):
+        """The host's view of k device env steps just enqueued."""
+        self._t += k
+        self.memory.ptr = self._t % self.n_steps
+        self.memory.size = min(self.memory.size + k, self.n_steps)
+        self.current_step += self.n_envs * k
+
+    def _end_iteration(self, log):
+        """After the update phase: the buffer starts over and the iteration's info is logged."""
+        self._t = 0
+        self.memory.ptr, self.memory.size = 0, 0
+        if log:
+            info = self._host_info()
+            self.infos.append(info)
+            self.log_infos(info, self.current_step)
 
     def save_model(self, model_name):
         """agent.py:74-76: the policy's state_dict to model_dir_save/model_name."""

@@ -138,6 +138,21 @@ __global__ __launch_bounds__(256) void permutation_kernel(int64_t n, int h, uint
     out[i] = (int64_t)x;
 }
 
+// permutation_kernel over grid (blocks, P): row blockIdx.y of out [P, n] is agent blockIdx.y's permutation, keyed by
+// its own (seed, counter) — element for element what permutation_kernel writes for that key
+__global__ __launch_bounds__(256) void permutation_batch_kernel(int64_t n, int h, const uint32_t *__restrict__ seeds,
+                                                                const uint32_t *__restrict__ counters,
+                                                                int64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t seed = seeds[blockIdx.y], counter = counters[blockIdx.y];
+    uint32_t x = (uint32_t)i;
+    do {
+        x = feistel(x, h, seed, counter);
+    } while ((int64_t)x >= n);
+    out[(int64_t)blockIdx.y * n + i] = (int64_t)x;
+}
+
 // ---------------------------------------------------------------------------------------------
 // K5 RunningMeanStd
 // ---------------------------------------------------------------------------------------------
@@ -1251,9 +1266,16 @@ struct RoNoEval {};
 // column (the sampler's three stores go to [N] scratch columns: T = 1, t = 0), no post step, no ret_rms; each step's
 // finished episodes are compacted into the log in env order and the step loop ends after the first step at which the
 // log holds `target` episodes (the reference's test loop, ppoclip_agent.py:113-165).
-template <class E, int ACT, int H0, bool EVAL = false>
-__global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRolloutArgs a, typename E::Head hd,
-                                                                   std::conditional_t<EVAL, RoEval, RoNoEval> ev) {
+// The body is one device function under two __global__ wrappers: small_rollout_kernel (one agent, the block and the
+// head in the kernel arguments) and small_rollout_batch_kernel (one workgroup per agent, each with its own block read
+// from device memory).
+template <class E, int ACT, int H0, bool EVAL>
+__device__ __forceinline__ void small_rollout_body(const XpaSmallRolloutArgs &args, const typename E::Head &head,
+                                                   const std::conditional_t<EVAL, RoEval, RoNoEval> &eval) {
+    // local copies: the fields become values read once at entry, as a kernel's by-value arguments are
+    const XpaSmallRolloutArgs a = args;
+    const typename E::Head hd = head;
+    const std::conditional_t<EVAL, RoEval, RoNoEval> ev = eval;
     extern __shared__ float lds[];
     __shared__ double s_sum[kRoThreads], s_sq[kRoThreads];
     __shared__ double s_red[kRoThreads / 64];
@@ -1607,6 +1629,27 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRollo
             ev.log[kLogDone] = e_count >= e_target ? 1 : 0;
         }
     }
+}
+
+template <class E, int ACT, int H0, bool EVAL = false>
+__global__ __launch_bounds__(kRoThreads) void small_rollout_kernel(XpaSmallRolloutArgs a, typename E::Head hd,
+                                                                   std::conditional_t<EVAL, RoEval, RoNoEval> ev) {
+    small_rollout_body<E, ACT, H0, EVAL>(a, hd, ev);
+}
+
+// The population form (xpa_small_rollout_batch): workgroup p is agent p.  Its block (and, for a Gaussian head, its
+// logstd / act_clip) is a plain load at a wave-uniform address; from there on it is the training body, and no
+// workgroup reads or waits on anything another one writes.
+template <class E, int ACT, int H0>
+__global__ __launch_bounds__(kRoThreads) void small_rollout_batch_kernel(
+    const XpaSmallRolloutArgs *__restrict__ blocks, const XpaSmallRolloutHead *__restrict__ heads) {
+    const XpaSmallRolloutArgs a = blocks[blockIdx.x];
+    typename E::Head hd{};
+    if constexpr (!std::is_empty_v<typename E::Head>) {
+        const XpaSmallRolloutHead h = heads[blockIdx.x];
+        hd = typename E::Head{h.logstd, h.act_clip};
+    }
+    small_rollout_body<E, ACT, H0, false>(a, hd, RoNoEval{});
 }
 
 // xpa_eval_post: one workgroup walks the envs in passes of kEvalThreads, so a step's entries land in env order (lane
@@ -2018,6 +2061,17 @@ XPA_API int xpa_random_permutation(int64_t n, uint32_t seed, uint32_t counter, i
     return xpa_launch_status();
 }
 
+XPA_API int xpa_random_permutation_batch(int64_t n, int64_t n_agents, const uint32_t *seeds, const uint32_t *counters,
+                                         int64_t *out, xpa_stream_t stream) {
+    if (n <= 0 || n > (1LL << 31) || n_agents < 1 || n_agents > 65535 || !seeds || !counters || !out)
+        return (int)hipErrorInvalidValue;
+    int h = 1;
+    while ((1LL << (2 * h)) < n) ++h;
+    hipLaunchKernelGGL(permutation_batch_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)n_agents), dim3(256), 0,
+                       (hipStream_t)stream, n, h, seeds, counters, out);
+    return xpa_launch_status();
+}
+
 XPA_API int xpa_rollout_policy_head_synthbox(int act, int64_t n_envs, int64_t act_dim, int64_t horizon, int64_t hidden,
                                              int64_t ld, const float *z_actor, const float *z_critic, float slope,
                                              const float *w_actor, const float *b_actor, const float *w_critic,
@@ -2178,26 +2232,80 @@ int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd,
     return xpa_launch_status();
 }
 
+// The argument checks of K32's training form (one agent's block)
 template <class E>
-int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head hd, xpa_stream_t stream) {
+bool ro_train_args_ok(const XpaSmallRolloutArgs *a, int k) {
     if (!a || a->n_envs <= 0 || a->n_envs > 256 || a->horizon <= 0 || a->steps <= 0 || a->d_in != E::D ||
         !ro_widths_ok(a->h0, a->h1, a->h2) || a->k != k ||
         a->act_code < 0 || a->act_code > 2 || a->n_slots < 1 || a->n_slots > a->horizon || a->max_episode_steps <= 0 ||
         a->ld_norm < a->d_in || a->ld_obs < E::D || a->ld_act < k || a->ld_boot < a->d_in)
-        return (int)hipErrorInvalidValue;
+        return false;
     if (!a->W0 || !a->b0 || !a->W1 || !a->b1 || !a->W2 || !a->b2 || !a->Wa || !a->ba || !a->Wc || !a->bc ||
         !a->obs_mean || !a->obs_var || !a->obs_count || !a->obs_norm || !a->buf_obs || !a->buf_act || !a->buf_logp ||
         !a->buf_val || !a->buf_rew || !a->buf_term || !a->buf_closed || !a->buf_boot || !a->act_in || !a->env_state ||
         !a->env_obs || !a->final_obs || !a->env_rew || !a->env_term || !a->env_trunc || !a->ep_step || !a->ep_index ||
         !a->ep_score || !a->ep_last_score || !a->ep_last_len || !a->returns || !a->ret_mean || !a->ret_var ||
         !a->ret_count || !a->slot_obs || !a->slot_t || !a->overflow || !a->boot_norm || !a->cursor)
-        return (int)hipErrorInvalidValue;
+        return false;
     const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
-    if (lf < 0 || lf > kRoLdsMax) return (int)hipErrorInvalidValue;
+    return lf >= 0 && lf <= kRoLdsMax;
+}
+
+template <class E>
+int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head hd, xpa_stream_t stream) {
+    if (!ro_train_args_ok<E>(a, k)) return (int)hipErrorInvalidValue;
+    const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
 #define XPA_RO_LAUNCH(ACT, H0) \
     hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a, hd, RoNoEval{})
+    if (a->h0 == kRoWide) {   // K32W
+        if (a->act_code == 0) XPA_RO_LAUNCH(0, kRoWide);
+        else if (a->act_code == 1) XPA_RO_LAUNCH(1, kRoWide);
+        else XPA_RO_LAUNCH(2, kRoWide);
+    } else if (a->h0 == 64) {
+        if (a->act_code == 0) XPA_RO_LAUNCH(0, 64);
+        else if (a->act_code == 1) XPA_RO_LAUNCH(1, 64);
+        else XPA_RO_LAUNCH(2, 64);
+    } else {
+        if (a->act_code == 0) XPA_RO_LAUNCH(0, 32);
+        else if (a->act_code == 1) XPA_RO_LAUNCH(1, 32);
+        else XPA_RO_LAUNCH(2, 32);
+    }
+#undef XPA_RO_LAUNCH
+    return xpa_launch_status();
+}
+
+// Every non-pointer field but seed / env_seed: what one instantiation, one LDS carve and one launch shape share
+bool ro_same_shape(const XpaSmallRolloutArgs &x, const XpaSmallRolloutArgs &y) {
+    return x.n_envs == y.n_envs && x.horizon == y.horizon && x.steps == y.steps && x.d_in == y.d_in && x.h0 == y.h0 &&
+           x.h1 == y.h1 && x.h2 == y.h2 && x.k == y.k && x.act_code == y.act_code && x.use_obsnorm == y.use_obsnorm &&
+           x.n_slots == y.n_slots && x.mask_returns == y.mask_returns && x.use_rewnorm == y.use_rewnorm &&
+           x.max_episode_steps == y.max_episode_steps && x.slot_reset_obs == y.slot_reset_obs && x.slope == y.slope &&
+           x.obs_clip == y.obs_clip && x.gamma == y.gamma && x.rew_range == y.rew_range && x.ld_norm == y.ld_norm &&
+           x.ld_act == y.ld_act && x.ld_obs == y.ld_obs && x.ld_boot == y.ld_boot;
+}
+
+// xpa_small_rollout_batch for one env / head pair: every check on the host copies before any HIP call, the
+// instantiation from block 0, one workgroup per agent
+template <class E>
+int small_rollout_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host, const XpaSmallRolloutArgs *dev,
+                               int k, const XpaSmallRolloutHead *host_heads, const XpaSmallRolloutHead *dev_heads,
+                               xpa_stream_t stream) {
+    constexpr bool kHead = !std::is_empty_v<typename E::Head>;
+    if (n_agents < 1 || n_agents > 0x7fffffff || !host || !dev || (kHead && (!host_heads || !dev_heads)))
+        return (int)hipErrorInvalidValue;
+    for (int64_t p = 0; p < n_agents; ++p) {
+        if (!ro_train_args_ok<E>(host + p, k) || !ro_same_shape(host[p], host[0])) return (int)hipErrorInvalidValue;
+        if (kHead && (!host_heads[p].logstd || !(host_heads[p].act_clip > 0.f))) return (int)hipErrorInvalidValue;
+    }
+    const XpaSmallRolloutArgs *a = host;
+    const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
+    const size_t bytes = (size_t)lf * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+#define XPA_RO_LAUNCH(ACT, H0)                                                                                   \
+    hipLaunchKernelGGL((small_rollout_batch_kernel<E, ACT, H0>), dim3((unsigned)n_agents), dim3(kRoThreads), bytes, \
+                       s, dev, dev_heads)
     if (a->h0 == kRoWide) {   // K32W
         if (a->act_code == 0) XPA_RO_LAUNCH(0, kRoWide);
         else if (a->act_code == 1) XPA_RO_LAUNCH(1, kRoWide);
@@ -2232,6 +2340,27 @@ XPA_API int xpa_small_rollout_acrobot(const XpaSmallRolloutArgs *a, xpa_stream_t
 
 XPA_API int xpa_small_rollout_mountaincar(const XpaSmallRolloutArgs *a, xpa_stream_t stream) {
     return small_rollout_launch<RoMountainCarCat>(a, 3, RoMountainCarCat::Head{}, stream);
+}
+
+XPA_API int xpa_small_rollout_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                                    const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
+                                    const XpaSmallRolloutHead *dev_heads, xpa_stream_t stream) {
+    switch (env) {
+    case XPA_ENV_CARTPOLE:
+        return small_rollout_batch_launch<RoCartPoleCat>(n_agents, host_blocks, dev_blocks, 2, host_heads, dev_heads,
+                                                         stream);
+    case XPA_ENV_PENDULUM:
+        return small_rollout_batch_launch<RoPendulumGauss>(n_agents, host_blocks, dev_blocks, 1, host_heads, dev_heads,
+                                                           stream);
+    case XPA_ENV_ACROBOT:
+        return small_rollout_batch_launch<RoAcrobotCat>(n_agents, host_blocks, dev_blocks, 3, host_heads, dev_heads,
+                                                        stream);
+    case XPA_ENV_MOUNTAINCAR:
+        return small_rollout_batch_launch<RoMountainCarCat>(n_agents, host_blocks, dev_blocks, 3, host_heads,
+                                                            dev_heads, stream);
+    default:
+        return (int)hipErrorInvalidValue;
+    }
 }
 
 // ---- device evaluation: K32E and the generic tier's per-step log writer ---------------------------------------------

@@ -94,8 +94,14 @@ struct SmGauss {
 // through ONE LDS image, one after the other — transposed for the actor's and then the critic's hidden layer in the
 // forward, row-major for the two halves of dh0 = dh1 W1 + dh2 W2 in the backward (the W1 half kept in the tile's
 // accumulator registers while W2 is staged, then summed as the resident form sums them).
-template <int ACT, int ALGO, bool GAUSS, bool ONE = false>
-__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmallMlpArgs a, SmGauss hd) {
+// The body is one device function under two __global__ wrappers: small_mlp_update_kernel (one agent, grid (G)) and
+// small_mlp_update_batch_kernel (grid (G, P): agent blockIdx.y, its block read from device memory).
+template <int ACT, int ALGO, bool GAUSS, bool ONE>
+__device__ __forceinline__ void small_mlp_update_body(const XpaSmallMlpArgs &args, const SmGauss &head) {
+    // local copies: the fields become values read once at entry, as a kernel's by-value arguments are (read through
+    // the references, the pointer selections below would keep the whole block addressable, in scratch)
+    const XpaSmallMlpArgs a = args;
+    const SmGauss hd = head;
     __shared__ __attribute__((aligned(16))) float lds[kSmLds];
     __shared__ double s_red[kSmWaves * 6];
     __shared__ float s_stat[4];
@@ -788,11 +794,32 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmal
     if (t == 0) a.cursor[0] = a.cursor[0] + 1;
 }
 
+template <int ACT, int ALGO, bool GAUSS, bool ONE = false>
+__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_kernel(XpaSmallMlpArgs a, SmGauss hd) {
+    small_mlp_update_body<ACT, ALGO, GAUSS, ONE>(a, hd);
+}
+
+// The population form (xpa_small_mlp_update_batch): grid (G, P), agent = blockIdx.y with its own block (and, for a
+// Gaussian head, its own logstd / d logstd) at a wave-uniform address; workgroup (g, p) is agent p's workgroup g of
+// the single-agent launch, and reads or waits on nothing of another agent.
+template <int ACT, int ALGO, bool GAUSS, bool ONE = false>
+__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_update_batch_kernel(
+    const XpaSmallMlpArgs *__restrict__ blocks, const XpaSmallMlpGauss *__restrict__ heads) {
+    const XpaSmallMlpArgs a = blocks[blockIdx.y];
+    SmGauss hd{nullptr, nullptr};
+    if constexpr (GAUSS) {
+        const XpaSmallMlpGauss h = heads[blockIdx.y];
+        hd = SmGauss{h.logstd, h.g_logstd};
+    }
+    small_mlp_update_body<ACT, ALGO, GAUSS, ONE>(a, hd);
+}
+
 // Split form's second launch: the loss scalars from the workgroups' loss sums, the gradient as the sum of the
 // workgroups' partials in workgroup order (written to the flat gradient buffer), clip_grad_norm_ and Adam — K30's
 // tail arithmetic.
 template <int ALGO>
-__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_finalize_kernel(XpaSmallMlpArgs a) {
+__device__ __forceinline__ void small_mlp_finalize_body(const XpaSmallMlpArgs &args) {
+    const XpaSmallMlpArgs a = args;   // as in small_mlp_update_body
     __shared__ double s_red[kSmWaves];
     __shared__ float s_coef, s_step, s_inv;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -961,6 +988,19 @@ __global__ __launch_bounds__(kSmThreads, 1) void small_mlp_finalize_kernel(XpaSm
     if (t == 0) a.cursor[0] = a.cursor[0] + 1;
 }
 
+template <int ALGO>
+__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_finalize_kernel(XpaSmallMlpArgs a) {
+    small_mlp_finalize_body<ALGO>(a);
+}
+
+// grid (1, P): agent blockIdx.y's finalize over its own partials, schedule cursor and flat buffers
+template <int ALGO>
+__global__ __launch_bounds__(kSmThreads, 1) void small_mlp_finalize_batch_kernel(
+    const XpaSmallMlpArgs *__restrict__ blocks) {
+    const XpaSmallMlpArgs a = blocks[blockIdx.y];
+    small_mlp_finalize_body<ALGO>(a);
+}
+
 }  // namespace
 
 XPA_API int64_t xpa_small_mlp_lds_floats(int64_t batch, int64_t d_in, int64_t h0, int64_t h1, int64_t h2, int64_t k) {
@@ -977,10 +1017,10 @@ XPA_API int64_t xpa_small_mlp_one_image_lds_floats(int64_t batch, int64_t d_in, 
 }
 
 namespace {
-// The checks and launches shared by K30's entry points; GAUSS: hd holds the Gaussian head's logstd and its gradient.
+// The argument checks of one agent's block; *one_out: the one-image form (the resident layout does not fit)
 template <bool GAUSS>
-int small_mlp_launch(const XpaSmallMlpArgs *args, SmGauss hd, xpa_stream_t stream) {
-    if (!args) return (int)hipErrorInvalidValue;
+bool sm_args_ok(const XpaSmallMlpArgs *args, bool *one_out) {
+    if (!args) return false;
     const XpaSmallMlpArgs &a = *args;
     if (a.batch < 1 || a.d_in < 1 || a.d_in > 32 || a.h0 < 32 || a.h1 < 32 || a.h2 < 32 || a.h0 % 32 || a.h1 % 32 ||
         a.h2 % 32 || a.h0 > 256 || a.h1 > 256 || a.h2 > 256 || a.k < (GAUSS ? 1 : 2) || a.k > kSmActMax ||
@@ -991,15 +1031,26 @@ int small_mlp_launch(const XpaSmallMlpArgs *args, SmGauss hd, xpa_stream_t strea
         !a.Wa || !a.ba || !a.Wc || !a.bc || !a.gW0 || !a.gb0 || !a.gW1 || !a.gb1 || !a.gW2 || !a.gb2 || !a.gWa ||
         !a.gba || !a.gWc || !a.gbc || a.n % 4 ||
         ((uintptr_t)a.param | (uintptr_t)a.grad | (uintptr_t)a.exp_avg | (uintptr_t)a.exp_avg_sq) % 16)
-        return (int)hipErrorInvalidValue;
+        return false;
     const int G = a.n_groups < 1 ? 1 : a.n_groups;
     if (G > 1 && (G > 16 || G != (a.batch + 31) / 32 || !a.grad_part || !a.loss_part || (uintptr_t)a.grad_part % 16))
-        return (int)hipErrorInvalidValue;
+        return false;
     // the one-image form only where the resident layout does not fit: at most 32 rows per workgroup
     const int64_t rows = G > 1 ? 32 : a.batch;
     const bool one = xpa_small_mlp_lds_floats(rows, a.d_in, a.h0, a.h1, a.h2, a.k) > kSmLds;
     if (one && (rows > 32 || xpa_small_mlp_one_image_lds_floats(rows, a.d_in, a.h0, a.h1, a.h2, a.k) > kSmLds))
-        return (int)hipErrorInvalidValue;
+        return false;
+    *one_out = one;
+    return true;
+}
+
+// The checks and launches shared by K30's entry points; GAUSS: hd holds the Gaussian head's logstd and its gradient.
+template <bool GAUSS>
+int small_mlp_launch(const XpaSmallMlpArgs *args, SmGauss hd, xpa_stream_t stream) {
+    bool one = false;
+    if (!sm_args_ok<GAUSS>(args, &one)) return (int)hipErrorInvalidValue;
+    const XpaSmallMlpArgs &a = *args;
+    const int G = a.n_groups < 1 ? 1 : a.n_groups;
     hipStream_t s = (hipStream_t)stream;
 #define XPA_SM(A_, G_)                                                                                             \
     do {                                                                                                           \
@@ -1027,6 +1078,69 @@ int small_mlp_launch(const XpaSmallMlpArgs *args, SmGauss hd, xpa_stream_t strea
     }
     return xpa_launch_status();
 }
+
+// Every non-pointer field: what one instantiation, one grid and one LDS carve share (n_rows and n with them)
+bool sm_same_shape(const XpaSmallMlpArgs &x, const XpaSmallMlpArgs &y) {
+    return x.batch == y.batch && x.d_in == y.d_in && x.h0 == y.h0 && x.h1 == y.h1 && x.h2 == y.h2 && x.k == y.k &&
+           x.act_code == y.act_code && x.algo == y.algo && x.use_advnorm == y.use_advnorm && x.n_sched == y.n_sched &&
+           x.slope == y.slope && x.clip_range == y.clip_range && x.vf_coef == y.vf_coef && x.ent_coef == y.ent_coef &&
+           x.max_norm == y.max_norm && x.beta1 == y.beta1 && x.beta2 == y.beta2 && x.eps == y.eps &&
+           x.obs_ld == y.obs_ld && x.n_rows == y.n_rows && x.n == y.n &&
+           (x.n_groups < 1 ? 1 : x.n_groups) == (y.n_groups < 1 ? 1 : y.n_groups);
+}
+
+// xpa_small_mlp_update_batch: every check on the host copies before any HIP call, the instantiation from block 0,
+// grid (G, P) and, in the split form, the finalize over grid (1, P)
+template <bool GAUSS>
+int small_mlp_batch_launch(int64_t n_agents, const XpaSmallMlpArgs *host, const XpaSmallMlpArgs *dev,
+                           const XpaSmallMlpGauss *host_heads, const XpaSmallMlpGauss *dev_heads,
+                           xpa_stream_t stream) {
+    if (n_agents < 1 || n_agents > 65535 || !host || !dev) return (int)hipErrorInvalidValue;
+    bool one = false;
+    for (int64_t p = 0; p < n_agents; ++p) {
+        bool one_p = false;
+        if (!sm_args_ok<GAUSS>(host + p, &one_p) || !sm_same_shape(host[p], host[0]))
+            return (int)hipErrorInvalidValue;
+        if (p == 0) one = one_p;
+        if (GAUSS) {
+            // g_logstd lies inside the agent's flat gradient, as xpa_small_mlp_update_gauss requires
+            const XpaSmallMlpGauss &h = host_heads[p];
+            if (!h.logstd || !h.g_logstd || h.g_logstd < host[p].grad || h.g_logstd + host[p].k > host[p].grad + host[p].n)
+                return (int)hipErrorInvalidValue;
+        }
+    }
+    const XpaSmallMlpArgs &a = host[0];
+    const unsigned G = a.n_groups < 1 ? 1u : (unsigned)a.n_groups, P = (unsigned)n_agents;
+    hipStream_t s = (hipStream_t)stream;
+#define XPA_SM(A_, G_)                                                                                         \
+    do {                                                                                                       \
+        if (one)                                                                                               \
+            hipLaunchKernelGGL((small_mlp_update_batch_kernel<A_, G_, GAUSS, true>), dim3(G, P), dim3(kSmThreads), \
+                               0, s, dev, dev_heads);                                                          \
+        else                                                                                                   \
+            hipLaunchKernelGGL((small_mlp_update_batch_kernel<A_, G_, GAUSS>), dim3(G, P), dim3(kSmThreads), 0, s, \
+                               dev, dev_heads);                                                                \
+    } while (0)
+    if (a.algo == XPA_ALGO_PPO) {
+        if (a.act_code == 0) XPA_SM(0, XPA_ALGO_PPO);
+        else if (a.act_code == 1) XPA_SM(1, XPA_ALGO_PPO);
+        else XPA_SM(2, XPA_ALGO_PPO);
+    } else {
+        if (a.act_code == 0) XPA_SM(0, XPA_ALGO_A2C);
+        else if (a.act_code == 1) XPA_SM(1, XPA_ALGO_A2C);
+        else XPA_SM(2, XPA_ALGO_A2C);
+    }
+#undef XPA_SM
+    if (G > 1) {
+        if (a.algo == XPA_ALGO_PPO)
+            hipLaunchKernelGGL((small_mlp_finalize_batch_kernel<XPA_ALGO_PPO>), dim3(1, P), dim3(kSmThreads), 0, s,
+                               dev);
+        else
+            hipLaunchKernelGGL((small_mlp_finalize_batch_kernel<XPA_ALGO_A2C>), dim3(1, P), dim3(kSmThreads), 0, s,
+                               dev);
+    }
+    return xpa_launch_status();
+}
 }  // namespace
 
 XPA_API int xpa_small_mlp_update(const XpaSmallMlpArgs *args, xpa_stream_t stream) {
@@ -1040,4 +1154,13 @@ XPA_API int xpa_small_mlp_update_gauss(const XpaSmallMlpArgs *args, const float 
         g_logstd + args->k > args->grad + args->n)
         return (int)hipErrorInvalidValue;
     return small_mlp_launch<true>(args, SmGauss{logstd, g_logstd}, stream);
+}
+
+XPA_API int xpa_small_mlp_update_batch(int64_t n_agents, const XpaSmallMlpArgs *host_blocks,
+                                       const XpaSmallMlpArgs *dev_blocks, const XpaSmallMlpGauss *host_heads,
+                                       const XpaSmallMlpGauss *dev_heads, xpa_stream_t stream) {
+    // both head arrays or neither: a Gaussian head (args->k the action dimension) or a Categorical one
+    if ((host_heads != nullptr) != (dev_heads != nullptr)) return (int)hipErrorInvalidValue;
+    if (host_heads) return small_mlp_batch_launch<true>(n_agents, host_blocks, dev_blocks, host_heads, dev_heads, stream);
+    return small_mlp_batch_launch<false>(n_agents, host_blocks, dev_blocks, nullptr, nullptr, stream);
 }

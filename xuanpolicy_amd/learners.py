@@ -351,9 +351,9 @@ class _FusedPolicyGradient(Learner):
         return rows <= 32 and \
             int(ops.lib().xpa_small_mlp_one_image_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704
 
-    def _small_launch(self, obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars=None):
-        """One K30 launch (capturable): reads lr / Adam step at the schedule cursor and advances it.  scalars: the
-        8-float destination of the loss scalars (default: the learner's shared one)."""
+    def _small_args(self, obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars=None):
+        """K30's argument block for one minibatch and the tensor its loss scalars go to (scalars, default: the
+        learner's shared one); allocates the split form's workspace on first use."""
         fm, fused = self._fused_mlp(), self.fused_opt
         (l0, code, slope), (l1, _, _), (la, _, _), (l2, _, _), (lc, _, _) = (fm.rep[0], fm.actor[0], fm.actor[1],
                                                                              fm.critic[0], fm.critic[1])
@@ -397,6 +397,13 @@ class _FusedPolicyGradient(Learner):
                 ws[G] = (torch.zeros((G, fused.fs.numel), dtype=torch.float32, device=obs_flat.device),
                          torch.zeros((G, 8), dtype=torch.float64, device=obs_flat.device))
             a.grad_part, a.loss_part = ws[G][0].data_ptr(), ws[G][1].data_ptr()
+        return a, out
+
+    def _small_launch(self, obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars=None):
+        """One K30 launch (capturable): reads lr / Adam step at the schedule cursor and advances it.  scalars: the
+        8-float destination of the loss scalars (default: the learner's shared one)."""
+        a, out = self._small_args(obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars)
+        fm = self._fused_mlp()
         if fm.logstd is None:
             _lib.call(ops.lib().xpa_small_mlp_update, ctypes.byref(a), ops._stream(obs_flat.device))
         else:   # Gaussian head: la is the mu layer, act [n_rows, A]

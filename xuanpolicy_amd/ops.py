@@ -737,6 +737,19 @@ def random_permutation(n, seed, counter, out=None, device=None):
     return out
 
 
+def random_permutation_batch(n, seeds, counters, out=None):
+    """Row p of out (int64 [P, n]): random_permutation(n, seeds[p], counters[p]), all P in one launch.  seeds /
+    counters: int32 [P] device tensors holding the uint32 keys' bits."""
+    P = seeds.shape[0]
+    _req(seeds, "seeds", torch.int32, (P,))
+    _req(counters, "counters", torch.int32, (P,))
+    if out is None:
+        out = torch.empty((P, n), dtype=torch.int64, device=seeds.device)
+    _req(out, "out", torch.int64, (P, n))
+    _lib.call(lib().xpa_random_permutation_batch, n, P, _p(seeds), _p(counters), _p(out), _stream(out.device))
+    return out
+
+
 def gather_num_partials(batch):
     return int(lib().xpa_gather_num_partials(batch))
 

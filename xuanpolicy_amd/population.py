@@ -1,0 +1,408 @@
+"""P classic-control agents trained side by side: one launch per stage for the whole population (DESIGN.md §3,
+"Population training").
+
+The one-launch small path (K32 / K32W rollout, K30 update) is one workgroup per agent — ten at most in the split update
+— on a chip of 256 CUs.  Population puts "agent" on a grid dimension of those kernels: xpa_small_rollout_batch,
+xpa_random_permutation_batch and xpa_small_mlp_update_batch run P members' rollout chunk, epoch permutation and
+minibatch update in one launch each, every workgroup reading its own agent's argument block from device memory and
+computing exactly what the single-agent launch computes.  So Population.train means `for a in agents: a.train(...)`
+bit for bit, and a member stays an ordinary agent before, between and after.
+
+plan_population decides eligibility from a facts record per member (host logic alone: no tensor, no device), in the
+style of rollout_plan.plan_rollout; there is no sequential fallback: an ineligible population raises."""
+import ctypes
+from typing import NamedTuple
+
+from .rollout_plan import _K32, K32_DRIVERS
+
+# xpa_small_rollout_batch's env codes (include/xuanpolicy_amd.h: XPA_ENV_*), by the single-agent entry point
+_ENV_CODE = {"xpa_small_rollout_cartpole": "XPA_ENV_CARTPOLE", "xpa_small_rollout_pendulum": "XPA_ENV_PENDULUM",
+             "xpa_small_rollout_acrobot": "XPA_ENV_ACROBOT", "xpa_small_rollout_mountaincar": "XPA_ENV_MOUNTAINCAR"}
+assert set(_ENV_CODE) == {entry for entry, _, _ in _K32.values()}
+MAX_AGENTS = 65535   # the y extent of a launch grid (the update's agent dimension); not a function of the CU count
+
+
+class MemberFacts(NamedTuple):
+    """What plan_population decides from, one record per member.  Population._facts gathers it."""
+    driver: str          # the member's RolloutPlan.driver
+    feed: str            # the member's RolloutPlan.feed
+    entry: str           # the single-agent rollout entry point its plan launches (None without a K32 driver)
+    chunk: int           # RolloutPlan.chunk: env steps per rollout launch
+    dims: tuple          # (d_in, h0, h1, h2, k) of learner.small_policy_layers (None: another policy shape)
+    activation: tuple    # (activation code, slope)
+    algo: str            # "ppo" | "a2c"
+    n_envs: int
+    n_steps: int
+    n_epoch: int
+    batch_size: int      # minibatch rows
+    device: str
+    world: int
+    t: int               # steps of the current rollout already taken
+    scalars: tuple       # ((name, value), ...): the hyper-parameters that are kernel-argument scalars
+    tensors: tuple       # data pointers of every tensor the launches write for this member
+
+
+class PopulationPlan(NamedTuple):
+    n_agents: int
+    entry: str           # the single-agent entry point the batch launch stands for
+    env: str             # its XPA_ENV_* constant's name
+    gaussian: bool       # the head arrays (logstd, act_clip / logstd, g_logstd) are passed
+    chunk: int
+
+
+_SHARED = ("entry", "dims", "activation", "algo", "n_envs", "n_steps", "n_epoch", "batch_size", "device", "chunk", "t")
+
+
+def plan_population(facts):
+    """The PopulationPlan of the members' facts, or ValueError naming the first thing that rules the population out.
+    The only place eligibility is decided."""
+    facts = list(facts)
+    if not 1 <= len(facts) <= MAX_AGENTS:
+        raise ValueError("a population has 1 .. %d members, not %d" % (MAX_AGENTS, len(facts)))
+    for i, f in enumerate(facts):
+        if f.world != 1:
+            raise ValueError("member %d: world size %d (a population trains in one process: world must be 1)"
+                             % (i, f.world))
+        if f.driver not in K32_DRIVERS or f.entry not in _ENV_CODE:
+            raise ValueError("member %d: rollout driver %r is not the one-launch small path %s"
+                             % (i, f.driver, "/".join(K32_DRIVERS)))
+        if f.feed != "small":
+            raise ValueError("member %d: minibatch feed %r is not the one-launch update (\"small\")" % (i, f.feed))
+        if f.dims is None:
+            raise ValueError("member %d: the policy is not the small-path shape" % i)
+    f0 = facts[0]
+    for i, f in enumerate(facts[1:], 1):
+        for name in _SHARED:
+            if getattr(f, name) != getattr(f0, name):
+                raise ValueError("member %d differs from member 0 in %s: %r != %r"
+                                 % (i, name, getattr(f, name), getattr(f0, name)))
+        if f.scalars != f0.scalars:
+            d0 = dict(f0.scalars)
+            name, v = next((n, v) for n, v in f.scalars if d0.get(n, v) != v or n not in d0)
+            raise ValueError("member %d differs from member 0 in %s: %r != %r (a kernel-argument scalar: one value "
+                             "per launch)" % (i, name, v, d0.get(name)))
+    seen = {}
+    for i, f in enumerate(facts):
+        for ptr in f.tensors:
+            if ptr in seen and seen[ptr] != i:
+                raise ValueError("members %d and %d share a tensor (data pointer 0x%x)" % (seen[ptr], i, ptr))
+            seen[ptr] = i
+    return PopulationPlan(len(facts), f0.entry, _ENV_CODE[f0.entry], f0.entry == "xpa_small_rollout_pendulum", f0.chunk)
+
+
+def _block_array(struct, blocks):
+    arr = (struct * len(blocks))()
+    for i, b in enumerate(blocks):
+        ctypes.memmove(ctypes.addressof(arr) + i * ctypes.sizeof(struct), ctypes.addressof(b), ctypes.sizeof(struct))
+    return arr
+
+
+class _DeviceBlocks:
+    """Argument-block arrays in device memory, uploaded once per distinct content (outside any capture) and kept
+    alive with their host copies for the launches and graphs that hold their addresses."""
+
+    def __init__(self, device):
+        self.device, self._cache = device, {}
+
+    def get(self, arr):
+        import torch
+        raw = bytes(arr)
+        ent = self._cache.get(raw)
+        if ent is None:
+            if len(self._cache) >= 64:   # a caller whose layouts never repeat: do not grow without bound
+                self._cache.clear()
+            dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
+            ent = self._cache[raw] = (arr, dev)
+        return ent
+
+
+def update_blocks(learners, rows, idxs, scalars, cache):
+    """xpa_small_mlp_update_batch's arguments for one minibatch of every learner: (host blocks, device blocks, host
+    heads, device heads).  rows[p] = (obs_flat, act, adv, ret, old_logp, use_advnorm) and idxs[p] (int64 row indices)
+    are learner p's, scalars[p] the 8 floats its loss scalars go to; each block is the learner's own
+    (learner._small_args), cache a _DeviceBlocks."""
+    from . import _lib
+    blocks, heads = [], []
+    for p, L in enumerate(learners):
+        obs_flat, act, adv, ret, old_logp, use_advnorm = rows[p]
+        blk, _ = L._small_args(obs_flat, idxs[p], act, adv, ret, old_logp, use_advnorm, scalars=scalars[p])
+        blocks.append(blk)
+        logstd = L._fused_mlp().logstd
+        if logstd is not None:
+            h = _lib.XpaSmallMlpGauss()
+            h.logstd, h.g_logstd = logstd.data_ptr(), logstd.grad.data_ptr()
+            heads.append(h)
+    if heads and len(heads) != len(blocks):
+        raise ValueError("Categorical and Gaussian heads in one batch update")
+    host, dev = cache.get(_block_array(_lib.XpaSmallMlpArgs, blocks))
+    hh = hd = None
+    if heads:
+        hh, hd = cache.get(_block_array(_lib.XpaSmallMlpGauss, heads))
+    return host, dev, hh, hd
+
+
+def launch_update(slot, n_agents, device):
+    """One minibatch update of every agent in one launch (xpa_small_mlp_update_batch; capturable)."""
+    from . import _lib, ops
+    host, dev, hh, hd = slot
+    _lib.call(ops.lib().xpa_small_mlp_update_batch, n_agents, ctypes.addressof(host), dev.data_ptr(),
+              None if hh is None else ctypes.addressof(hh), None if hd is None else hd.data_ptr(), ops._stream(device))
+
+
+def small_update_batch(learners, rows, idxs, scalars, cache=None):
+    """learner.small_update (one eager K30 update and the host bookkeeping of the step) for every learner, the device
+    part as one batch launch.  Arguments as update_blocks'; returns scalars."""
+    device = scalars.device
+    for L in learners:
+        if not L.fused_opt.sched_enabled:
+            L.fused_opt.enable_sched()   # the blocks hold the schedule's and the cursor's addresses
+    slot = update_blocks(learners, rows, idxs, scalars, _DeviceBlocks(device) if cache is None else cache)
+    for L in learners:
+        L.fused_opt.ensure_window(L.scheduler)
+        L.iterations += 1
+    launch_update(slot, len(learners), device)
+    for L in learners:
+        L._host_steps(1)
+    return scalars
+
+
+class Population:
+    """Population(agents): P PPOCLIP_Agent / A2C_Agent members of one shape (plan_population) trained in lockstep.
+
+    train(train_steps, log) is `for a in agents: a.train(train_steps, log)` for every member's parameters, Adam state,
+    schedule cursor, statistics, env state, buffers and host counters; the members' own `timers` are not advanced (the
+    population's `timers` are).  The schedule cursor agrees for members that have taken all their updates in the same
+    way (alone or in this population); after a mix of the two the table may be refilled at another update, which
+    changes the cursor's value and nothing a launch computes."""
+
+    def __init__(self, agents):
+        from .agents import _OnPolicyAgent
+        self.agents = list(agents)
+        for i, a in enumerate(self.agents):
+            if not isinstance(a, _OnPolicyAgent):
+                raise ValueError("member %d: a population's members are PPOCLIP_Agent / A2C_Agent objects, not %s"
+                                 % (i, type(a).__name__))
+        self.timers = {"rollout": 0.0, "update": 0.0}
+        self.phase_events = None   # a list: ("rollout_end" | "close_end" | "update_end", event) per iteration
+        self._plan = self._plan_key = None
+        self.plan()
+        a0 = self.agents[0]
+        self.device = a0.device
+        self._blocks = _DeviceBlocks(self.device)
+        self._perm = self._perm_keys = self._perm_host = None   # [P, n] permutations; (seeds, counters) on the device
+        self._epochs = {}          # epoch key -> ["warm" | graph, per-slot launch arguments, their loss scalars]
+        self._graph_pool = None
+        self._graph_failed = False
+
+    # ---- eligibility --------------------------------------------------------------------------------------------
+    @staticmethod
+    def _facts(a):
+        plan, L, env, mem = a.plan(), a.learner, a.envs, a.memory
+        layers = L.small_policy_layers()
+        k32 = plan.driver in K32_DRIVERS
+        dims = act = None
+        tensors = ()
+        if layers is not None:
+            (l0, l1, la, l2, _), code, slope, _ = layers
+            dims = (l0.in_features, l0.out_features, l1.out_features, l2.out_features, la.out_features)
+            act = (int(code), float(slope))
+        if k32 and plan.feed == "small":
+            fused = L.fused_opt
+            ts = [fused.fs.param, fused.fs.flat, fused.exp_avg, fused.exp_avg_sq, mem.observations, mem.actions,
+                  mem.values, mem.rewards, mem.terminals, mem.closed, mem.boot, env.state, env.obs, env.act_in,
+                  a.obs_mean, a.obs_var, a.obs_count, a.ret_mean, a.ret_var, a.ret_count, a.returns, a.cursor,
+                  a.obs_norm, a._boot_pair, a.slot_t]
+            tensors = tuple(int(t.data_ptr()) for t in ts)
+        g = L.optimizer.param_groups[0]
+        scalars = (("use_obsnorm", a.use_obsnorm), ("use_rewnorm", a.use_rewnorm), ("obs_clip", float(a._obs_clip())),
+                   ("rewnorm_range", float(a.rewnorm_range)), ("gamma", float(a.gamma)), ("n_slots", int(a.n_slots)),
+                   ("max_episode_steps", int(getattr(env, "max_episode_steps", 0) or 0)),
+                   ("boot_from_reset", bool(a.boot_from_reset)), ("use_advnorm", bool(mem.use_advnorm)),
+                   ("clip_range", float(getattr(L, "clip_range", 0.0) or 0.0)), ("vf_coef", float(L.vf_coef)),
+                   ("ent_coef", float(L.ent_coef)),
+                   ("max_norm", float(L._max_norm) if L._use_clip else -1.0), ("betas", tuple(map(float, g["betas"]))),
+                   ("eps", float(g["eps"])), ("small_split", bool(L.small_split)),
+                   ("graph_updates", bool(L.graph_updates)))
+        entry = plan.step_launches()[0] if k32 else None
+        return MemberFacts(plan.driver, plan.feed, entry, plan.chunk, dims, act, a.algo, a.n_envs, a.n_steps, a.n_epoch,
+                           a.batch_size, str(a.device), a.world, a._t, scalars, tensors)
+
+    def plan(self):
+        """The PopulationPlan of the members as they stand (cached under the members' own plans and positions)."""
+        for a in self.agents:
+            a.plan()   # refreshes the member's own plan, its key and its K32 block when what they rest on changed
+        key = tuple((id(a), a._plan_key) for a in self.agents)
+        if key != self._plan_key or any(a._t != self.agents[0]._t for a in self.agents):
+            self._plan = plan_population([self._facts(a) for a in self.agents])
+            self._plan_key = key
+        return self._plan
+
+    # ---- the batch launches ---------------------------------------------------------------------------------------
+    def _rollout_launch(self, plan, steps):
+        """`steps` env steps of every member in one launch (xpa_small_rollout_batch)."""
+        from . import _lib, ops
+        blocks = []
+        for a in self.agents:
+            a._k32.steps = int(steps)
+            blocks.append(a._k32)
+        host, dev = self._blocks.get(_block_array(_lib.XpaSmallRolloutArgs, blocks))
+        hh = hd = None
+        if plan.gaussian:
+            heads = []
+            for a in self.agents:
+                h = _lib.XpaSmallRolloutHead()
+                h.logstd, h.act_clip = ops._p(a._k32_logstd), a._act_clip()
+                heads.append(h)
+            hh, hd = self._blocks.get(_block_array(_lib.XpaSmallRolloutHead, heads))
+        lib = ops.lib()
+        _lib.call(lib.xpa_small_rollout_batch, _lib.ENV_CODES[plan.env], len(blocks), ctypes.addressof(host),
+                  dev.data_ptr(), None if hh is None else ctypes.addressof(hh), None if hd is None else hd.data_ptr(),
+                  ops._stream(self.device))
+
+    def _permutations(self, n):
+        """Row p: member p's next epoch permutation (agent.epoch_permutation), all in one launch."""
+        import numpy as np
+        import torch
+        from . import ops
+        P = len(self.agents)
+        if self._perm is None or self._perm.shape[1] != n:
+            self._perm = torch.empty((P, n), dtype=torch.int64, device=self.device)
+        want = [(int(a.seed) & 0xFFFFFFFF, int(a._perm_counter) & 0xFFFFFFFF) for a in self.agents]
+        if self._perm_host != want:
+            # (seed, counter) per member on the device; the counters then advance there, one add per epoch, and are
+            # uploaded again only when a member's own counter moved some other way (it trained alone in between)
+            keys = np.asarray(want, dtype=np.uint32).T.copy().view(np.int32)
+            self._perm_keys = torch.from_numpy(keys).to(self.device)
+        ops.random_permutation_batch(n, self._perm_keys[0], self._perm_keys[1], out=self._perm)
+        self._perm_keys[1].add_(1)
+        for a in self.agents:
+            a._perm_counter += 1
+        self._perm_host = [(s, (c + 1) & 0xFFFFFFFF) for s, c in want]
+        return self._perm
+
+    def _epoch_args(self, rows, perm, NT, B):
+        """The launch arguments of one epoch's minibatch slots (the blocks built by the members' own learners) and
+        the [P, slots, 8] tensor their loss scalars go to."""
+        import torch
+        starts = list(range(0, NT, B))
+        scalars = torch.zeros((len(self.agents), len(starts), 8), dtype=torch.float32, device=self.device)
+        learners = [a.learner for a in self.agents]
+        return [update_blocks(learners, rows, [perm[p, s:s + B] for p in range(len(learners))], scalars[:, j],
+                              self._blocks) for j, s in enumerate(starts)], scalars
+
+    def _update_launch(self, slot):
+        launch_update(slot, len(self.agents), self.device)
+
+    def _epoch_key(self, rows, NT, B):
+        """What an epoch's launches (and their captured graph) bake in besides the permutation buffer: every member's
+        learners.small_epoch key.  Formed once per update phase: nothing of it can change between two epochs."""
+        from .learners import _ptr
+        return (NT, B) + tuple(
+            (_ptr(r[0]), tuple(r[0].shape), _ptr(r[1]), _ptr(r[2]), _ptr(r[3]), _ptr(r[4]), bool(r[5]),
+             float(a.learner.clip_range), float(a.learner.vf_coef), float(a.learner.ent_coef),
+             bool(a.learner.small_split)) + a.learner._step_key() for r, a in zip(rows, self.agents))
+
+    def _epoch(self, rows, perm, NT, B, key):
+        """One epoch of minibatch updates for every member: learners.small_epoch's legs over the batch launches —
+        eager the first time a layout is seen, then captured once as one linear graph and replayed.  Returns the
+        [P, slots, 8] loss scalars of the epoch's updates."""
+        from . import graphs
+        learners = [a.learner for a in self.agents]
+        n_slots = -(-NT // B)
+        key = (perm.data_ptr(),) + key
+        for L in learners:
+            if not L.fused_opt.sched_enabled:
+                L.fused_opt.enable_sched()
+        cache = self._epochs
+        ent = cache.get(key)
+        W = learners[0].fused_opt.SCHED_WINDOW
+        graphed = (all(L.graph_updates for L in learners) and not self._graph_failed and n_slots <= W
+                   and (ent is not None or len(cache) < learners[0].graph_max_slots))
+        if ent is None or not graphed:
+            slots, scalars = self._epoch_args(rows, perm, NT, B) if ent is None else ent[1:]
+            for slot in slots:
+                for L in learners:
+                    L.fused_opt.ensure_window(L.scheduler)
+                    L.iterations += 1
+                self._update_launch(slot)
+                for L in learners:
+                    L._host_steps(1)
+            if graphed:
+                cache[key] = ["warm", slots, scalars]
+            return scalars
+        for L in learners:
+            L.fused_opt.ensure_window(L.scheduler, need=n_slots)
+        if ent[0] == "warm":
+            import torch
+            if self._graph_pool is None:
+                self._graph_pool = torch.cuda.graph_pool_handle()
+            try:
+                ent[0], _ = graphs.capture(lambda: [self._update_launch(s) for s in ent[1]], self._graph_pool)
+            except Exception:
+                torch.cuda.synchronize()   # nothing of an aborted capture ran: stay eager from here on
+                self._graph_failed = True
+                del cache[key]
+                return self._epoch(rows, perm, NT, B, key[1:])
+        ent[0].replay()
+        for L in learners:
+            L.iterations += n_slots
+            L._host_steps(n_slots)
+        return ent[2]
+
+    def _update_phase(self):
+        """agent._update_phase for every member: each closes its own rollout (bootstrap critic pass + GAE, the code it
+        runs alone), then per epoch one permutation launch and the minibatch slots' batch launches."""
+        import torch
+        agents = self.agents
+        for a in agents:
+            a._close_rollout()
+        if self.phase_events is not None:
+            self.phase_events.append(("close_end", torch.cuda.Event(enable_timing=True)))
+            self.phase_events[-1][1].record()
+        a0 = agents[0]
+        NT, B = a0.buffer_size, a0.batch_size
+        rows = [a._flat_rows() + (a.memory.use_advnorm,) for a in agents]
+        n_slots = -(-NT // B)
+        key = self._epoch_key(rows, NT, B)
+        for _ in range(a0.n_epoch):
+            perm = self._permutations(NT)
+            scalars = self._epoch(rows, perm, NT, B, key)
+            for p, a in enumerate(agents):
+                if a.update_log is not None:
+                    a.update_log.extend(scalars[p, j].clone() for j in range(n_slots))
+        for p, a in enumerate(agents):
+            a._end_update(scalars[p, n_slots - 1])
+
+    # ---- public API -------------------------------------------------------------------------------------------------
+    def train(self, train_steps, log=True):
+        """agent.train(train_steps, log) for every member, in lockstep (see the class docstring)."""
+        import time
+        import torch
+        agents = self.agents
+        a0 = agents[0]
+        left = train_steps
+        while left > 0:
+            plan = self.plan()
+            chunk, t = plan.chunk, a0._t
+            t0 = time.perf_counter()
+            if t == 0:
+                for a in agents:
+                    a._begin_rollout()
+            k = chunk if chunk > 1 and left >= chunk and t % chunk == 0 and a0.n_steps - t >= chunk else 1
+            self._rollout_launch(plan, k)
+            left -= k
+            for a in agents:
+                a._advance(k)
+            t1 = time.perf_counter()
+            self.timers["rollout"] += t1 - t0
+            if a0._t == a0.n_steps:
+                if self.phase_events is not None:
+                    self.phase_events.append(("rollout_end", torch.cuda.Event(enable_timing=True)))
+                    self.phase_events[-1][1].record()
+                self._update_phase()
+                if self.phase_events is not None:
+                    self.phase_events.append(("update_end", torch.cuda.Event(enable_timing=True)))
+                    self.phase_events[-1][1].record()
+                for a in agents:
+                    a._end_iteration(log)
+                self.timers["update"] += time.perf_counter() - t1

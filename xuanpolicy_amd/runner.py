@@ -210,6 +210,22 @@ def build_classic_control(env_id, agent="PPO_Clip", n_envs=8, n_steps=128, hidde
     return build_agent(cfg, device)
 
 
+def build_classic_population(env_id, seeds, agent="PPO_Clip", **kw):
+    """One member per seed of `seeds`, each built as it would be alone (build_cartpole_ppo for CartPole-v1,
+    build_pendulum_ppo for Pendulum-v1, build_classic_control for the rest; kw goes to the builder), as a
+    population.Population: train() runs the members side by side, one launch per stage for all of them, each
+    computing what it would compute alone.  Raises ValueError when the members are not one small-path shape."""
+    from .population import Population
+    build = {"CartPole-v1": build_cartpole_ppo, "Pendulum-v1": build_pendulum_ppo}.get(env_id)
+    members = []
+    for seed in seeds:
+        if build is None:
+            members.append(build_classic_control(env_id, agent=agent, seed=seed, **kw))
+        else:
+            members.append(build(agent=agent, seed=seed, **kw))
+    return Population(members)
+
+
 def build_perdqn(n_envs=8, n_size=131072, batch_size=2048, seed=1, device="cuda:0", **overrides):
     """The BASELINE.json C5 configuration: PER-DQN (perdqn/atari.yaml keys) on SynthAtari frames with 18 actions,
     replay n_envs x n_size (8 x 131 072 = 1 M transitions), batch 2048, BasicQnetwork over Basic_CNN; Adam(eps=1e-5)
