@@ -39,7 +39,8 @@ typedef struct ihipStream_t *xpa_stream_t; /* == hipStream_t */
  * need int32 [XPA_COLSUM_TICKET_INTS] there, zero-initialised and left at zero (two ticket levels on separate lines:
  * ~300 blocks counting on one int serialised their atomics).
  * Added since without a version change (new entry points only, no existing signature or struct touched): the
- * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch. */
+ * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch; K33's xpa_small_close and
+ * xpa_small_close_batch (XpaSmallCloseArgs). */
 #define XPA_ABI_VERSION 4
 #define XPA_COLSUM_TICKET_INTS 4096
 
@@ -371,6 +372,41 @@ typedef struct XpaSmallRolloutHead {
 int xpa_small_rollout_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
                             const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
                             const XpaSmallRolloutHead *dev_heads, xpa_stream_t stream);
+
+/* K33 — the closing of a one-launch small-path rollout in ONE launch (one workgroup of 256 threads per agent): the
+ * critic over the deferred bootstrap rows, xpa_rollout_bootstrap_fixup's writes and the advantage scan.
+ *   1. rows: float [(n_slots + 1) * n_envs, d_in] at row stride ld_rows, already normalised, slot-major (n_slots groups
+ *      of n_envs truncation-slot rows, then n_envs last-step rows).  The value of a row is bit for bit the value K32
+ *      (K32W at 128-wide layers) writes into buf_val for the same normalised row: K32's whole forward (the first layer's
+ *      fmaf chain over ascending d, v_mfma_f32_16x16x4_f32 over 16-row tiles with the unit tiles wave + 4 j, the
+ *      per-lane fmaf over the lane's tiles, the 16-lane row sum, bc + wave 0 + .. + wave 3) in passes of n_envs rows.
+ *      vboot_out (nullable): float [(n_slots + 1) * n_envs], those values.
+ *   2. xpa_rollout_bootstrap_fixup's writes: boot[n, slot_t[k n_envs + n]] = v[k n_envs + n] for every used slot, slot_t
+ *      reset to -1, boot[n, horizon - 1] = term[n, horizon - 1] != 0 ? 0 : v[n_slots n_envs + n].
+ *   3. xpa_gae_scan's recurrence over [n_envs, horizon] on the dense closure record (closed u8, boot), use_gae 1 or 0:
+ *      adv and ret, written where a closure exists at or after the step.
+ * Limits: K32's (n_envs <= 256, d_in 1 .. 8, h0, h1, h2 each in {32, 64} or all 128, k 1 .. 3, act_code 0 .. 2,
+ * xpa_small_rollout_lds_floats(...) <= 16384), 1 <= n_slots <= horizon, ld_rows >= d_in; no pointer but vboot_out may
+ * be NULL.  The kernel does not depend on the env.  Plain vector stores only. */
+typedef struct XpaSmallCloseArgs {
+    int n_envs, horizon, d_in, h0, h1, h2, k, act_code, n_slots, use_gae;
+    float slope, gamma, gae_lambda;
+    const float *W0, *b0, *W1, *b1, *W2, *b2, *Wa, *ba, *Wc, *bc;
+    const float *rows;
+    int64_t ld_rows;
+    int32_t *slot_t;
+    const float *rew, *val, *term;
+    const uint8_t *closed;
+    float *boot, *adv, *ret;
+    float *vboot_out;
+} XpaSmallCloseArgs;
+int xpa_small_close(const XpaSmallCloseArgs *args, xpa_stream_t stream);
+/* K33 for a population: workgroup p closes agent p's rollout from dev_blocks[p] (device memory), so agent p's tensors
+ * end bit for bit as xpa_small_close(&host_blocks[p]) leaves them; no workgroup reads or waits on what another writes.
+ * Every check runs on host_blocks before any HIP call: each block passes the single-agent checks, every block equals
+ * block 0 in every non-pointer field, 1 <= n_agents <= 65535; else an error is returned and nothing is launched. */
+int xpa_small_close_batch(int64_t n_agents, const XpaSmallCloseArgs *host_blocks, const XpaSmallCloseArgs *dev_blocks,
+                          xpa_stream_t stream);
 
 /* Device evaluation (the reference's test loop, ppoclip_agent.py:113-165 / a2c_agent.py:109-160, without a host round
  * trip per step): an episode log on the device and its two writers.

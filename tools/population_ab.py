@@ -9,6 +9,12 @@ the output file.  A further, separately timed iteration per leg records device e
 split into rollout / closing (bootstrap critic pass + GAE) / epochs.
 
     python tools/population_ab.py --out profiles/population_ab.json
+
+--small-close: the second leg is a Population of members built with small_close=True (the closing in ONE K33 launch,
+xpa_small_close_batch) in place of the Python loop: the same shapes, P and protocol, the default population as the
+other leg of the same process.  The figures of merit are the closing phase and ms per iteration of the two legs.
+
+    python tools/population_ab.py --small-close --out profiles/population_close_ab.json
 """
 import argparse
 import json
@@ -62,32 +68,38 @@ def _phase_pass(train, holders, n_steps):
     return _split(shared)
 
 
-def measure(shape, ps, repeats, warmup, device):
+def measure(shape, ps, repeats, warmup, device, small_close=False):
     import torch
     from xuanpolicy_amd.population import Population
     from xuanpolicy_amd.runner import build_cartpole_ppo
     kw = SHAPES[shape]
     T, N = kw["n_steps"], kw["n_envs"]
-    sets = [[build_cartpole_ppo(seed=s + 1, device=device, **kw) for s in range(max(ps))] for _ in range(2)]
+    other = "population_small_close" if small_close else "loop"
+    sets = [[build_cartpole_ppo(seed=s + 1, device=device, **dict(kw, **over)) for s in range(max(ps))]
+            for over in ({}, dict(small_close=True) if small_close else {})]
     cfg = sets[0][0].config
     res = {"workload": "PPO-Clip CartPole-v1 num_envs=%d horizon=%d, n_epoch %d, n_minibatch %d, nets [%d]"
                        % (N, T, cfg.n_epoch, cfg.n_minibatch, kw["hidden"]), "P": {}}
     for P in ps:
         pop, loop = Population(sets[0][:P]), sets[1][:P]
+        pop2 = Population(loop) if small_close else None
+        assert not pop.plan().close_batch and (pop2 is None or pop2.plan().close_batch)
         iters = max(2, 32 // P)   # iterations per sample: a window of at least ~0.1 s at every P
 
         def pop_train(steps):
             pop.train(steps, log=False)
 
         def loop_train(steps):
+            if small_close:
+                return pop2.train(steps, log=False)
             for a in loop:
                 a.train(steps, log=False)
         for _ in range(warmup):
             pop_train(T)
             loop_train(T)
-        samples = {"population": [], "loop": []}
+        samples = {"population": [], other: []}
         for _ in range(repeats):
-            for leg, fn in (("population", pop_train), ("loop", loop_train)):
+            for leg, fn in (("population", pop_train), (other, loop_train)):
                 el = _sync_time(lambda: fn(T * iters))
                 samples[leg].append({"ms_per_iteration": round(el / iters * 1e3, 4),
                                      "env_steps_per_s": round(P * N * T * iters / el, 1)})
@@ -99,14 +111,17 @@ def measure(shape, ps, repeats, warmup, device):
                           "env_steps_per_s_median": round(statistics.median(s["env_steps_per_s"]
                                                                             for s in samples[leg]), 1)}
         entry["population"]["phase_ms"] = _phase_pass(pop_train, [pop], T)
-        entry["loop"]["phase_ms"] = _phase_pass(loop_train, loop, T)
-        entry["loop_over_population"] = round(entry["loop"]["ms_per_iteration_median"]
-                                              / entry["population"]["ms_per_iteration_median"], 3)
+        entry[other]["phase_ms"] = _phase_pass(loop_train, [pop2] if small_close else loop, T)
+        entry[other + "_over_population"] = round(entry[other]["ms_per_iteration_median"]
+                                                  / entry["population"]["ms_per_iteration_median"], 3)
         ph = entry["population"]["phase_ms"]
-        entry["population"]["closing_share"] = round(ph["closing"] / max(sum(ph.values()), 1e-9), 4)
+        for leg in ("population", other) if small_close else ("population",):
+            lp = entry[leg]["phase_ms"]
+            entry[leg]["closing_share"] = round(lp["closing"] / max(sum(lp.values()), 1e-9), 4)
         res["P"][str(P)] = entry
-        print(shape, "P", P, {k: entry[k]["ms_per_iteration_median"] for k in ("population", "loop")},
-              "loop / population", entry["loop_over_population"], "population phases", ph, flush=True)
+        print(shape, "P", P, {k: entry[k]["ms_per_iteration_median"] for k in ("population", other)},
+              other, "/ population", entry[other + "_over_population"], "population phases", ph,
+              *((other, "phases", entry[other]["phase_ms"]) if small_close else ()), flush=True)
     del sets
     torch.cuda.empty_cache()
     return res
@@ -120,18 +135,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--small-close", action="store_true",
+                    help="second leg: a population of small_close=True members (K33) instead of the Python loop")
     args = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "population_ab.py measures on a ROCm GPU"
     ps = [int(p) for p in args.ps.split(",")]
-    out = {"what": "Population.train against `for a in agents: a.train(...)` over the same P agents, one process, "
+    out = {"what": ("Population.train of small_close=True members (population_small_close: the closing is one "
+                    "xpa_small_close_batch launch) against Population.train of default members (population: each "
+                    "member closes through its own _close_rollout), P agents each" if args.small_close else
+                    "Population.train against `for a in agents: a.train(...)` over the same P agents") + ", one process, "
                    "legs alternating, %d warm-up iterations and %d samples per leg; ms per iteration of all P "
                    "agents, aggregate env-steps/s; phase_ms: one further iteration per leg with device events at "
                    "the phase boundaries (rollout | closing = bootstrap critic pass + GAE per member | epochs)"
                    % (args.warmup, args.repeats),
            "device": torch.cuda.get_device_name(0), "shapes": {}}
     for shape in args.shapes.split(","):
-        out["shapes"][shape] = measure(shape, ps, args.repeats, args.warmup, args.device)
+        out["shapes"][shape] = measure(shape, ps, args.repeats, args.warmup, args.device, args.small_close)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)

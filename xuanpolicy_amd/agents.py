@@ -189,6 +189,10 @@ class _OnPolicyAgent:
         # K32: whole device env steps (RMS, normalise, forward, sample, env, post) in one launch (plan().driver)
         self.fused_rollout = bool(_cfg(config, "fused_rollout", True))
         self._k32 = None                      # K32's argument block, rebuilt with the plan
+        # K33 (opt-in, plan().gae == "K33"): a one-launch small-path rollout closes in one launch, its bootstraps in
+        # K32's own arithmetic
+        self.small_close = bool(_cfg(config, "small_close", False))
+        self._k33 = None                      # K33's argument block, rebuilt with the plan
         self._plan = self._plan_key = None
         self._eval_cursor = None              # test_device's step counter (made on first use; continues across calls)
         self.last_test_log = None             # test_device's decoded episode log (ops.eval_log_decode)
@@ -333,14 +337,15 @@ class _OnPolicyAgent:
         if obs is None and self.device_env:
             obs = self.envs.obs
         key = (self.fuse_env_step, self.fuse_post, self.fold_rms, self.fuse_value_gae, self.value_gemm,
-               self.fuse_gather, self.fused_rollout, self.use_graph, self.graph_chunk, F.ROLLOUT_SPLIT, F.ROLLOUT_TRUNK,
-               F.WIDE_TRUNK, ops.S3_GEMMS, L.small_updates, L.small_split, L.graph_updates, L.grad_sync is None,
+               self.fuse_gather, self.fused_rollout, self.small_close, self.use_graph, self.graph_chunk, F.ROLLOUT_SPLIT,
+               F.ROLLOUT_TRUNK, F.WIDE_TRUNK, ops.S3_GEMMS, L.small_updates, L.small_split, L.graph_updates, L.grad_sync is None,
                bool(self.memory._pending), None if obs is None else (obs.shape, obs.stride()),
                self.memory.observations.data_ptr(), self.memory.actions.data_ptr(),
                *[p.data_ptr() for p in self._params])
         if key != self._plan_key:
             self._plan = plan_rollout(self._facts(fm, F, obs))
             self._k32 = self._build_small_rollout() if self._plan.driver in K32_DRIVERS else None
+            self._k33 = self._build_small_close() if self._plan.gae == "K33" else None
             self._plan_key = key
         return self._plan
 
@@ -374,7 +379,7 @@ class _OnPolicyAgent:
             small_bufs=(all(b.dtype == torch.float32 and b.is_contiguous() for b in bufs)
                         and mem.closed.is_contiguous()),
             rows_ok=fm is not None and fm.rows_ok(obs_flat), small_update=L.small_update_ok(obs_flat, self.batch_size),
-            epoch_graphs=bool(L.graph_updates), dist=self.dist)
+            epoch_graphs=bool(L.graph_updates), dist=self.dist, small_close=bool(self.small_close))
 
     def _env_fused(self, fm=None):
         """True when the device env's step runs inside the rollout's K14 launch (ops.rollout_policy_head_synthbox);
@@ -539,6 +544,22 @@ class _OnPolicyAgent:
         a.slot_obs, a.slot_t, a.overflow = p(self.slot_obs), p(self.slot_t), p(self.slot_overflow)
         a.boot_norm, a.ld_boot = p(self.boot_obs), self.boot_obs.stride(0)
         a.cursor = p(self.cursor)
+        return a
+
+    def _build_small_close(self):
+        """K33's argument block (xpa_small_close) for a plan whose gae form is "K33": the policy's layers, the deferred
+        bootstrap rows and the buffer's tensors; plan() rebuilds it with K32's block."""
+        mem = self.memory
+        layers, code, slope, _ = self.learner.small_policy_layers()
+        return ops.small_close_args(layers, (code, slope), self._boot_pair, self.slot_t, mem.rewards, mem.values,
+                                    mem.terminals, mem.closed, mem.boot, mem._advantages, mem._returns, mem.gamma,
+                                    mem.gae_lam, mem.use_gae)
+
+    def _small_close_block(self):
+        """K33's block for a launch now: the scan's scalars are the buffer's as they stand, as every other closing
+        reads them (the tensors' addresses are the plan's: plan() rebuilds the block when they move)."""
+        a, mem = self._k33, self.memory
+        a.gamma, a.gae_lambda, a.use_gae = float(mem.gamma), float(mem.gae_lam), int(bool(mem.use_gae))
         return a
 
     def _small_rollout_launch(self, steps):
@@ -774,6 +795,10 @@ class _OnPolicyAgent:
         gae = plan.gae
         if gae == "scan":
             mem.compute_advantages()
+        elif gae == "K33":
+            # one launch: the deferred rows' critic in K32's arithmetic, the fixup's writes and the advantage scan
+            ops.small_close(self._small_close_block(), self.device)
+            self._closed_small()
         elif gae == "value":
             # one launch: the critic's output layer, the fixup's bootstrap writes and the compact GAE scan
             fm = self._rollout_mlp()
@@ -804,6 +829,12 @@ class _OnPolicyAgent:
                 self.gae_form = "compact"
         else:
             _no_form("the advantage scan", gae)
+
+    def _closed_small(self):
+        """The host state a K33 launch (the agent's own, or the population's batch launch) leaves."""
+        self.memory.size = self.n_steps
+        self.memory._dirty = False
+        self.gae_form = "K33"
 
     def _flat_rows(self):
         """The closed rollout as the minibatch updates read it: (obs, act, adv, ret, old_logp) flat over env x step."""

@@ -1652,6 +1652,455 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_batch_kernel(
     small_rollout_body<E, ACT, H0, false>(a, hd, RoNoEval{});
 }
 
+// ---------------------------------------------------------------------------------------------
+// K33 — the closing of a K32 / K32W rollout in one launch (one workgroup per agent): the critic over the deferred
+// bootstrap rows, bootstrap_fixup_kernel's writes and the advantage scan (xpa_gae_scan's recurrence on the dense
+// closure record).
+// The critic pass is K32's forward restated (K32's own code is left as it is): the same weight registers, the same
+// fmaf chain over ascending d, the same MFMA tiling with every unit tile (the actor's too: they add the exact +0
+// terms they add in K32), the same per-lane fmaf over the lane's tiles, ro_row_sum16 and bc + wave 0 + .. + wave 3,
+// so a row's value is bit for bit what K32 writes into buf_val for that normalised row.  Only the value output is
+// formed (each output's sum is independent of the others).  The observation width is a run-time 1 .. 8 here (the
+// kernel does not depend on the env): the first layer's chain is unrolled to 8 and steps d >= D are skipped, not
+// added as zeros.  The rows go through LDS in passes of n_envs, so ro_layout(n_envs, ...) is the budget.
+// Thread n then owns env n's bootstraps: it writes them into boot (the fixup), and after a barrier the four waves scan
+// the rows with xpa_gae_scan's own dense forms, restated below over a wave index instead of a grid: a row is a segment
+// of L lanes, 4 steps per lane in 16-B accesses (T % 4 == 0 and 16-B aligned tensors: every rollout buffer; the DPP
+// form for T > 32), the same affine compositions in the same order, so adv / ret are what xpa_gae_scan gives on the
+// same record.  (gae.hip's kernels are left as they are: moving their bodies into shared device functions changed
+// their ISA.)  The problem is latency-bound (8 x 128 .. 10 x 256 elements per agent).
+// ---------------------------------------------------------------------------------------------
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ float ro_dpp_mov(float old, float src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old),
+                                                                 __builtin_bit_cast(int, src), CTRL, ROW_MASK, 0xf,
+                                                                 false));
+}
+// v of lane src of the wave (a ds_bpermute lane read)
+__device__ __forceinline__ float ro_lane(float v, int src) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ int ro_lane(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
+constexpr int kRoDppRowShr = 0x110, kRoDppWaveShr1 = 0x138, kRoDppRowBcast15 = 0x142, kRoDppRowBcast31 = 0x143;
+
+// (LA, LB) <- (LA, LB) o the map CTRL brings in; disabled / out-of-row lanes bring the identity.  FUSED: LB + LA oB
+// rounded once (fma) or twice — see the note on roundings below.
+template <int CTRL, int ROW_MASK, bool FUSED>
+__device__ __forceinline__ void ro_dpp_combine(float &LA, float &LB) {
+#pragma clang fp contract(off)
+    const float oA = ro_dpp_mov<CTRL, ROW_MASK>(1.f, LA);
+    const float oB = ro_dpp_mov<CTRL, ROW_MASK>(0.f, LB);
+    LB = FUSED ? fmaf(LA, oB, LB) : LB + LA * oB;
+    LA = LA * oA;
+}
+
+struct RoScanArgs {
+    const float *rew, *val, *term;
+    const uint8_t *closed;
+    const float *boot;
+    int n_rows, T;
+    float gamma, gl;
+    int use_gae;
+    float *adv, *ret;
+};
+
+// Roundings: the compiler is free to fuse x + a b into an fma, and xpa_gae_scan's compiled kernels fuse every one but
+// two — in the DPP form, the segment scan's last combine and `first` (the two products become one packed multiply).
+// The restatements below fix exactly those choices (contraction off, fmaf where gae.hip's kernels fuse), so that K33's
+// adv / ret are xpa_gae_scan's to the last bit on the same record; tests/test_gpu_small_close.py compares them.
+// Maintenance: the fused and non-fused spots are read off gae.hip's ISA as one compiler builds it.  If that test fails
+// after a toolchain change with neither source changed, re-derive them from the new ISA of gae_scan_kernel<., ., 0>
+// and gae_dpp_kernel<., 0> (v_fma / v_fmac against v_mul + v_add, v_pk_mul) and place fmaf accordingly; and any change
+// to gae.hip's scan arithmetic has to be mirrored here.
+// gae_scan_kernel<VEC, ., COMPACT = 0> (gae.hip) for the rows of wave index `wave`: lane sl of a row's L = 1 <<
+// seg_log2 lanes owns VEC consecutive steps, chunks of L * VEC steps from the row's end with a register carry, the
+// segmented scan on lane shuffles.  VEC = 4 takes T % 4 == 0 and 16-B aligned tensors.
+template <int VEC>
+__device__ __forceinline__ void ro_gae_scan_rows(const RoScanArgs &g, int wave, int seg_log2) {
+#pragma clang fp contract(off)
+    const int T = g.T;
+    const int L = 1 << seg_log2;
+    const int lane = threadIdx.x & 63;
+    const int sl = lane & (L - 1);
+    const int row = wave * (64 >> seg_log2) + (lane >> seg_log2);
+    const bool row_ok = row < g.n_rows;
+    const int64_t base = row_ok ? row * (int64_t)T : 0;
+    const int C = L * VEC;
+    const int nchunks = (T + C - 1) / C;
+    float carry = 0.f, carry_v = 0.f;
+    int carry_any = 0;
+    for (int c = nchunks - 1; c >= 0; --c) {
+        const int t0 = c * C + sl * VEC;
+        float r[VEC], v[VEC], d[VEC], bt[VEC];
+        int cl[VEC];
+        const bool full = row_ok && (t0 + VEC <= T);
+        if (VEC == 4 && full) {
+            const float4 r4 = *reinterpret_cast<const float4 *>(g.rew + base + t0);
+            const float4 v4 = *reinterpret_cast<const float4 *>(g.val + base + t0);
+            const float4 d4 = *reinterpret_cast<const float4 *>(g.term + base + t0);
+            const uint32_t c4 = *reinterpret_cast<const uint32_t *>(g.closed + base + t0);
+            const float4 q4 = *reinterpret_cast<const float4 *>(g.boot + base + t0);
+            bt[0] = q4.x; bt[1] = q4.y; bt[2] = q4.z; bt[3] = q4.w;
+            r[0] = r4.x; r[1] = r4.y; r[2] = r4.z; r[3] = r4.w;
+            v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
+            d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
+            cl[0] = c4 & 0xff; cl[1] = (c4 >> 8) & 0xff; cl[2] = (c4 >> 16) & 0xff; cl[3] = c4 >> 24;
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const int t = t0 + e;
+                const bool ok = row_ok && t < T;
+                r[e] = ok ? g.rew[base + t] : 0.f;
+                v[e] = ok ? g.val[base + t] : 0.f;
+                d[e] = ok ? g.term[base + t] : 0.f;
+                cl[e] = ok ? (int)g.closed[base + t] : 0;
+                bt[e] = cl[e] ? g.boot[base + t] : 0.f;
+            }
+        }
+        // v_{t+1} of this lane's last element: the next lane's first v, or the later chunk's
+        const int seg0 = lane & ~(L - 1);
+        // (a lane whose partner would lie past the row's segment reads itself and does not use the value)
+        float vn_lane = ro_lane(v[0], sl + 1 < L ? lane + 1 : lane);
+        if (sl == L - 1) vn_lane = carry_v;
+        float a[VEC], b[VEC], adv_direct[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const int t = t0 + e;
+            const bool ok = row_ok && t < T;
+            const float vnext = (e < VEC - 1) ? v[e + 1] : vn_lane;
+            const float nv = cl[e] ? bt[e] : vnext;
+            const float nd = 1.0f - d[e];
+            if (g.use_gae) {
+                b[e] = fmaf(g.gamma * nd, nv, r[e]) - v[e];
+                a[e] = cl[e] ? 0.f : g.gl * nd;
+            } else {
+                b[e] = r[e] + (cl[e] ? g.gamma * bt[e] : 0.f);
+                a[e] = cl[e] ? 0.f : g.gamma;
+                adv_direct[e] = fmaf(g.gamma, nv, r[e]) - v[e];
+            }
+            if (!ok) { a[e] = 1.f; b[e] = 0.f; }
+        }
+        float LA = 1.f, LB = 0.f;   // the lane's own composition (last element first)
+        int lany = 0;
+#pragma unroll
+        for (int e = VEC - 1; e >= 0; --e) {
+            LB = fmaf(a[e], LB, b[e]);
+            LA = a[e] * LA;
+            lany |= cl[e];
+        }
+        for (int o = 1; o < L; o <<= 1) {   // segmented reverse inclusive scan across the row's lanes
+            const int src = sl + o < L ? lane + o : lane;
+            const float oA = ro_lane(LA, src);
+            const float oB = ro_lane(LB, src);
+            const int oany = ro_lane(lany, src);
+            if (sl + o < L) {
+                LB = fmaf(LA, oB, LB);
+                LA = LA * oA;
+                lany |= oany;
+            }
+        }
+        const float first = fmaf(LA, carry, LB);
+        const int any_first = lany | carry_any;
+        float nxt = ro_lane(first, sl + 1 < L ? lane + 1 : lane);
+        int nany = ro_lane(any_first, sl + 1 < L ? lane + 1 : lane);
+        if (sl == L - 1) {
+            nxt = carry;
+            nany = carry_any;
+        }
+        float oa[VEC], orr[VEC];
+        int wr[VEC];
+#pragma unroll
+        for (int e = VEC - 1; e >= 0; --e) {
+            const float x = fmaf(a[e], nxt, b[e]);
+            const int anyc = cl[e] | nany;
+            if (g.use_gae) {
+                oa[e] = x;
+                orr[e] = x + v[e];
+            } else {
+                oa[e] = adv_direct[e];
+                orr[e] = x;
+            }
+            wr[e] = anyc && row_ok && (t0 + e < T);
+            nxt = x;
+            nany = anyc;
+        }
+        if (VEC == 4 && full && wr[0] && wr[1] && wr[2] && wr[3]) {
+            *reinterpret_cast<float4 *>(g.adv + base + t0) = make_float4(oa[0], oa[1], oa[2], oa[3]);
+            *reinterpret_cast<float4 *>(g.ret + base + t0) = make_float4(orr[0], orr[1], orr[2], orr[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e)
+                if (wr[e]) {
+                    g.adv[base + t0 + e] = oa[e];
+                    g.ret[base + t0 + e] = orr[e];
+                }
+        }
+        carry = ro_lane(first, seg0);
+        carry_v = ro_lane(v[0], seg0);
+        carry_any = ro_lane(any_first, seg0);
+    }
+}
+
+// gae_dpp_kernel<SEG_LOG2, COMPACT = 0> (gae.hip; T > 32, T % 4 == 0, 16-B aligned) for the rows of wave index `wave`:
+// the lane order reversed inside a row segment (lane sl owns the 4 steps from c C + (L - 1 - sl) 4), so the reverse
+// scan in time is a forward scan in lane order on DPP moves.
+template <int SEG_LOG2>
+__device__ __forceinline__ void ro_gae_dpp_rows(const RoScanArgs &g, int wave) {
+#pragma clang fp contract(off)
+    constexpr int L = 1 << SEG_LOG2;
+    constexpr int C = 4 * L;
+    const int T = g.T;
+    const int lane = threadIdx.x & 63;
+    const int sl = lane & (L - 1);
+    const int seg_base = lane & ~(L - 1);
+    const int row = wave * (64 / L) + (lane >> SEG_LOG2);
+    const bool row_ok = row < g.n_rows;
+    const int64_t base = row_ok ? row * (int64_t)T : 0;
+    const int nchunks = (T + C - 1) / C;
+    const uint64_t seg_mask = (L == 64) ? ~0ull : ((1ull << L) - 1ull);
+    float carry = 0.f, carry_v = 0.f;
+    bool carry_any = false;
+    for (int c = nchunks - 1; c >= 0; --c) {
+        const int t0 = c * C + (L - 1 - sl) * 4;
+        const bool in = row_ok && t0 < T;   // T % 4 == 0: a lane's 4 steps are all in or all out
+        float r[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f}, d[4] = {0.f, 0.f, 0.f, 0.f};
+        float bt[4] = {0.f, 0.f, 0.f, 0.f};
+        bool cl[4] = {false, false, false, false};
+        if (in) {
+            const float4 r4 = *reinterpret_cast<const float4 *>(g.rew + base + t0);
+            const float4 v4 = *reinterpret_cast<const float4 *>(g.val + base + t0);
+            const float4 d4 = *reinterpret_cast<const float4 *>(g.term + base + t0);
+            const uint32_t c4 = *reinterpret_cast<const uint32_t *>(g.closed + base + t0);
+            const float4 q4 = *reinterpret_cast<const float4 *>(g.boot + base + t0);
+            r[0] = r4.x; r[1] = r4.y; r[2] = r4.z; r[3] = r4.w;
+            v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
+            d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
+            bt[0] = q4.x; bt[1] = q4.y; bt[2] = q4.z; bt[3] = q4.w;
+            cl[0] = (c4 & 0xff) != 0; cl[1] = ((c4 >> 8) & 0xff) != 0;
+            cl[2] = ((c4 >> 16) & 0xff) != 0; cl[3] = (c4 >> 24) != 0;
+        }
+        // v_{t+1} of this lane's last step = v[0] of the lane below it (it owns the following steps)
+        float vn = ro_dpp_mov<kRoDppWaveShr1>(0.f, v[0]);
+        if (sl == 0) vn = carry_v;
+        float a[4], b[4], adv_direct[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float vnext = (e < 3) ? v[e + 1] : vn;
+            const float nv = cl[e] ? bt[e] : vnext;
+            const float nd = 1.0f - d[e];
+            if (g.use_gae) {
+                b[e] = fmaf(g.gamma * nd, nv, r[e]) - v[e];
+                a[e] = cl[e] ? 0.f : g.gl * nd;
+            } else {
+                b[e] = r[e] + (cl[e] ? g.gamma * bt[e] : 0.f);
+                a[e] = cl[e] ? 0.f : g.gamma;
+            }
+            adv_direct[e] = fmaf(g.gamma, nv, r[e]) - v[e];
+            if (!in) { a[e] = 1.f; b[e] = 0.f; }
+        }
+        float LA = 1.f, LB = 0.f;
+        bool lany = false;
+#pragma unroll
+        for (int e = 3; e >= 0; --e) {
+            LB = fmaf(a[e], LB, b[e]);
+            LA = a[e] * LA;
+            lany |= cl[e];
+        }
+        // inclusive scan in lane order inside the segment (lower lanes = later steps)
+        ro_dpp_combine<kRoDppRowShr + 1, 0xf, true>(LA, LB);
+        ro_dpp_combine<kRoDppRowShr + 2, 0xf, true>(LA, LB);
+        ro_dpp_combine<kRoDppRowShr + 4, 0xf, true>(LA, LB);
+        ro_dpp_combine<kRoDppRowShr + 8, 0xf, (L > 16)>(LA, LB);
+        if (L >= 32) ro_dpp_combine<kRoDppRowBcast15, 0xa, (L > 32)>(LA, LB);
+        if (L == 64) ro_dpp_combine<kRoDppRowBcast31, 0xc, false>(LA, LB);
+        const float first = LB + LA * carry;   // A (or R) at this lane's first step (two roundings)
+        const uint64_t segbits = (__ballot(lany) >> seg_base) & seg_mask;
+        bool nany = carry_any || (segbits & ((1ull << sl) - 1ull)) != 0;
+        float nxt = ro_dpp_mov<kRoDppWaveShr1>(0.f, first);
+        if (sl == 0) nxt = carry;
+        float oa[4], orr[4];
+        bool wr[4];
+#pragma unroll
+        for (int e = 3; e >= 0; --e) {
+            const float x = fmaf(a[e], nxt, b[e]);
+            const bool anyc = cl[e] || nany;
+            oa[e] = g.use_gae ? x : adv_direct[e];
+            orr[e] = g.use_gae ? x + v[e] : x;
+            wr[e] = anyc && in;
+            nxt = x;
+            nany = anyc;
+        }
+        if (wr[0] && wr[1] && wr[2] && wr[3]) {
+            *reinterpret_cast<float4 *>(g.adv + base + t0) = make_float4(oa[0], oa[1], oa[2], oa[3]);
+            *reinterpret_cast<float4 *>(g.ret + base + t0) = make_float4(orr[0], orr[1], orr[2], orr[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (wr[e]) {
+                    g.adv[base + t0 + e] = oa[e];
+                    g.ret[base + t0 + e] = orr[e];
+                }
+        }
+        if (c > 0) {   // the earlier chunk continues from this chunk's first step (lane L - 1)
+            carry = ro_lane(first, seg_base + L - 1);
+            carry_v = ro_lane(v[0], seg_base + L - 1);
+            carry_any = carry_any || segbits != 0;
+        }
+    }
+}
+
+template <int ACT, int H0>
+__device__ __forceinline__ void small_close_body(const XpaSmallCloseArgs &args) {
+    const XpaSmallCloseArgs a = args;
+    extern __shared__ float lds[];
+    constexpr int DM = 8;   // the widest observation
+    const int tid = threadIdx.x;
+    const int N = a.n_envs, D = a.d_in, H1 = a.h1, H2 = a.h2, U = a.h1 + a.h2, T = a.horizon, S = a.n_slots;
+    const RoLayout L = ro_layout(N, D, H0, H1, H2, a.k);
+    float *sy = lds + L.sy, *sz = lds + L.sz;   // sz: the value's partial sums [wave][N]
+    constexpr bool WIDE = H0 == kRoWide;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int li = lane & 15, lq = lane >> 4;
+    constexpr int KK = H0 / 4, J = WIDE ? 4 : 2, KW = WIDE ? 1 : KK;
+    const int UT = U >> 4;
+    float w0k[KW][DM], b0k[KW];
+#pragma unroll
+    for (int kk = 0; kk < KW; ++kk) {
+        const int k = WIDE ? (tid & (kRoWide - 1)) : 4 * kk + lq;
+#pragma unroll
+        for (int d = 0; d < DM; ++d) w0k[kk][d] = d < D ? a.W0[k * D + d] : 0.f;
+        b0k[kk] = a.b0[k];
+    }
+    float bw[J][KK], b12[J], wc[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int tile = wave + 4 * j;
+        const bool tok = tile < UT;
+        const int u = tok ? 16 * tile + li : 0;
+        const bool actor = u < H1;
+        const float *wr = actor ? a.W1 + u * H0 : a.W2 + (u - H1) * H0;
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) bw[j][kk] = tok ? wr[4 * kk + lq] : 0.f;
+        b12[j] = tok ? (actor ? a.b1[u] : a.b2[u - H1]) : 0.f;
+        wc[j] = tok && !actor ? a.Wc[u - H1] : 0.f;
+    }
+    const float bc = a.bc[0];
+    const int64_t rbase = (int64_t)tid * T;   // thread n < N: env n's row
+    for (int k = 0; k <= S; ++k) {
+        if (k > 0) __syncthreads();   // the previous pass's rows and partial sums are read
+        for (int e = tid; e < N * D; e += kRoThreads) {
+            const int r = e / D, d = e % D;
+            sy[e] = a.rows[((int64_t)k * N + r) * a.ld_rows + d];
+        }
+        __syncthreads();
+        for (int r0 = 0; r0 < N; r0 += 16) {
+            ro_f32x4 acc[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) acc[j] = ro_f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (WIDE) {
+                float *sh = lds + L.sh;
+                if (r0 > 0) __syncthreads();   // the previous tile's A operands are read
+                const int u = tid & (kRoWide - 1), rh = tid >> 7;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int row = rh + 2 * i;
+                    const float *yr = sy + (r0 + row < N ? r0 + row : N - 1) * D;
+                    float z = b0k[0];
+#pragma unroll
+                    for (int d = 0; d < DM; ++d)
+                        if (d < D) z = fmaf(w0k[0][d], yr[d], z);   // ascending d
+                    sh[row * kRoWideP + (u & 3) * kRoWideQ + (u >> 2)] = ro_act<ACT>(z, a.slope);
+                }
+                __syncthreads();
+                const float *ap = sh + li * kRoWideP + lq * kRoWideQ;
+#pragma unroll
+                for (int k4 = 0; k4 < KK; k4 += 4) {
+                    const float4 a4 = *reinterpret_cast<const float4 *>(ap + k4);
+                    const float av[4] = {a4.x, a4.y, a4.z, a4.w};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+#pragma unroll
+                        for (int j = 0; j < J; ++j)
+                            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], bw[j][k4 + c], acc[j], 0, 0, 0);
+                }
+            } else {
+                const int ra = r0 + li < N ? r0 + li : N - 1;   // this lane's A row (rows past N: results unused)
+                float y[DM];
+#pragma unroll
+                for (int d = 0; d < DM; ++d) y[d] = d < D ? sy[ra * D + d] : 0.f;
+                float av[KK];
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) {
+                    float z = b0k[kk];
+#pragma unroll
+                    for (int d = 0; d < DM; ++d)
+                        if (d < D) z = fmaf(w0k[kk][d], y[d], z);   // ascending d
+                    av[kk] = ro_act<ACT>(z, a.slope);
+                }
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+                    for (int j = 0; j < J; ++j)
+                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bw[j][kk], acc[j], 0, 0, 0);
+            }
+            // D element r of lane (q, i): row r0 + 4 q + r, unit 16 tile + i
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float pv = 0.f;
+#pragma unroll
+                for (int j = 0; j < J; ++j) pv = fmaf(wc[j], ro_act<ACT>(acc[j][r] + b12[j], a.slope), pv);
+                pv = ro_row_sum16(pv);
+                const int m = r0 + 4 * lq + r;
+                if (li == 0 && m < N) sz[wave * N + m] = pv;
+            }
+        }
+        __syncthreads();
+        if (tid < N) {
+            float v = bc;
+            for (int w = 0; w < 4; ++w) v += sz[w * N + tid];
+            const int64_t sl = (int64_t)k * N + tid;
+            if (a.vboot_out) a.vboot_out[sl] = v;
+            if (k < S) {   // bootstrap_fixup_kernel's writes
+                const int t = a.slot_t[sl];
+                if (t >= 0 && t < T) a.boot[rbase + t] = v;
+                a.slot_t[sl] = -1;
+            } else {
+                a.boot[rbase + T - 1] = a.term[rbase + T - 1] != 0.f ? 0.f : v;
+            }
+        }
+    }
+    __syncthreads();   // the bootstraps in boot (global stores of this workgroup) are visible to its scan
+    // the advantage scan: xpa_gae_scan's choice of form, the four waves over the wave indices
+    const RoScanArgs g{a.rew, a.val, a.term, a.closed, a.boot, N, T, a.gamma, a.gamma * a.gae_lambda, a.use_gae,
+                       a.adv, a.ret};
+    const bool vec4 = T % 4 == 0 && ((((uintptr_t)a.rew | (uintptr_t)a.val | (uintptr_t)a.term | (uintptr_t)a.boot |
+                                       (uintptr_t)a.adv | (uintptr_t)a.ret) & 15) == 0) &&
+                      (((uintptr_t)a.closed & 3) == 0);
+    const int per_lane = vec4 ? T / 4 : T;
+    int seg_log2 = 0;
+    while ((1 << seg_log2) < per_lane && seg_log2 < 6) ++seg_log2;
+    const int rows_per_wave = 64 >> seg_log2;
+    for (int w = wave; w * rows_per_wave < N; w += kRoThreads / 64) {
+        if (!vec4) ro_gae_scan_rows<1>(g, w, seg_log2);
+        else if (seg_log2 == 4) ro_gae_dpp_rows<4>(g, w);
+        else if (seg_log2 == 5) ro_gae_dpp_rows<5>(g, w);
+        else if (seg_log2 == 6) ro_gae_dpp_rows<6>(g, w);
+        else ro_gae_scan_rows<4>(g, w, seg_log2);
+    }
+}
+
+template <int ACT, int H0>
+__global__ __launch_bounds__(kRoThreads) void small_close_kernel(XpaSmallCloseArgs a) {
+    small_close_body<ACT, H0>(a);
+}
+
+// The population form (xpa_small_close_batch): workgroup p closes agent p's rollout from its own block
+template <int ACT, int H0>
+__global__ __launch_bounds__(kRoThreads) void small_close_batch_kernel(const XpaSmallCloseArgs *__restrict__ blocks) {
+    const XpaSmallCloseArgs a = blocks[blockIdx.x];
+    small_close_body<ACT, H0>(a);
+}
+
 // xpa_eval_post: one workgroup walks the envs in passes of kEvalThreads, so a step's entries land in env order (lane
 // offset from the wave's ballot, wave offset from the pass's wave totals, pass offset carried along).
 constexpr int kEvalThreads = 1024;
@@ -2361,6 +2810,75 @@ XPA_API int xpa_small_rollout_batch(int env, int64_t n_agents, const XpaSmallRol
     default:
         return (int)hipErrorInvalidValue;
     }
+}
+
+// ---- K33 -------------------------------------------------------------------------------------------
+namespace {
+// The argument checks of one agent's closing block (host only: no HIP call)
+bool ro_close_args_ok(const XpaSmallCloseArgs *a) {
+    if (!a || a->n_envs <= 0 || a->n_envs > 256 || a->horizon <= 0 || a->d_in < 1 || a->d_in > 8 ||
+        !ro_widths_ok(a->h0, a->h1, a->h2) || a->k < 1 || a->k > 3 || a->act_code < 0 || a->act_code > 2 ||
+        a->n_slots < 1 || a->n_slots > a->horizon || a->ld_rows < a->d_in)
+        return false;
+    if (!a->W0 || !a->b0 || !a->W1 || !a->b1 || !a->W2 || !a->b2 || !a->Wa || !a->ba || !a->Wc || !a->bc || !a->rows ||
+        !a->slot_t || !a->rew || !a->val || !a->term || !a->closed || !a->boot || !a->adv || !a->ret)
+        return false;
+    const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
+    return lf >= 0 && lf <= kRoLdsMax;
+}
+
+// Every non-pointer field: what one instantiation, one LDS carve and one set of scalars share
+bool ro_close_same_shape(const XpaSmallCloseArgs &x, const XpaSmallCloseArgs &y) {
+    return x.n_envs == y.n_envs && x.horizon == y.horizon && x.d_in == y.d_in && x.h0 == y.h0 && x.h1 == y.h1 &&
+           x.h2 == y.h2 && x.k == y.k && x.act_code == y.act_code && x.n_slots == y.n_slots &&
+           x.use_gae == y.use_gae && x.slope == y.slope && x.gamma == y.gamma && x.gae_lambda == y.gae_lambda &&
+           x.ld_rows == y.ld_rows;
+}
+
+// one: the single agent's block (by value); else n_agents blocks in device memory.  a: the (first) host block, checked.
+int small_close_launch(const XpaSmallCloseArgs *a, int64_t n_agents, const XpaSmallCloseArgs *dev, bool one,
+                       xpa_stream_t stream) {
+    const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
+    const size_t bytes = (size_t)lf * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+#define XPA_RC_LAUNCH(ACT, H0)                                                                                     \
+    do {                                                                                                           \
+        if (one)                                                                                                   \
+            hipLaunchKernelGGL((small_close_kernel<ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a);            \
+        else                                                                                                       \
+            hipLaunchKernelGGL((small_close_batch_kernel<ACT, H0>), dim3((unsigned)n_agents), dim3(kRoThreads),    \
+                               bytes, s, dev);                                                                     \
+    } while (0)
+    if (a->h0 == kRoWide) {   // K32W's forward
+        if (a->act_code == 0) XPA_RC_LAUNCH(0, kRoWide);
+        else if (a->act_code == 1) XPA_RC_LAUNCH(1, kRoWide);
+        else XPA_RC_LAUNCH(2, kRoWide);
+    } else if (a->h0 == 64) {
+        if (a->act_code == 0) XPA_RC_LAUNCH(0, 64);
+        else if (a->act_code == 1) XPA_RC_LAUNCH(1, 64);
+        else XPA_RC_LAUNCH(2, 64);
+    } else {
+        if (a->act_code == 0) XPA_RC_LAUNCH(0, 32);
+        else if (a->act_code == 1) XPA_RC_LAUNCH(1, 32);
+        else XPA_RC_LAUNCH(2, 32);
+    }
+#undef XPA_RC_LAUNCH
+    return xpa_launch_status();
+}
+}  // namespace
+
+XPA_API int xpa_small_close(const XpaSmallCloseArgs *a, xpa_stream_t stream) {
+    if (!ro_close_args_ok(a)) return (int)hipErrorInvalidValue;
+    return small_close_launch(a, 1, nullptr, true, stream);
+}
+
+XPA_API int xpa_small_close_batch(int64_t n_agents, const XpaSmallCloseArgs *host_blocks,
+                                  const XpaSmallCloseArgs *dev_blocks, xpa_stream_t stream) {
+    if (n_agents < 1 || n_agents > 65535 || !host_blocks || !dev_blocks) return (int)hipErrorInvalidValue;
+    for (int64_t p = 0; p < n_agents; ++p)
+        if (!ro_close_args_ok(host_blocks + p) || !ro_close_same_shape(host_blocks[p], host_blocks[0]))
+            return (int)hipErrorInvalidValue;
+    return small_close_launch(host_blocks, n_agents, dev_blocks, false, stream);
 }
 
 // ---- device evaluation: K32E and the generic tier's per-step log writer ---------------------------------------------

@@ -1506,6 +1506,56 @@ def bootstrap_fixup(values, slot_t, buf_term, buf_boot):
               _stream(values.device))
 
 
+def small_close_args(layers, act, rows, slot_t, rew, val, term, closed, boot, adv, ret, gamma, gae_lambda,
+                     use_gae=True, vboot_out=None):
+    """K33's argument block (XpaSmallCloseArgs) of one agent.  layers: the five Linear modules (representation, actor
+    hidden, actor out, critic hidden, critic out) of learner.small_policy_layers, act = (code, slope); rows
+    [(S + 1) N, d_in] the normalised deferred bootstrap rows (slot-major, then the last-step rows; row-strided allowed);
+    slot_t [S N]; rew / val / term / boot / adv / ret float32 [N, T], closed uint8 [N, T]; vboot_out (optional)
+    float32 [(S + 1) N].  The block holds the tensors' addresses and, as a Python object, references that keep them
+    alive (a byte copy of it does not)."""
+    l0, l1, la, l2, lc = layers
+    N, T = rew.shape
+    S = _n_slots(slot_t, N)
+    D = l0.in_features
+    for name, t in (("rew", rew), ("val", val), ("term", term), ("boot", boot), ("adv", adv), ("ret", ret)):
+        _req(t, name, torch.float32, (N, T))
+    _req(closed, "closed", torch.uint8, (N, T))
+    _req(rows, "rows", torch.float32, contiguous=False)
+    ld = _row_stride(rows, "rows", D)
+    if rows.shape[0] != (S + 1) * N:
+        raise ValueError("rows must hold (n_slots + 1) x n_envs rows")
+    if vboot_out is not None:
+        _req(vboot_out, "vboot_out", torch.float32, ((S + 1) * N,))
+    a = _lib.XpaSmallCloseArgs()
+    a.n_envs, a.horizon, a.d_in, a.h0, a.h1, a.h2, a.k = N, T, D, l0.out_features, l1.out_features, l2.out_features, \
+        la.out_features
+    a.act_code, a.n_slots, a.use_gae = int(act[0]), S, int(bool(use_gae))
+    a.slope, a.gamma, a.gae_lambda = float(act[1]), float(gamma), float(gae_lambda)
+    for name, lin in (("0", l0), ("1", l1), ("2", l2), ("a", la), ("c", lc)):
+        _req(lin.weight, "W" + name, torch.float32)
+        _req(lin.bias, "b" + name, torch.float32)
+        setattr(a, "W" + name, _p(lin.weight))
+        setattr(a, "b" + name, _p(lin.bias))
+    a.rows, a.ld_rows, a.slot_t = _p(rows), ld, _p(slot_t)
+    a.rew, a.val, a.term, a.closed = _p(rew), _p(val), _p(term), _p(closed)
+    a.boot, a.adv, a.ret, a.vboot_out = _p(boot), _p(adv), _p(ret), _p(vboot_out)
+    a._keep = (layers, rows, slot_t, rew, val, term, closed, boot, adv, ret, vboot_out)
+    return a
+
+
+def small_close(block, device):
+    """K33 (xpa_small_close): one agent's closing — the deferred bootstraps' critic with K32's arithmetic, the
+    fixup's writes and the advantage scan — in one launch.  block: small_close_args'."""
+    _lib.call(lib().xpa_small_close, ctypes.byref(block), _stream(device))
+
+
+def small_close_batch(n_agents, host_blocks, dev_blocks, device):
+    """K33 for a population (xpa_small_close_batch): host_blocks a ctypes array of XpaSmallCloseArgs, dev_blocks its
+    copy in device memory (a uint8 tensor)."""
+    _lib.call(lib().xpa_small_close_batch, n_agents, ctypes.addressof(host_blocks), _p(dev_blocks), _stream(device))
+
+
 def dqn_td_loss(evalQ, targetQ, act, rew, term, gamma, dQ=None, td_abs=None, scalars=None, err=None):
     """K19 (xpa_dqn_td_loss): the PER-DQN TD target / MSE loss / d loss d evalQ / |TD| of one batch
     (perdqn_learner.py:23-30).  evalQ / targetQ [B, A] f32 (row-strided allowed), act / rew / term [B] f32.

@@ -40,6 +40,7 @@ class MemberFacts(NamedTuple):
     t: int               # steps of the current rollout already taken
     scalars: tuple       # ((name, value), ...): the hyper-parameters that are kernel-argument scalars
     tensors: tuple       # data pointers of every tensor the launches write for this member
+    gae: str = None      # the member's RolloutPlan.gae: the closing's form ("K33": one batch launch for the population)
 
 
 class PopulationPlan(NamedTuple):
@@ -48,9 +49,11 @@ class PopulationPlan(NamedTuple):
     env: str             # its XPA_ENV_* constant's name
     gaussian: bool       # the head arrays (logstd, act_clip / logstd, g_logstd) are passed
     chunk: int
+    close_batch: bool = False   # the closing is one xpa_small_close_batch launch (every member plans gae "K33")
 
 
-_SHARED = ("entry", "dims", "activation", "algo", "n_envs", "n_steps", "n_epoch", "batch_size", "device", "chunk", "t")
+_SHARED = ("gae", "entry", "dims", "activation", "algo", "n_envs", "n_steps", "n_epoch", "batch_size", "device", "chunk",
+           "t")
 
 
 def plan_population(facts):
@@ -87,7 +90,8 @@ def plan_population(facts):
             if ptr in seen and seen[ptr] != i:
                 raise ValueError("members %d and %d share a tensor (data pointer 0x%x)" % (seen[ptr], i, ptr))
             seen[ptr] = i
-    return PopulationPlan(len(facts), f0.entry, _ENV_CODE[f0.entry], f0.entry == "xpa_small_rollout_pendulum", f0.chunk)
+    return PopulationPlan(len(facts), f0.entry, _ENV_CODE[f0.entry], f0.entry == "xpa_small_rollout_pendulum", f0.chunk,
+                          f0.gae == "K33")
 
 
 def _block_array(struct, blocks):
@@ -211,7 +215,7 @@ class Population:
             ts = [fused.fs.param, fused.fs.flat, fused.exp_avg, fused.exp_avg_sq, mem.observations, mem.actions,
                   mem.values, mem.rewards, mem.terminals, mem.closed, mem.boot, env.state, env.obs, env.act_in,
                   a.obs_mean, a.obs_var, a.obs_count, a.ret_mean, a.ret_var, a.ret_count, a.returns, a.cursor,
-                  a.obs_norm, a._boot_pair, a.slot_t]
+                  a.obs_norm, a._boot_pair, a.slot_t, mem._advantages, mem._returns]
             tensors = tuple(int(t.data_ptr()) for t in ts)
         g = L.optimizer.param_groups[0]
         scalars = (("use_obsnorm", a.use_obsnorm), ("use_rewnorm", a.use_rewnorm), ("obs_clip", float(a._obs_clip())),
@@ -223,9 +227,11 @@ class Population:
                    ("max_norm", float(L._max_norm) if L._use_clip else -1.0), ("betas", tuple(map(float, g["betas"]))),
                    ("eps", float(g["eps"])), ("small_split", bool(L.small_split)),
                    ("graph_updates", bool(L.graph_updates)))
+        if plan.gae == "K33":   # K33's scalars: one value per batch launch
+            scalars += (("gae_lam", float(mem.gae_lam)), ("use_gae", bool(mem.use_gae)))
         entry = plan.step_launches()[0] if k32 else None
         return MemberFacts(plan.driver, plan.feed, entry, plan.chunk, dims, act, a.algo, a.n_envs, a.n_steps, a.n_epoch,
-                           a.batch_size, str(a.device), a.world, a._t, scalars, tensors)
+                           a.batch_size, str(a.device), a.world, a._t, scalars, tensors, plan.gae)
 
     def plan(self):
         """The PopulationPlan of the members as they stand (cached under the members' own plans and positions)."""
@@ -258,6 +264,15 @@ class Population:
         _lib.call(lib.xpa_small_rollout_batch, _lib.ENV_CODES[plan.env], len(blocks), ctypes.addressof(host),
                   dev.data_ptr(), None if hh is None else ctypes.addressof(hh), None if hd is None else hd.data_ptr(),
                   ops._stream(self.device))
+
+    def _close_launch(self):
+        """Every member's closing (agent._close_rollout's "K33" form) in one launch (xpa_small_close_batch) over the
+        members' own blocks, then the host state each member's own launch leaves."""
+        from . import _lib, ops
+        host, dev = self._blocks.get(_block_array(_lib.XpaSmallCloseArgs, [a._small_close_block() for a in self.agents]))
+        ops.small_close_batch(len(self.agents), host, dev, self.device)
+        for a in self.agents:
+            a._closed_small()
 
     def _permutations(self, n):
         """Row p: member p's next epoch permutation (agent.epoch_permutation), all in one launch."""
@@ -351,11 +366,15 @@ class Population:
 
     def _update_phase(self):
         """agent._update_phase for every member: each closes its own rollout (bootstrap critic pass + GAE, the code it
-        runs alone), then per epoch one permutation launch and the minibatch slots' batch launches."""
+        runs alone) or, where every member plans the "K33" closing, one batch launch closes them all; then per epoch
+        one permutation launch and the minibatch slots' batch launches."""
         import torch
         agents = self.agents
-        for a in agents:
-            a._close_rollout()
+        if self._plan.close_batch:   # train()'s plan of this iteration
+            self._close_launch()
+        else:
+            for a in agents:
+                a._close_rollout()
         if self.phase_events is not None:
             self.phase_events.append(("close_end", torch.cuda.Event(enable_timing=True)))
             self.phase_events[-1][1].record()

@@ -60,6 +60,7 @@ class RolloutFacts(NamedTuple):
     small_update: bool        # learner.small_update_ok (K30)
     epoch_graphs: bool        # learner.graph_updates
     dist: str = "categorical"  # the head's distribution: "categorical" | "gaussian" (K32's instantiation)
+    small_close: bool = False  # the switch: a one-launch small-path rollout closes in one launch (K33)
 
 
 _RMS = {None: (), "standalone": ("xpa_rms_update",), "all-reduce": ("xpa_rms_partials", "xpa_rms_merge"),
@@ -89,6 +90,9 @@ _CLOSE = {None: (), "raw-last": ("xpa_rollout_bootstrap_fixup",), "raw-mid-next"
 _GAE = {"K40V+compact": ("xpa_s3_gemm_value", "xpa_gae_scan_compact"), "value": ("xpa_gae_scan_value",),
         "compact": ("xpa_gae_scan_compact",), "fixup+scan": ("xpa_rollout_bootstrap_fixup", "xpa_gae_scan"),
         "scan": ("xpa_gae_scan",)}
+# close_launches' scan table: _GAE (whose keys test_rollout_plan_cpu's invariants require the planner to emit over its
+# own product of switches) and the opt-in form added since
+_GAE_CLOSE = dict(_GAE, K33=("xpa_small_close",))
 _FEED = {"rows": (), "small": (), "epoch": (), "slot": (), "all-reduce": ("xpa_gather_minibatch",)}
 
 
@@ -109,7 +113,8 @@ class RolloutPlan(NamedTuple):
     boot: str          # "slots" | "per-step" | "zero"
     mid: object        # A2C's mid-rollout bootstraps: None | "critic" | "next-column" | "slots-from-next"
     close: object      # None | "raw-last" | "raw-mid-next"
-    gae: str           # "K40V+compact" | "value" | "compact" | "fixup+scan" | "scan"
+    gae: str           # "K40V+compact" | "value" | "compact" | "fixup+scan" | "scan" | "K33" (small_close: the critic
+                       # pass, the fixup and the scan in one launch)
     feed: str          # "rows" | "small" | "epoch" | "slot" | "all-reduce"
 
     def _values(self):
@@ -140,11 +145,13 @@ class RolloutPlan(NamedTuple):
     def close_launches(self):
         """The library entry points from the end of the last step up to the first update call."""
         out = list(_CLOSE[self.close])
+        if self.gae == "K33":   # the deferred rows' critic pass is inside the launch
+            return out + list(_GAE_CLOSE[self.gae]) + ["xpa_random_permutation"] + list(_FEED[self.feed])
         if self.gae in ("K40V+compact", "value"):   # (value: + the critic's hidden layer, a library GEMM)
             out += _TRUNK[self.value_trunk]
         elif self.boot == "slots":
             out += self._values()
-        out += _GAE[self.gae]
+        out += _GAE_CLOSE[self.gae]
         out.append("xpa_random_permutation")
         return out + list(_FEED[self.feed])
 
@@ -201,6 +208,9 @@ def plan_rollout(f):
         gae = "value"
     else:
         gae = "compact" if one else "fixup+scan" if f.defer_boot else "scan"
+    # K33 (opt-in): the closing of a one-launch small-path rollout in one launch, the bootstraps in K32's arithmetic
+    if f.small_close and driver in K32_DRIVERS and f.defer_boot and not f.atari and not f.pending and close is None:
+        gae = "K33"
     if f.global_advnorm and f.world > 1:
         feed = "all-reduce"
     else:
