@@ -26,7 +26,6 @@ CPU generator; the truncation bootstrap value V(norm(final obs)) is computed for
 all finished envs of a step in one Chan update (mathematically equal to the reference's sequential
 single-value updates).
 """
-import ctypes
 import json
 import os
 import time
@@ -34,7 +33,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, graphs, ops
+from . import _lib, graphs, ops, small_path
 from .buffer import DummyOnPolicyBuffer, DummyOnPolicyBuffer_Atari
 from .fused_mlp import FusedActorCritic, Rows, _no_form
 from .learners import A2C_Learner, PerDQN_Learner, PPOCLIP_Learner
@@ -188,7 +187,7 @@ class _OnPolicyAgent:
         self._rms_fold_part = None
         # K32: whole device env steps (RMS, normalise, forward, sample, env, post) in one launch (plan().driver)
         self.fused_rollout = bool(_cfg(config, "fused_rollout", True))
-        self._k32 = None                      # K32's argument block, rebuilt with the plan
+        self._k32 = None                      # K32's argument block (small_path.rollout), rebuilt with the plan
         # K33 (opt-in, plan().gae == "K33"): a one-launch small-path rollout closes in one launch, its bootstraps in
         # K32's own arithmetic
         self.small_close = bool(_cfg(config, "small_close", False))
@@ -344,7 +343,8 @@ class _OnPolicyAgent:
                *[p.data_ptr() for p in self._params])
         if key != self._plan_key:
             self._plan = plan_rollout(self._facts(fm, F, obs))
-            self._k32 = self._build_small_rollout() if self._plan.driver in K32_DRIVERS else None
+            self._k32, self._k32_launch, self._k32_head = \
+                small_path.rollout(self) if self._plan.driver in K32_DRIVERS else (None, None, None)
             self._k33 = self._build_small_close() if self._plan.gae == "K33" else None
             self._plan_key = key
         return self._plan
@@ -352,13 +352,8 @@ class _OnPolicyAgent:
     def _facts(self, fm, F, obs):
         """What plan_rollout decides from (rollout_plan.RolloutFacts), gathered when plan()'s key changes."""
         L, env, mem = self.learner, self.envs, self.memory
-        layers = L.small_policy_layers()
-        small = None
-        if layers is not None:
-            l0, l1, la, l2, _ = layers[0]
-            dims = (l0.in_features, l0.out_features, l1.out_features, l2.out_features, la.out_features)
-            small = dims + (int(ops.lib().xpa_small_rollout_lds_floats(self.n_envs, self.obs_dim, *dims[1:]))
-                            if self.device.type == "cuda" else 0,)
+        policy = L.small_policy_layers()
+        small = policy and policy.rollout_shape(self.n_envs, self.obs_dim, self.device.type == "cuda")
         bufs = (mem.observations, mem.actions, mem.values, mem.rewards, mem.terminals, mem.boot)
         obs_flat = mem.observations.reshape((self.buffer_size,) + tuple(mem.observations.shape[2:]))
         fusable = getattr(env, "fusable_with_policy_step", None)
@@ -508,50 +503,12 @@ class _OnPolicyAgent:
         self.obs_count.copy_(c)
         self._rms_c0 = None
 
-    def _build_small_rollout(self):
-        """K32's argument block (xpa_small_rollout_<env>) for a plan whose driver is K32 / K32W; plan() rebuilds
-        it when the parameters are re-homed (the block holds their pointers)."""
-        env, mem = self.envs, self.memory
-        (l0, l1, la, l2, lc), code, slope, self._k32_logstd = self.learner.small_policy_layers()
-        self._k32_entry, = self._plan.step_launches()
-        N, T, D = self.n_envs, self.n_steps, self.obs_dim
-        h0, h1, h2, k = l0.out_features, l1.out_features, l2.out_features, la.out_features
-        a = _lib.XpaSmallRolloutArgs()
-        a.n_envs, a.horizon, a.steps, a.d_in, a.h0, a.h1, a.h2, a.k = N, T, 1, D, h0, h1, h2, k
-        a.act_code, a.use_obsnorm, a.n_slots = int(code), int(self.use_obsnorm), int(self.n_slots)
-        a.mask_returns, a.use_rewnorm, a.max_episode_steps = int(self.algo == "ppo"), int(self.use_rewnorm), \
-            int(env.max_episode_steps)
-        a.slot_reset_obs = int(self.boot_from_reset)
-        a.slope, a.obs_clip, a.gamma, a.rew_range = float(slope), float(self._obs_clip()), float(self.gamma), \
-            float(self.rewnorm_range)
-        a.seed, a.env_seed = int(self.seed) & 0xFFFFFFFF, int(env.noise_seed) & 0xFFFFFFFF
-        p = ops._p
-        a.W0, a.b0, a.W1, a.b1, a.W2, a.b2 = (p(l0.weight), p(l0.bias), p(l1.weight), p(l1.bias), p(l2.weight),
-                                              p(l2.bias))
-        a.Wa, a.ba, a.Wc, a.bc = p(la.weight), p(la.bias), p(lc.weight), p(lc.bias)
-        a.obs_mean, a.obs_var, a.obs_count = p(self.obs_mean), p(self.obs_var), p(self.obs_count)
-        a.obs_norm, a.ld_norm = p(self.obs_norm), self.obs_norm.stride(0)
-        logp_buf = mem.auxiliary_infos["old_logp"] if self.algo == "ppo" else self.logp_scratch
-        a.buf_obs, a.buf_act, a.buf_logp, a.buf_val = p(mem.observations), p(mem.actions), p(logp_buf), p(mem.values)
-        a.buf_rew, a.buf_term, a.buf_closed, a.buf_boot = p(mem.rewards), p(mem.terminals), p(mem.closed), p(mem.boot)
-        a.act_in, a.ld_act = p(env.act_in), env.act_in.stride(0)
-        a.env_state, a.env_obs, a.ld_obs = p(env.state), p(env.obs), env.obs.stride(0)
-        a.final_obs, a.env_rew, a.env_term, a.env_trunc = p(env.final_obs), p(env.rew), p(env.term), p(env.trunc)
-        a.ep_step, a.ep_index, a.ep_score = p(env.ep_step), p(env.ep_index), p(env.ep_score)
-        a.ep_last_score, a.ep_last_len = p(env.ep_last_score), p(env.ep_last_len)
-        a.returns, a.ret_mean, a.ret_var, a.ret_count = p(self.returns), p(self.ret_mean), p(self.ret_var), \
-            p(self.ret_count)
-        a.slot_obs, a.slot_t, a.overflow = p(self.slot_obs), p(self.slot_t), p(self.slot_overflow)
-        a.boot_norm, a.ld_boot = p(self.boot_obs), self.boot_obs.stride(0)
-        a.cursor = p(self.cursor)
-        return a
-
     def _build_small_close(self):
         """K33's argument block (xpa_small_close) for a plan whose gae form is "K33": the policy's layers, the deferred
         bootstrap rows and the buffer's tensors; plan() rebuilds it with K32's block."""
         mem = self.memory
         layers, code, slope, _ = self.learner.small_policy_layers()
-        return ops.small_close_args(layers, (code, slope), self._boot_pair, self.slot_t, mem.rewards, mem.values,
+        return small_path.small_close_args(layers, (code, slope), self._boot_pair, self.slot_t, mem.rewards, mem.values,
                                     mem.terminals, mem.closed, mem.boot, mem._advantages, mem._returns, mem.gamma,
                                     mem.gae_lam, mem.use_gae)
 
@@ -564,14 +521,7 @@ class _OnPolicyAgent:
 
     def _small_rollout_launch(self, steps):
         self._k32.steps = int(steps)
-        if self._k32_entry in ("xpa_small_rollout_cartpole", "xpa_small_rollout_acrobot",
-                               "xpa_small_rollout_mountaincar"):   # Categorical heads: the block alone
-            _lib.call(getattr(ops.lib(), self._k32_entry), ctypes.byref(self._k32), ops._stream(self.device))
-        elif self._k32_entry == "xpa_small_rollout_pendulum":
-            _lib.call(ops.lib().xpa_small_rollout_pendulum, ctypes.byref(self._k32), ops._p(self._k32_logstd),
-                      self._act_clip(), ops._stream(self.device))
-        else:
-            _no_form("the one-launch rollout step", self._k32_entry)
+        self._k32_launch()
 
     def _rollout_step_device(self):
         env = self.envs
@@ -797,7 +747,7 @@ class _OnPolicyAgent:
             mem.compute_advantages()
         elif gae == "K33":
             # one launch: the deferred rows' critic in K32's arithmetic, the fixup's writes and the advantage scan
-            ops.small_close(self._small_close_block(), self.device)
+            small_path.small_close(self._small_close_block(), self.device)
             self._closed_small()
         elif gae == "value":
             # one launch: the critic's output layer, the fixup's bootstrap writes and the compact GAE scan
@@ -1017,13 +967,8 @@ class _OnPolicyAgent:
         """What plan_test decides from (rollout_plan.EvalFacts) for these test envs."""
         device = hasattr(test_envs, "step_device")
         n = int(test_envs.num_envs)
-        layers = self.learner.small_policy_layers()
-        small = None
-        if layers is not None:
-            l0, l1, la, l2, _ = layers[0]
-            dims = (l0.in_features, l0.out_features, l1.out_features, l2.out_features, la.out_features)
-            small = dims + (int(ops.lib().xpa_small_rollout_lds_floats(n, self.obs_dim, *dims[1:]))
-                            if self.device.type == "cuda" else 0,)
+        policy = self.learner.small_policy_layers()
+        small = policy and policy.rollout_shape(n, self.obs_dim, self.device.type == "cuda")
         return EvalFacts(cuda=self.device.type == "cuda", env=getattr(test_envs, "kind", "device") if device else "host",
                          dist=self.dist, small=small, n_envs=n, obs_dim=self.obs_dim, raw_obs=self.raw_obs,
                          world=self.world, sync_obs_rms=True if self.sync_obs_rms else
@@ -1043,27 +988,9 @@ class _OnPolicyAgent:
         return (int(self.seed) ^ EVAL_SALT) & 0xFFFFFFFF, self._eval_cursor
 
     def _build_small_eval(self, env, seed, cursor):
-        """K32E's argument block over the test envs: _build_small_rollout's weights, statistics and env fields; the
-        training-only pointers (buffer, returns, slots) stay NULL."""
-        (l0, l1, la, l2, lc), code, slope, logstd = self.learner.small_policy_layers()
-        a = _lib.XpaSmallRolloutArgs()
-        a.n_envs, a.horizon, a.steps, a.d_in = int(env.num_envs), 1, 1, self.obs_dim
-        a.h0, a.h1, a.h2, a.k = l0.out_features, l1.out_features, l2.out_features, la.out_features
-        a.act_code, a.use_obsnorm, a.max_episode_steps = int(code), int(self.use_obsnorm), int(env.max_episode_steps)
-        a.slope, a.obs_clip = float(slope), float(self._obs_clip())
-        a.seed, a.env_seed = int(seed) & 0xFFFFFFFF, int(env.noise_seed) & 0xFFFFFFFF
-        p = ops._p
-        a.W0, a.b0, a.W1, a.b1, a.W2, a.b2 = (p(l0.weight), p(l0.bias), p(l1.weight), p(l1.bias), p(l2.weight),
-                                              p(l2.bias))
-        a.Wa, a.ba, a.Wc, a.bc = p(la.weight), p(la.bias), p(lc.weight), p(lc.bias)
-        a.obs_mean, a.obs_var, a.obs_count = p(self.obs_mean), p(self.obs_var), p(self.obs_count)
-        a.act_in, a.ld_act = p(env.act_in), env.act_in.stride(0)
-        a.env_state, a.env_obs, a.ld_obs = p(env.state), p(env.obs), env.obs.stride(0)
-        a.final_obs, a.env_rew, a.env_term, a.env_trunc = p(env.final_obs), p(env.rew), p(env.term), p(env.trunc)
-        a.ep_step, a.ep_index, a.ep_score = p(env.ep_step), p(env.ep_index), p(env.ep_score)
-        a.ep_last_score, a.ep_last_len = p(env.ep_last_score), p(env.ep_last_len)
-        a.cursor = p(cursor)
-        return a, logstd
+        """K32E's argument block over the test envs (small_path.env_block) and the Gaussian head's logstd (or None)."""
+        policy = self.learner.small_policy_layers()
+        return small_path.env_block(self, policy, env, env.num_envs, 1, seed, cursor), policy.logstd
 
     @torch.no_grad()
     def _eval_step(self, env, ws, log, capacity, snap_dim, seed, cursor, act_clip):
@@ -1116,15 +1043,15 @@ class _OnPolicyAgent:
         capacity = target + N
         log = ops.eval_log_new(target, N, snap_dim, dev)
         bound = (target // N + 2) * max_ep
+        act_clip = 1.0 if self.discrete else _space_clip(env.action_space)
         if tier == "K32E":
             chunk = 128 if chunk is None else int(chunk)
             args, logstd = self._build_small_eval(env, seed, cursor)
-            args.steps = chunk
+            args.steps, entry = chunk, eval_entry(f)
             scratch = torch.empty((3 * N,), dtype=torch.float32, device=dev)
-            act_clip = 1.0 if self.discrete else _space_clip(env.action_space)
 
             def step():
-                ops.small_eval(eval_entry(f), args, log, capacity, snap_dim, scratch, logstd, act_clip)
+                small_path.small_eval(entry, args, log, capacity, snap_dim, scratch, logstd, act_clip)
         else:
             chunk = 8 if chunk is None else int(chunk)
             A = env.act_in.shape[1]
@@ -1135,7 +1062,6 @@ class _OnPolicyAgent:
                 ws["norm"] = torch.empty((N, self.obs_dim), **f32)
                 ws["part"] = torch.empty((2 * ops.rms_num_partials(N), self.obs_dim), dtype=torch.float64, device=dev)
                 ws["ticket"] = torch.zeros((1,), dtype=torch.int32, device=dev)
-            act_clip = 1.0 if self.discrete else _space_clip(env.action_space)
 
             def step():
                 for _ in range(chunk):

@@ -2638,6 +2638,23 @@ bool ro_widths_ok(int64_t h0, int64_t h1, int64_t h2) {
     return (h0 == 32 || h0 == 64) && (h1 == 32 || h1 == 64) && (h2 == 32 || h2 == 64);
 }
 
+// The one ladder over a checked block's (h0, act_code): launch(ACT, H0), both std::integral_constants, so that the
+// callee names its instantiation with decltype(ACT)::value / decltype(H0)::value.  WIDE: the 128-wide column (K32W)
+// exists for this kernel; without it h0 is 32 or 64 and no H0 = 128 instantiation is made (K32E).
+template <bool WIDE, class F>
+void ro_dispatch(int64_t h0, int act_code, F launch) {
+    auto by_act = [&](auto H0) {
+        if (act_code == 0) launch(std::integral_constant<int, 0>{}, H0);
+        else if (act_code == 1) launch(std::integral_constant<int, 1>{}, H0);
+        else launch(std::integral_constant<int, 2>{}, H0);
+    };
+    if constexpr (WIDE) {
+        if (h0 == kRoWide) return by_act(std::integral_constant<int, kRoWide>{});
+    }
+    if (h0 == 64) by_act(std::integral_constant<int, 64>{});
+    else by_act(std::integral_constant<int, 32>{});
+}
+
 // The checks and the launch shared by K32's entry points; E: the instantiation's env / head pair, k its head width.
 // K32E's checks and launch: only what the evaluation form dereferences is required (the training-only pointers of
 // XpaSmallRolloutArgs may be null); horizon 1 and the sampler's three stores into scratch [3 * n_envs]
@@ -2666,18 +2683,10 @@ int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd,
     const RoEval ev{log, capacity, eval_log_entries(snap_dim)};
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define XPA_RO_LAUNCH(ACT, H0) \
-    hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0, true>), dim3(1), dim3(kRoThreads), bytes, s, a, hd, ev)
-    if (a.h0 == 64) {
-        if (a.act_code == 0) XPA_RO_LAUNCH(0, 64);
-        else if (a.act_code == 1) XPA_RO_LAUNCH(1, 64);
-        else XPA_RO_LAUNCH(2, 64);
-    } else {
-        if (a.act_code == 0) XPA_RO_LAUNCH(0, 32);
-        else if (a.act_code == 1) XPA_RO_LAUNCH(1, 32);
-        else XPA_RO_LAUNCH(2, 32);
-    }
-#undef XPA_RO_LAUNCH
+    ro_dispatch<false>(a.h0, a.act_code, [&](auto ACT, auto H0) {
+        hipLaunchKernelGGL((small_rollout_kernel<E, decltype(ACT)::value, decltype(H0)::value, true>), dim3(1),
+                           dim3(kRoThreads), bytes, s, a, hd, ev);
+    });
     return xpa_launch_status();
 }
 
@@ -2706,22 +2715,10 @@ int small_rollout_launch(const XpaSmallRolloutArgs *a, int k, typename E::Head h
     const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define XPA_RO_LAUNCH(ACT, H0) \
-    hipLaunchKernelGGL((small_rollout_kernel<E, ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a, hd, RoNoEval{})
-    if (a->h0 == kRoWide) {   // K32W
-        if (a->act_code == 0) XPA_RO_LAUNCH(0, kRoWide);
-        else if (a->act_code == 1) XPA_RO_LAUNCH(1, kRoWide);
-        else XPA_RO_LAUNCH(2, kRoWide);
-    } else if (a->h0 == 64) {
-        if (a->act_code == 0) XPA_RO_LAUNCH(0, 64);
-        else if (a->act_code == 1) XPA_RO_LAUNCH(1, 64);
-        else XPA_RO_LAUNCH(2, 64);
-    } else {
-        if (a->act_code == 0) XPA_RO_LAUNCH(0, 32);
-        else if (a->act_code == 1) XPA_RO_LAUNCH(1, 32);
-        else XPA_RO_LAUNCH(2, 32);
-    }
-#undef XPA_RO_LAUNCH
+    ro_dispatch<true>(a->h0, a->act_code, [&](auto ACT, auto H0) {
+        hipLaunchKernelGGL((small_rollout_kernel<E, decltype(ACT)::value, decltype(H0)::value>), dim3(1),
+                           dim3(kRoThreads), bytes, s, *a, hd, RoNoEval{});
+    });
     return xpa_launch_status();
 }
 
@@ -2752,23 +2749,10 @@ int small_rollout_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host
     const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define XPA_RO_LAUNCH(ACT, H0)                                                                                   \
-    hipLaunchKernelGGL((small_rollout_batch_kernel<E, ACT, H0>), dim3((unsigned)n_agents), dim3(kRoThreads), bytes, \
-                       s, dev, dev_heads)
-    if (a->h0 == kRoWide) {   // K32W
-        if (a->act_code == 0) XPA_RO_LAUNCH(0, kRoWide);
-        else if (a->act_code == 1) XPA_RO_LAUNCH(1, kRoWide);
-        else XPA_RO_LAUNCH(2, kRoWide);
-    } else if (a->h0 == 64) {
-        if (a->act_code == 0) XPA_RO_LAUNCH(0, 64);
-        else if (a->act_code == 1) XPA_RO_LAUNCH(1, 64);
-        else XPA_RO_LAUNCH(2, 64);
-    } else {
-        if (a->act_code == 0) XPA_RO_LAUNCH(0, 32);
-        else if (a->act_code == 1) XPA_RO_LAUNCH(1, 32);
-        else XPA_RO_LAUNCH(2, 32);
-    }
-#undef XPA_RO_LAUNCH
+    ro_dispatch<true>(a->h0, a->act_code, [&](auto ACT, auto H0) {
+        hipLaunchKernelGGL((small_rollout_batch_kernel<E, decltype(ACT)::value, decltype(H0)::value>),
+                           dim3((unsigned)n_agents), dim3(kRoThreads), bytes, s, dev, dev_heads);
+    });
     return xpa_launch_status();
 }
 }  // namespace
@@ -2841,28 +2825,14 @@ int small_close_launch(const XpaSmallCloseArgs *a, int64_t n_agents, const XpaSm
     const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-#define XPA_RC_LAUNCH(ACT, H0)                                                                                     \
-    do {                                                                                                           \
-        if (one)                                                                                                   \
-            hipLaunchKernelGGL((small_close_kernel<ACT, H0>), dim3(1), dim3(kRoThreads), bytes, s, *a);            \
-        else                                                                                                       \
-            hipLaunchKernelGGL((small_close_batch_kernel<ACT, H0>), dim3((unsigned)n_agents), dim3(kRoThreads),    \
-                               bytes, s, dev);                                                                     \
-    } while (0)
-    if (a->h0 == kRoWide) {   // K32W's forward
-        if (a->act_code == 0) XPA_RC_LAUNCH(0, kRoWide);
-        else if (a->act_code == 1) XPA_RC_LAUNCH(1, kRoWide);
-        else XPA_RC_LAUNCH(2, kRoWide);
-    } else if (a->h0 == 64) {
-        if (a->act_code == 0) XPA_RC_LAUNCH(0, 64);
-        else if (a->act_code == 1) XPA_RC_LAUNCH(1, 64);
-        else XPA_RC_LAUNCH(2, 64);
-    } else {
-        if (a->act_code == 0) XPA_RC_LAUNCH(0, 32);
-        else if (a->act_code == 1) XPA_RC_LAUNCH(1, 32);
-        else XPA_RC_LAUNCH(2, 32);
-    }
-#undef XPA_RC_LAUNCH
+    ro_dispatch<true>(a->h0, a->act_code, [&](auto ACT, auto H0) {
+        constexpr int A = decltype(ACT)::value, H = decltype(H0)::value;
+        if (one)
+            hipLaunchKernelGGL((small_close_kernel<A, H>), dim3(1), dim3(kRoThreads), bytes, s, *a);
+        else
+            hipLaunchKernelGGL((small_close_batch_kernel<A, H>), dim3((unsigned)n_agents), dim3(kRoThreads), bytes, s,
+                               dev);
+    });
     return xpa_launch_status();
 }
 }  // namespace

@@ -16,12 +16,11 @@ all-reduce when data-parallel] -> clip_grad_norm_ -> optimizer.step -> scheduler
     backward) and K9 — no autograd graph (DESIGN.md §3).  update() returns host floats like the reference (one sync);
 update_fused() keeps everything on device for the agent's hot loop.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _lib, graphs, ops
+from . import _lib, graphs, ops, small_path
 from .fused_mlp import Rows
 from .policies import policy_discrete, policy_heads
 
@@ -302,10 +301,10 @@ class _FusedPolicyGradient(Learner):
 
     # ---- K30: the whole small-MLP update in one launch (C1) ----------------------------------------------------
     def small_policy_layers(self):
-        """((l0, l1, la, l2, lc), code, slope, logstd) when the policy is a Categorical or Gaussian actor-critic of one
-        representation layer and one hidden layer per head, all with the same activation — the shape K30 (update) and
-        K32 (rollout step) take — else None.  la: the logits layer, or the Gaussian's mu layer; logstd: the Gaussian's
-        parameter (None for a Categorical policy)."""
+        """small_path.SmallPolicy((l0, l1, la, l2, lc), code, slope, logstd) when the policy is a Categorical or Gaussian
+        actor-critic of one representation layer and one hidden layer per head, all with the same activation — the shape
+        K30 (update) and K32 (rollout step) take — else None.  la: the logits layer, or the Gaussian's mu layer; logstd:
+        the Gaussian's parameter (None for a Categorical policy)."""
         if self.dist not in ("categorical", "gaussian"):
             return None
         fm = self._fused_mlp()
@@ -317,7 +316,7 @@ class _FusedPolicyGradient(Learner):
             return None
         if (fm.logstd is None) != (self.dist == "categorical"):
             return None
-        return (l0, l1, la, l2, lc), c0, s0, fm.logstd
+        return small_path.SmallPolicy((l0, l1, la, l2, lc), c0, s0, fm.logstd)
 
     def small_update_ok(self, obs_flat, batch):
         """True when a minibatch of `batch` rows of obs_flat [n_rows, d] can take K30 (xpa_small_mlp_update, or
@@ -326,10 +325,10 @@ class _FusedPolicyGradient(Learner):
         if not self.small_updates or self.grad_sync is not None:
             return False
         fused = self.fused_opt
-        layers = self.small_policy_layers()
-        if layers is None or fused is None or fused.fs.numel % 4:
+        policy = self.small_policy_layers()
+        if policy is None or fused is None or fused.fs.numel % 4:
             return False
-        logstd = layers[3]
+        logstd = policy.logstd
         if logstd is not None:   # d logstd is written where clip + Adam read it: inside the flat gradient
             g, flat = logstd.grad, fused.fs.flat
             if g is None or not g.is_contiguous() or not \
@@ -338,44 +337,35 @@ class _FusedPolicyGradient(Learner):
         if not (isinstance(obs_flat, torch.Tensor) and obs_flat.is_cuda and obs_flat.dim() == 2
                 and obs_flat.dtype == torch.float32 and obs_flat.stride(1) == 1):
             return False
-        (l0, l1, la, l2, lc) = layers[0]
-        h0, h1, h2, k = l0.out_features, l1.out_features, l2.out_features, la.out_features
+        d_in, h0, h1, h2, k = dims = policy.dims
         if any(h % 32 or h > 256 for h in (h0, h1, h2)) or not (2 if logstd is None else 1) <= k <= 16 \
-                or l0.in_features != obs_flat.shape[1] \
-                or l0.in_features > 32:
+                or d_in != obs_flat.shape[1] or d_in > 32:
             return False
         rows = 32 if self.small_split and 32 < batch <= 512 else batch   # per workgroup
-        if int(ops.lib().xpa_small_mlp_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704:
+        if int(ops.lib().xpa_small_mlp_lds_floats(rows, *dims)) <= 40704:
             return True
         # the one-image form (128-wide layers): at most 32 rows per workgroup, which the kernel selects by the budget
-        return rows <= 32 and \
-            int(ops.lib().xpa_small_mlp_one_image_lds_floats(rows, l0.in_features, h0, h1, h2, k)) <= 40704
+        return rows <= 32 and int(ops.lib().xpa_small_mlp_one_image_lds_floats(rows, *dims)) <= 40704
 
     def _small_args(self, obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars=None):
         """K30's argument block for one minibatch and the tensor its loss scalars go to (scalars, default: the
         learner's shared one); allocates the split form's workspace on first use."""
-        fm, fused = self._fused_mlp(), self.fused_opt
-        (l0, code, slope), (l1, _, _), (la, _, _), (l2, _, _), (lc, _, _) = (fm.rep[0], fm.actor[0], fm.actor[1],
-                                                                             fm.critic[0], fm.critic[1])
+        fused = self.fused_opt
+        policy = self.small_policy_layers()
+        l0, l1, la, l2, lc = policy.layers
         if self._small_scalars is None:
             self._small_scalars = torch.zeros(8, dtype=torch.float32, device=obs_flat.device)
         g = self.optimizer.param_groups[0]
         b1, b2 = g["betas"]
         max_norm = float(self._max_norm) if self._use_clip else -1.0
-        a = _lib.XpaSmallMlpArgs()
-        a.batch, a.d_in, a.h0, a.h1, a.h2, a.k = (idx.shape[0], l0.in_features, l0.out_features, l1.out_features,
-                                                  l2.out_features, la.out_features)
-        a.act_code, a.algo, a.use_advnorm, a.n_sched = code, ops.ALGO[self.algo], int(bool(use_advnorm)), \
+        a = policy.fill(_lib.XpaSmallMlpArgs())
+        a.batch, a.algo, a.use_advnorm, a.n_sched = idx.shape[0], ops.ALGO[self.algo], int(bool(use_advnorm)), \
             fused.SCHED_WINDOW
-        a.slope, a.clip_range, a.vf_coef, a.ent_coef = slope, float(self.clip_range), float(self.vf_coef), \
-            float(self.ent_coef)
+        a.clip_range, a.vf_coef, a.ent_coef = float(self.clip_range), float(self.vf_coef), float(self.ent_coef)
         a.max_norm, a.beta1, a.beta2, a.eps = max_norm, float(b1), float(b2), float(g["eps"])
         a.obs, a.obs_ld, a.idx, a.n_rows = obs_flat.data_ptr(), obs_flat.stride(0), idx.data_ptr(), obs_flat.shape[0]
         a.actions, a.adv, a.ret = act.data_ptr(), adv.data_ptr(), ret.data_ptr()
         a.old_logp = old_logp.data_ptr() if old_logp is not None else None
-        a.W0, a.b0, a.W1, a.b1 = l0.weight.data_ptr(), l0.bias.data_ptr(), l1.weight.data_ptr(), l1.bias.data_ptr()
-        a.W2, a.b2, a.Wa, a.ba = l2.weight.data_ptr(), l2.bias.data_ptr(), la.weight.data_ptr(), la.bias.data_ptr()
-        a.Wc, a.bc = lc.weight.data_ptr(), lc.bias.data_ptr()
         a.gW0, a.gb0, a.gW1, a.gb1 = (l0.weight.grad.data_ptr(), l0.bias.grad.data_ptr(), l1.weight.grad.data_ptr(),
                                       l1.bias.grad.data_ptr())
         a.gW2, a.gb2, a.gWa, a.gba = (l2.weight.grad.data_ptr(), l2.bias.grad.data_ptr(), la.weight.grad.data_ptr(),
@@ -403,12 +393,7 @@ class _FusedPolicyGradient(Learner):
         """One K30 launch (capturable): reads lr / Adam step at the schedule cursor and advances it.  scalars: the
         8-float destination of the loss scalars (default: the learner's shared one)."""
         a, out = self._small_args(obs_flat, idx, act, adv, ret, old_logp, use_advnorm, scalars)
-        fm = self._fused_mlp()
-        if fm.logstd is None:
-            _lib.call(ops.lib().xpa_small_mlp_update, ctypes.byref(a), ops._stream(obs_flat.device))
-        else:   # Gaussian head: la is the mu layer, act [n_rows, A]
-            _lib.call(ops.lib().xpa_small_mlp_update_gauss, ctypes.byref(a), fm.logstd.data_ptr(),
-                      fm.logstd.grad.data_ptr(), ops._stream(obs_flat.device))
+        small_path.update(a, self._fused_mlp().logstd, obs_flat.device)
         return out
 
     def small_update(self, obs_flat, idx, act, adv, ret, old_logp=None, use_advnorm=True):

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .small_path import small_close, small_close_args, small_close_batch, small_eval  # noqa: F401 (theirs)
 
 ALGO = {"ppo": 0, "a2c": 1}
 DIST = {"gaussian": 0, "categorical": 1}
@@ -125,10 +126,10 @@ def _stream(device=None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def _req(t, name, dtype, shape=None, contiguous=True):
+def _req(t, name, dtype, shape=None, contiguous=True, cuda=True):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
-    if t.device.type != "cuda":
+    if cuda and t.device.type != "cuda":
         raise ValueError("%s must be on a ROCm device (got %s); xuanpolicy_amd has no CPU path" % (name, t.device))
     if t.dtype != dtype:
         raise TypeError("%s must be %s (got %s)" % (name, dtype, t.dtype))
@@ -1486,9 +1487,9 @@ def rollout_post(rew, term, trunc, v_boot, cursor, ret_mean, ret_var, ret_count,
               _stream(rew.device))
 
 
-def _n_slots(slot_t, N):
+def _n_slots(slot_t, N, cuda=True):
     """Deferred truncation slots per env of a slot_t buffer ([S N] or [S, N] int32, contiguous)."""
-    _req(slot_t, "slot_t", torch.int32)
+    _req(slot_t, "slot_t", torch.int32, cuda=cuda)
     if slot_t.numel() == 0 or slot_t.numel() % N:
         raise ValueError("slot_t must hold n_slots x n_envs entries")
     return slot_t.numel() // N
@@ -1504,56 +1505,6 @@ def bootstrap_fixup(values, slot_t, buf_term, buf_boot):
     _req(buf_boot, "buf_boot", torch.float32, (N, T))
     _lib.call(lib().xpa_rollout_bootstrap_fixup, N, T, _p(values), _p(slot_t), S, _p(buf_term), _p(buf_boot),
               _stream(values.device))
-
-
-def small_close_args(layers, act, rows, slot_t, rew, val, term, closed, boot, adv, ret, gamma, gae_lambda,
-                     use_gae=True, vboot_out=None):
-    """K33's argument block (XpaSmallCloseArgs) of one agent.  layers: the five Linear modules (representation, actor
-    hidden, actor out, critic hidden, critic out) of learner.small_policy_layers, act = (code, slope); rows
-    [(S + 1) N, d_in] the normalised deferred bootstrap rows (slot-major, then the last-step rows; row-strided allowed);
-    slot_t [S N]; rew / val / term / boot / adv / ret float32 [N, T], closed uint8 [N, T]; vboot_out (optional)
-    float32 [(S + 1) N].  The block holds the tensors' addresses and, as a Python object, references that keep them
-    alive (a byte copy of it does not)."""
-    l0, l1, la, l2, lc = layers
-    N, T = rew.shape
-    S = _n_slots(slot_t, N)
-    D = l0.in_features
-    for name, t in (("rew", rew), ("val", val), ("term", term), ("boot", boot), ("adv", adv), ("ret", ret)):
-        _req(t, name, torch.float32, (N, T))
-    _req(closed, "closed", torch.uint8, (N, T))
-    _req(rows, "rows", torch.float32, contiguous=False)
-    ld = _row_stride(rows, "rows", D)
-    if rows.shape[0] != (S + 1) * N:
-        raise ValueError("rows must hold (n_slots + 1) x n_envs rows")
-    if vboot_out is not None:
-        _req(vboot_out, "vboot_out", torch.float32, ((S + 1) * N,))
-    a = _lib.XpaSmallCloseArgs()
-    a.n_envs, a.horizon, a.d_in, a.h0, a.h1, a.h2, a.k = N, T, D, l0.out_features, l1.out_features, l2.out_features, \
-        la.out_features
-    a.act_code, a.n_slots, a.use_gae = int(act[0]), S, int(bool(use_gae))
-    a.slope, a.gamma, a.gae_lambda = float(act[1]), float(gamma), float(gae_lambda)
-    for name, lin in (("0", l0), ("1", l1), ("2", l2), ("a", la), ("c", lc)):
-        _req(lin.weight, "W" + name, torch.float32)
-        _req(lin.bias, "b" + name, torch.float32)
-        setattr(a, "W" + name, _p(lin.weight))
-        setattr(a, "b" + name, _p(lin.bias))
-    a.rows, a.ld_rows, a.slot_t = _p(rows), ld, _p(slot_t)
-    a.rew, a.val, a.term, a.closed = _p(rew), _p(val), _p(term), _p(closed)
-    a.boot, a.adv, a.ret, a.vboot_out = _p(boot), _p(adv), _p(ret), _p(vboot_out)
-    a._keep = (layers, rows, slot_t, rew, val, term, closed, boot, adv, ret, vboot_out)
-    return a
-
-
-def small_close(block, device):
-    """K33 (xpa_small_close): one agent's closing — the deferred bootstraps' critic with K32's arithmetic, the
-    fixup's writes and the advantage scan — in one launch.  block: small_close_args'."""
-    _lib.call(lib().xpa_small_close, ctypes.byref(block), _stream(device))
-
-
-def small_close_batch(n_agents, host_blocks, dev_blocks, device):
-    """K33 for a population (xpa_small_close_batch): host_blocks a ctypes array of XpaSmallCloseArgs, dev_blocks its
-    copy in device memory (a uint8 tensor)."""
-    _lib.call(lib().xpa_small_close_batch, n_agents, ctypes.addressof(host_blocks), _p(dev_blocks), _stream(device))
 
 
 def dqn_td_loss(evalQ, targetQ, act, rew, term, gamma, dQ=None, td_abs=None, scalars=None, err=None):
@@ -1662,20 +1613,3 @@ def eval_post(log, capacity, snap_dim, term, trunc, ep_last_score, ep_last_len, 
         _req(count, "obs_count", torch.float64, (1,))
     _lib.call(lib().xpa_eval_post, _p(log), int(capacity), int(snap_dim), N, _p(term), _p(trunc), _p(ep_last_score),
               _p(ep_last_len), int(bool(atari_lifeloss)), _p(cursor), _p(mean), _p(var), _p(count), _stream(log.device))
-
-
-def small_eval(entry, args, log, capacity, snap_dim, scratch, logstd=None, act_clip=1.0):
-    """K32E (xpa_small_eval_<env>): up to args.steps evaluation steps in one launch, the finished
-    episodes into the log.  args: an XpaSmallRolloutArgs whose seed / cursor are the evaluation's; scratch f32
-    [3 * n_envs]."""
-    _eval_log_dims(log, capacity, snap_dim)
-    _req(scratch, "scratch", torch.float32, (3 * int(args.n_envs),))
-    s = _stream(log.device)
-    if entry in ("xpa_small_eval_cartpole", "xpa_small_eval_acrobot", "xpa_small_eval_mountaincar"):
-        _lib.call(getattr(lib(), entry), ctypes.byref(args), _p(log), int(capacity), int(snap_dim), _p(scratch), s)
-    elif entry == "xpa_small_eval_pendulum":
-        _req(logstd, "logstd", torch.float32, (1,))
-        _lib.call(lib().xpa_small_eval_pendulum, ctypes.byref(args), _p(logstd), float(act_clip), _p(log),
-                  int(capacity), int(snap_dim), _p(scratch), s)
-    else:
-        raise _lib.XpaError("no one-launch evaluation entry point named %r" % (entry,))

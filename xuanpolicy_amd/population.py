@@ -13,12 +13,8 @@ style of rollout_plan.plan_rollout; there is no sequential fallback: an ineligib
 import ctypes
 from typing import NamedTuple
 
-from .rollout_plan import _K32, K32_DRIVERS
+from .rollout_plan import K32_DRIVERS, SMALL_BY_ENTRY
 
-# xpa_small_rollout_batch's env codes (include/xuanpolicy_amd.h: XPA_ENV_*), by the single-agent entry point
-_ENV_CODE = {"xpa_small_rollout_cartpole": "XPA_ENV_CARTPOLE", "xpa_small_rollout_pendulum": "XPA_ENV_PENDULUM",
-             "xpa_small_rollout_acrobot": "XPA_ENV_ACROBOT", "xpa_small_rollout_mountaincar": "XPA_ENV_MOUNTAINCAR"}
-assert set(_ENV_CODE) == {entry for entry, _, _ in _K32.values()}
 MAX_AGENTS = 65535   # the y extent of a launch grid (the update's agent dimension); not a function of the CU count
 
 
@@ -66,7 +62,7 @@ def plan_population(facts):
         if f.world != 1:
             raise ValueError("member %d: world size %d (a population trains in one process: world must be 1)"
                              % (i, f.world))
-        if f.driver not in K32_DRIVERS or f.entry not in _ENV_CODE:
+        if f.driver not in K32_DRIVERS or f.entry not in SMALL_BY_ENTRY:
             raise ValueError("member %d: rollout driver %r is not the one-launch small path %s"
                              % (i, f.driver, "/".join(K32_DRIVERS)))
         if f.feed != "small":
@@ -90,8 +86,8 @@ def plan_population(facts):
             if ptr in seen and seen[ptr] != i:
                 raise ValueError("members %d and %d share a tensor (data pointer 0x%x)" % (seen[ptr], i, ptr))
             seen[ptr] = i
-    return PopulationPlan(len(facts), f0.entry, _ENV_CODE[f0.entry], f0.entry == "xpa_small_rollout_pendulum", f0.chunk,
-                          f0.gae == "K33")
+    row = SMALL_BY_ENTRY[f0.entry]
+    return PopulationPlan(len(facts), f0.entry, row.code, row.gaussian, f0.chunk, f0.gae == "K33")
 
 
 def _block_array(struct, blocks):
@@ -121,41 +117,28 @@ class _DeviceBlocks:
 
 
 def update_blocks(learners, rows, idxs, scalars, cache):
-    """xpa_small_mlp_update_batch's arguments for one minibatch of every learner: (host blocks, device blocks, host
-    heads, device heads).  rows[p] = (obs_flat, act, adv, ret, old_logp, use_advnorm) and idxs[p] (int64 row indices)
-    are learner p's, scalars[p] the 8 floats its loss scalars go to; each block is the learner's own
-    (learner._small_args), cache a _DeviceBlocks."""
+    """xpa_small_mlp_update_batch's arguments for one minibatch of every learner: (blocks, heads), each a (host array,
+    device copy) pair, heads None for Categorical heads.  rows[p] = (obs_flat, act, adv, ret, old_logp, use_advnorm) and
+    idxs[p] (int64 row indices) are learner p's, scalars[p] the 8 floats its loss scalars go to; each block is the
+    learner's own (learner._small_args), cache a _DeviceBlocks."""
     from . import _lib
     blocks, heads = [], []
     for p, L in enumerate(learners):
         obs_flat, act, adv, ret, old_logp, use_advnorm = rows[p]
-        blk, _ = L._small_args(obs_flat, idxs[p], act, adv, ret, old_logp, use_advnorm, scalars=scalars[p])
-        blocks.append(blk)
+        blocks.append(L._small_args(obs_flat, idxs[p], act, adv, ret, old_logp, use_advnorm, scalars=scalars[p])[0])
         logstd = L._fused_mlp().logstd
         if logstd is not None:
-            h = _lib.XpaSmallMlpGauss()
-            h.logstd, h.g_logstd = logstd.data_ptr(), logstd.grad.data_ptr()
-            heads.append(h)
+            heads.append(_lib.XpaSmallMlpGauss(logstd.data_ptr(), logstd.grad.data_ptr()))
     if heads and len(heads) != len(blocks):
         raise ValueError("Categorical and Gaussian heads in one batch update")
-    host, dev = cache.get(_block_array(_lib.XpaSmallMlpArgs, blocks))
-    hh = hd = None
-    if heads:
-        hh, hd = cache.get(_block_array(_lib.XpaSmallMlpGauss, heads))
-    return host, dev, hh, hd
-
-
-def launch_update(slot, n_agents, device):
-    """One minibatch update of every agent in one launch (xpa_small_mlp_update_batch; capturable)."""
-    from . import _lib, ops
-    host, dev, hh, hd = slot
-    _lib.call(ops.lib().xpa_small_mlp_update_batch, n_agents, ctypes.addressof(host), dev.data_ptr(),
-              None if hh is None else ctypes.addressof(hh), None if hd is None else hd.data_ptr(), ops._stream(device))
+    return (cache.get(_block_array(_lib.XpaSmallMlpArgs, blocks)),
+            cache.get(_block_array(_lib.XpaSmallMlpGauss, heads)) if heads else None)
 
 
 def small_update_batch(learners, rows, idxs, scalars, cache=None):
     """learner.small_update (one eager K30 update and the host bookkeeping of the step) for every learner, the device
     part as one batch launch.  Arguments as update_blocks'; returns scalars."""
+    from . import small_path
     device = scalars.device
     for L in learners:
         if not L.fused_opt.sched_enabled:
@@ -164,7 +147,7 @@ def small_update_batch(learners, rows, idxs, scalars, cache=None):
     for L in learners:
         L.fused_opt.ensure_window(L.scheduler)
         L.iterations += 1
-    launch_update(slot, len(learners), device)
+    small_path.update_batch(len(learners), *slot, device)
     for L in learners:
         L._host_steps(1)
     return scalars
@@ -202,14 +185,10 @@ class Population:
     @staticmethod
     def _facts(a):
         plan, L, env, mem = a.plan(), a.learner, a.envs, a.memory
-        layers = L.small_policy_layers()
+        policy = L.small_policy_layers()
         k32 = plan.driver in K32_DRIVERS
-        dims = act = None
+        dims, act = (policy.dims, (int(policy.code), float(policy.slope))) if policy else (None, None)
         tensors = ()
-        if layers is not None:
-            (l0, l1, la, l2, _), code, slope, _ = layers
-            dims = (l0.in_features, l0.out_features, l1.out_features, l2.out_features, la.out_features)
-            act = (int(code), float(slope))
         if k32 and plan.feed == "small":
             fused = L.fused_opt
             ts = [fused.fs.param, fused.fs.flat, fused.exp_avg, fused.exp_avg_sq, mem.observations, mem.actions,
@@ -245,32 +224,21 @@ class Population:
 
     # ---- the batch launches ---------------------------------------------------------------------------------------
     def _rollout_launch(self, plan, steps):
-        """`steps` env steps of every member in one launch (xpa_small_rollout_batch)."""
-        from . import _lib, ops
-        blocks = []
+        """`steps` env steps of every member in one launch (xpa_small_rollout_batch) over the members' own blocks."""
+        from . import _lib, small_path
         for a in self.agents:
             a._k32.steps = int(steps)
-            blocks.append(a._k32)
-        host, dev = self._blocks.get(_block_array(_lib.XpaSmallRolloutArgs, blocks))
-        hh = hd = None
-        if plan.gaussian:
-            heads = []
-            for a in self.agents:
-                h = _lib.XpaSmallRolloutHead()
-                h.logstd, h.act_clip = ops._p(a._k32_logstd), a._act_clip()
-                heads.append(h)
-            hh, hd = self._blocks.get(_block_array(_lib.XpaSmallRolloutHead, heads))
-        lib = ops.lib()
-        _lib.call(lib.xpa_small_rollout_batch, _lib.ENV_CODES[plan.env], len(blocks), ctypes.addressof(host),
-                  dev.data_ptr(), None if hh is None else ctypes.addressof(hh), None if hd is None else hd.data_ptr(),
-                  ops._stream(self.device))
+        blocks = self._blocks.get(_block_array(_lib.XpaSmallRolloutArgs, [a._k32 for a in self.agents]))
+        heads = plan.gaussian and self._blocks.get(_block_array(_lib.XpaSmallRolloutHead,
+                                                                [a._k32_head for a in self.agents]))
+        small_path.rollout_batch(plan.env, len(self.agents), blocks, heads, self.device)
 
     def _close_launch(self):
         """Every member's closing (agent._close_rollout's "K33" form) in one launch (xpa_small_close_batch) over the
         members' own blocks, then the host state each member's own launch leaves."""
-        from . import _lib, ops
+        from . import _lib, small_path
         host, dev = self._blocks.get(_block_array(_lib.XpaSmallCloseArgs, [a._small_close_block() for a in self.agents]))
-        ops.small_close_batch(len(self.agents), host, dev, self.device)
+        small_path.small_close_batch(len(self.agents), host, dev, self.device)
         for a in self.agents:
             a._closed_small()
 
@@ -305,9 +273,6 @@ class Population:
         return [update_blocks(learners, rows, [perm[p, s:s + B] for p in range(len(learners))], scalars[:, j],
                               self._blocks) for j, s in enumerate(starts)], scalars
 
-    def _update_launch(self, slot):
-        launch_update(slot, len(self.agents), self.device)
-
     def _epoch_key(self, rows, NT, B):
         """What an epoch's launches (and their captured graph) bake in besides the permutation buffer: every member's
         learners.small_epoch key.  Formed once per update phase: nothing of it can change between two epochs."""
@@ -321,7 +286,7 @@ class Population:
         """One epoch of minibatch updates for every member: learners.small_epoch's legs over the batch launches —
         eager the first time a layout is seen, then captured once as one linear graph and replayed.  Returns the
         [P, slots, 8] loss scalars of the epoch's updates."""
-        from . import graphs
+        from . import graphs, small_path
         learners = [a.learner for a in self.agents]
         n_slots = -(-NT // B)
         key = (perm.data_ptr(),) + key
@@ -339,7 +304,7 @@ class Population:
                 for L in learners:
                     L.fused_opt.ensure_window(L.scheduler)
                     L.iterations += 1
-                self._update_launch(slot)
+                small_path.update_batch(len(learners), *slot, self.device)
                 for L in learners:
                     L._host_steps(1)
             if graphed:
@@ -352,7 +317,8 @@ class Population:
             if self._graph_pool is None:
                 self._graph_pool = torch.cuda.graph_pool_handle()
             try:
-                ent[0], _ = graphs.capture(lambda: [self._update_launch(s) for s in ent[1]], self._graph_pool)
+                ent[0], _ = graphs.capture(
+                    lambda: [small_path.update_batch(len(learners), *s, self.device) for s in ent[1]], self._graph_pool)
             except Exception:
                 torch.cuda.synchronize()   # nothing of an aborted capture ran: stay eager from here on
                 self._graph_failed = True

@@ -78,11 +78,30 @@ _ENV = {"in-head": (), "synthbox": ("xpa_synthbox_step",), "synthatari": ("xpa_s
 # device envs added since
 _ENV_STEP = dict(_ENV, pendulum=("xpa_pendulum_step",), acrobot=("xpa_acrobot_step",),
                  mountaincar=("xpa_mountaincar_step",))
-# K32's instantiations: (env, the head's distribution) -> (entry point, d_in, head width)
-_K32 = {("cartpole", "categorical"): ("xpa_small_rollout_cartpole", 4, 2),
-        ("pendulum", "gaussian"): ("xpa_small_rollout_pendulum", 3, 1),
-        ("acrobot", "categorical"): ("xpa_small_rollout_acrobot", 6, 3),
-        ("mountaincar", "categorical"): ("xpa_small_rollout_mountaincar", 8, 3)}
+
+
+class SmallEnv(NamedTuple):
+    """One env / head pair of the one-launch small path (K32, K32W, K32E, the population's batch launch): a row of
+    SMALL_ENVS, the only statement of them on the host."""
+    d_in: int        # the env's observation width
+    k: int           # the head's width
+    rollout: str     # K32's single-agent entry point
+    eval: str        # K32E's entry point
+    code: str        # xpa_small_rollout_batch's env code: the XPA_ENV_* constant's name
+    gaussian: bool   # the entry points take (logstd, act_clip) after the block, the batch launch its head arrays
+
+
+SMALL_ENVS = {   # by (env kind, the head's distribution)
+    ("cartpole", "categorical"): SmallEnv(4, 2, "xpa_small_rollout_cartpole", "xpa_small_eval_cartpole",
+                                          "XPA_ENV_CARTPOLE", False),
+    ("pendulum", "gaussian"): SmallEnv(3, 1, "xpa_small_rollout_pendulum", "xpa_small_eval_pendulum",
+                                       "XPA_ENV_PENDULUM", True),
+    ("acrobot", "categorical"): SmallEnv(6, 3, "xpa_small_rollout_acrobot", "xpa_small_eval_acrobot",
+                                         "XPA_ENV_ACROBOT", False),
+    ("mountaincar", "categorical"): SmallEnv(8, 3, "xpa_small_rollout_mountaincar", "xpa_small_eval_mountaincar",
+                                             "XPA_ENV_MOUNTAINCAR", False)}
+SMALL_BY_ENTRY = {e: row for row in SMALL_ENVS.values() for e in (row.rollout, row.eval)}   # the row of an entry point
+_K32 = {key: (row.rollout, row.d_in, row.k) for key, row in SMALL_ENVS.items()}   # a view of the table tests read
 K32_DRIVERS = ("K32", "K32W")   # the one-launch rollout's drivers: the same entry points, run the same way
 _VALUE_HEAD = {"K13": ("xpa_value_head",), "chain": ("xpa_value_head",), "cnn": (), "policy": ()}
 _POST = {"K14F": (), "K8-deferred": ("xpa_rollout_post_deferred_norm",), "K8": ("xpa_rollout_post",)}
@@ -129,7 +148,7 @@ class RolloutPlan(NamedTuple):
         """The library entry points of one steady device env step, in order (hipBLASLt / torch launches are not
         counted).  pending: the step after a reset, which runs the standalone obs_rms update whatever the form."""
         if self.driver in K32_DRIVERS:
-            return [entry for (env, _), (entry, _, _) in _K32.items() if env == self.env]
+            return [row.rollout for (env, _), row in SMALL_ENVS.items() if env == self.env]
         out = list(_RMS["standalone"] if pending and self.rms in ("fold-K8", "fold-K14F") else _RMS[self.rms])
         out += _OBS[self.obs] + _TRUNK[self.trunk]
         if self.trunk != "K40T":
@@ -163,14 +182,14 @@ def plan_rollout(f):
     collective = f.sync_obs_rms is True and f.world > 1 and f.use_obsnorm
     # K32: a CartPole (Categorical, 2 actions), Pendulum (Gaussian, 1 torque), Acrobot or MountainCar (Categorical, 3
     # actions) device env with deferred bootstraps, no per-step collective, the small_policy_layers shape
-    k32 = (f.fused_rollout and f.cuda and (f.env, f.dist) in _K32 and f.defer_boot and not f.raw_obs and not collective
+    k32 = (f.fused_rollout and f.cuda and (f.env, f.dist) in SMALL_ENVS and f.defer_boot and not f.raw_obs and not collective
            and f.algo in ("ppo", "a2c") and f.small is not None and f.small_bufs)
     wide = False
     if k32:
         d_in, h0, h1, h2, k, lds = f.small
         wide = (h0, h1, h2) == (128, 128, 128)   # K32W: the forward's own layout, everything else K32's
         k32 = ((wide or (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64)))
-               and (d_in, k) == _K32[f.env, f.dist][1:] and d_in == f.obs_dim and 0 < lds <= 16384)
+               and (d_in, k) == SMALL_ENVS[f.env, f.dist][:2] and d_in == f.obs_dim and 0 < lds <= 16384)
     chunk = max(1, f.graph_chunk) if f.use_graph and device and not collective else 1
     driver = ("host" if not device else ("K32W" if wide else "K32") if k32
               else "eager" if not (f.use_graph and not collective) else "graph-chunk" if chunk > 1 else "graph-step")
@@ -221,12 +240,6 @@ def plan_rollout(f):
 
 
 # ---- evaluation (agent.test) ------------------------------------------------------------------------------------------
-# K32's evaluation form (K32E): the entry point of each of K32's instantiations
-_K32E = {("cartpole", "categorical"): "xpa_small_eval_cartpole", ("pendulum", "gaussian"): "xpa_small_eval_pendulum",
-         ("acrobot", "categorical"): "xpa_small_eval_acrobot",
-         ("mountaincar", "categorical"): "xpa_small_eval_mountaincar"}
-
-
 class EvalFacts(NamedTuple):
     """What plan_test decides from.  _OnPolicyAgent._eval_facts gathers it for one set of test envs."""
     cuda: bool
@@ -245,9 +258,9 @@ def plan_test(f):
     multi-kernel step, eager, + xpa_eval_post) or "host" (the reference's Python loop).  The only place it is decided."""
     if not f.cuda or f.env == "host" or (f.sync_obs_rms is True and f.world > 1):   # the per-step collective
         return "host"
-    if (f.env, f.dist) in _K32E and not f.raw_obs and 0 < f.n_envs <= 256 and f.small is not None:
+    if (f.env, f.dist) in SMALL_ENVS and not f.raw_obs and 0 < f.n_envs <= 256 and f.small is not None:
         d_in, h0, h1, h2, k, lds = f.small
-        if (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and (d_in, k) == _K32[f.env, f.dist][1:]
+        if (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and (d_in, k) == SMALL_ENVS[f.env, f.dist][:2]
                 and d_in == f.obs_dim and 0 < lds <= 16384):
             return "K32E"
     return "steps"
@@ -255,4 +268,4 @@ def plan_test(f):
 
 def eval_entry(f):
     """K32E's entry point for facts that plan "K32E"."""
-    return _K32E[f.env, f.dist]
+    return SMALL_ENVS[f.env, f.dist].eval
