@@ -74,15 +74,20 @@ WIDTHS = {"cartpole-64": ("cartpole", dict(hidden=64)), "pendulum-32": ("pendulu
           "acrobot-32-64-32": ("acrobot", dict(hidden=32, actor_hidden_size=[64]))}
 
 
-def _one_k32_step(case, N):
+def _one_k32_step(case, N, randomise_biases=False):
     """An agent after ONE K32 / K32W step through its own single-step launch: agent.obs_norm holds the rows the launch
     forwarded, column 0 of memory.values what it wrote for them.  Returns (agent, vboot_out of a K33 launch whose every
-    row group is obs_norm, S)."""
+    row group is obs_norm, S).  case: a key of WIDTHS, or its own (env kind, builder keywords).  randomise_biases:
+    every policy bias (and a Gaussian head's logstd) is overwritten in place before the rollout begins (a fresh
+    policy's biases are all 0)."""
     from xuanpolicy_amd import ops
-    kind, kw = WIDTHS[case]
+    kind, kw = WIDTHS[case] if isinstance(case, str) else case
     agent = _build(kind, n_envs=N, n_steps=8, seed=11, max_episode_steps=3, n_minibatch=1, **kw)   # 3 slots per env
     S = agent.n_slots
     assert S == 3 and agent.plan().driver == ("K32W" if kw["hidden"] == 128 else "K32")
+    if randomise_biases:
+        from tests._small_ref import randomise_biases as overwrite
+        assert len(overwrite(agent.policy)) == (6 if kind == "pendulum" else 5)
     agent._begin_rollout()
     agent._small_rollout_launch(1)
     mem, T = agent.memory, agent.n_steps
