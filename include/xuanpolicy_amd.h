@@ -40,7 +40,7 @@ typedef struct ihipStream_t *xpa_stream_t; /* == hipStream_t */
  * ~300 blocks counting on one int serialised their atomics).
  * Added since without a version change (new entry points only, no existing signature or struct touched): the
  * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch; K33's xpa_small_close and
- * xpa_small_close_batch (XpaSmallCloseArgs). */
+ * xpa_small_close_batch (XpaSmallCloseArgs); the population evaluation xpa_small_eval_batch (XpaSmallEval). */
 #define XPA_ABI_VERSION 4
 #define XPA_COLSUM_TICKET_INTS 4096
 
@@ -429,7 +429,8 @@ int64_t xpa_eval_log_ints(int64_t capacity, int64_t snap_dim);
  * are appended to the log in env order, and the launch ends after the first step with count >= target; then it writes
  * the env state, count, steps_run, done and the cursor (ptr 0, step advanced by the steps run).  A launch that finds
  * done set returns at once, so several may be queued before the host looks.  Only what this form reads is required of
- * args (weights, obs statistics, act_in, the env's tensors, cursor); the buffer / return / slot pointers may be NULL. */
+ * args (weights, obs statistics, act_in, the env's tensors, cursor); the buffer / return / slot pointers may be NULL.
+ * One workgroup per launch; a population's members are evaluated side by side by xpa_small_eval_batch below. */
 int xpa_small_eval_cartpole(const XpaSmallRolloutArgs *args, int32_t *log, int64_t capacity, int64_t snap_dim,
                             float *scratch, xpa_stream_t stream);
 int xpa_small_eval_pendulum(const XpaSmallRolloutArgs *args, const float *logstd, float act_clip, int32_t *log,
@@ -438,6 +439,29 @@ int xpa_small_eval_acrobot(const XpaSmallRolloutArgs *args, int32_t *log, int64_
                            float *scratch, xpa_stream_t stream);
 int xpa_small_eval_mountaincar(const XpaSmallRolloutArgs *args, int32_t *log, int64_t capacity, int64_t snap_dim,
                                float *scratch, xpa_stream_t stream);
+/* K32EB — K32E for a population: P agents' evaluation launches in ONE, workgroup p = agent p (env: XPA_ENV_*).  Each
+ * workgroup loads its XpaSmallRolloutArgs from dev_blocks[p], for a Gaussian head its XpaSmallRolloutHead from
+ * dev_heads[p], and its XpaSmallEval from dev_evals[p] (device memory; the addresses are wave-uniform), applies the
+ * single-agent entry point's overrides to its copy of the block (horizon 1, the sampler's stores into scratch, no
+ * stamps) and runs K32E's body: agent p's log, scratch, env tensors, obs statistics and cursor end bit for bit as
+ * xpa_small_eval_<env>(&host_blocks[p], ...) leaves them.  The stop rule is per log: a workgroup whose log has done
+ * set returns at once while its neighbours run on, and no workgroup reads or waits on what another writes, so several
+ * launches may be queued before the host looks at the P headers.  The targets live in the logs and may differ.
+ * Every check runs on the host copies before any HIP call: 1 <= n_agents <= 0x7fffffff; all six arrays present, the
+ * two head arrays NULL exactly for the Categorical envs; each block passes the single-agent evaluation checks (K32's
+ * widths 32 / 64 only) and equals block 0 in n_envs, steps, d_in, h0, h1, h2, k, act_code, use_obsnorm,
+ * max_episode_steps, slope, obs_clip, ld_obs, ld_act (seed may differ); capacity in (0, 2^31) and snap_dim >= 0, both
+ * equal across members; every log non-NULL and 16-B aligned, every scratch non-NULL, no two members sharing either;
+ * each head with a logstd and act_clip > 0.  Else an error is returned and nothing is launched. */
+typedef struct XpaSmallEval {
+    int32_t *log;      /* int32 [xpa_eval_log_ints(capacity, snap_dim)], 16-B aligned; target in word 1 */
+    float *scratch;    /* float [3 * n_envs] */
+    int64_t capacity, snap_dim;
+} XpaSmallEval;
+int xpa_small_eval_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                         const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
+                         const XpaSmallRolloutHead *dev_heads, const XpaSmallEval *host_evals,
+                         const XpaSmallEval *dev_evals, xpa_stream_t stream);
 /* The generic tier's log writer, one launch per env step after the env's step kernel (one workgroup over all envs, so
  * a step's entries land in env order): appends the envs with term || trunc (atari_lifeloss = 1: not those that did
  * not truncate), steps_run += 1, cursor->step += 1 (ptr stays 0).  At the step where count first reaches target it

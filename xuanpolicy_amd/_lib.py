@@ -79,7 +79,7 @@ with open(HEADER) as _f:
     SIGNATURES, _structs, _constants = parse_header(_f.read())
 XpaSmallMlpArgs, XpaSmallRolloutArgs = _structs["XpaSmallMlpArgs"], _structs["XpaSmallRolloutArgs"]
 XpaSmallRolloutHead, XpaSmallMlpGauss = _structs["XpaSmallRolloutHead"], _structs["XpaSmallMlpGauss"]
-XpaSmallCloseArgs = _structs["XpaSmallCloseArgs"]
+XpaSmallCloseArgs, XpaSmallEval = _structs["XpaSmallCloseArgs"], _structs["XpaSmallEval"]
 ABI_VERSION, COLSUM_TICKET_INTS = _constants["XPA_ABI_VERSION"], _constants["XPA_COLSUM_TICKET_INTS"]
 ENV_CODES = {n: v for n, v in _constants.items() if n.startswith("XPA_ENV_")}   # xpa_small_rollout_batch's `env`
 

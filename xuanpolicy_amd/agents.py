@@ -987,6 +987,11 @@ class _OnPolicyAgent:
             self._eval_cursor = ops.new_cursor(self.device)
         return (int(self.seed) ^ EVAL_SALT) & 0xFFFFFFFF, self._eval_cursor
 
+    def _eval_scalars(self, env):
+        """(snap_dim, act_clip) of an evaluation on env: the log's snapshot width and the sampler's action clip."""
+        return (0 if self.raw_obs or not self.use_obsnorm else self.obs_dim,
+                1.0 if self.discrete else _space_clip(env.action_space))
+
     def _build_small_eval(self, env, seed, cursor):
         """K32E's argument block over the test envs (small_path.env_block) and the Gaussian head's logstd (or None)."""
         policy = self.learner.small_policy_layers()
@@ -1039,11 +1044,10 @@ class _OnPolicyAgent:
             raise ValueError("test_device: test_episode >= 1 and time-limited test envs (max_episode_steps)")
         env.reset()
         seed, cursor = self._eval_stream(rng)
-        snap_dim = 0 if self.raw_obs or not self.use_obsnorm else self.obs_dim
+        snap_dim, act_clip = self._eval_scalars(env)
         capacity = target + N
         log = ops.eval_log_new(target, N, snap_dim, dev)
         bound = (target // N + 2) * max_ep
-        act_clip = 1.0 if self.discrete else _space_clip(env.action_space)
         if tier == "K32E":
             chunk = 128 if chunk is None else int(chunk)
             args, logstd = self._build_small_eval(env, seed, cursor)
@@ -1095,17 +1099,9 @@ class _OnPolicyAgent:
         where plan_test allows it."""
         test_envs = env_fn()
         if bool(_cfg(self.config, "device_test", False)) and self.plan_test(test_envs) != "host":
-            scores = self.test_device(test_envs, test_episode)
-            if bool(_cfg(self.config, "test_mode", False)):
-                for i, s in enumerate(scores):
-                    print("Episode: %d, Score: %.2f" % (i + 1, s))
-                print("Best Score: %.2f" % max(scores))
-            self.log_infos({"Test-Episode-Rewards/Mean-Score": float(np.mean(scores)),
-                            "Test-Episode-Rewards/Std-Score": float(np.std(scores))}, self.current_step)
-            test_envs.close()
-            return scores
+            return self._finish_test(test_envs, self.test_device(test_envs, test_episode))
         num_envs = test_envs.num_envs
-        current_episode, scores, best_score = 0, [], -np.inf
+        current_episode, scores = 0, []
         obs, _ = test_envs.reset()
         obs = obs.cpu().numpy() if isinstance(obs, torch.Tensor) else np.asarray(obs)
         verbose = bool(_cfg(self.config, "test_mode", False))
@@ -1122,11 +1118,18 @@ class _OnPolicyAgent:
                     obs[i] = infos[i]["reset_obs"]
                     scores.append(infos[i]["episode_score"])
                     current_episode += 1
-                    best_score = max(best_score, infos[i]["episode_score"])
                     if verbose:
                         print("Episode: %d, Score: %.2f" % (current_episode, infos[i]["episode_score"]))
-        if verbose:
-            print("Best Score: %.2f" % best_score)
+        return self._finish_test(test_envs, scores, listed=True)
+
+    def _finish_test(self, test_envs, scores, listed=False):
+        """test()'s tail, shared by the host loop, the device path and Population.test: the scores printed under
+        config.test_mode (listed: the host loop printed each episode as it ended), the two test infos logged at
+        current_step, the test envs closed; returns scores."""
+        if bool(_cfg(self.config, "test_mode", False)):
+            for i, s in enumerate(() if listed else scores):
+                print("Episode: %d, Score: %.2f" % (i + 1, s))
+            print("Best Score: %.2f" % max(scores, default=-np.inf))
         self.log_infos({"Test-Episode-Rewards/Mean-Score": float(np.mean(scores)),
                         "Test-Episode-Rewards/Std-Score": float(np.std(scores))}, self.current_step)
         test_envs.close()

@@ -11,6 +11,9 @@
 #include "mountaincar_body.h"
 #include "pendulum_body.h"
 
+#include <algorithm>
+#include <vector>
+
 namespace {
 
 constexpr int kGatherRows = 64;  // rows per gather block == rows per adv partial (1024 blocks at B = 65 536)
@@ -1652,6 +1655,31 @@ __global__ __launch_bounds__(kRoThreads) void small_rollout_batch_kernel(
     small_rollout_body<E, ACT, H0, false>(a, hd, RoNoEval{});
 }
 
+// K32EB — the population form of the evaluation (xpa_small_eval_batch): workgroup p is agent p.  Its block, its head
+// and its XpaSmallEval record (log, scratch, capacity, snap_dim) are plain loads at wave-uniform addresses; the local
+// copy of the block takes the overrides small_eval_launch makes on the host (horizon 1, the sampler's three stores
+// into scratch, no stamps), and from there on it is K32E's body.  The stop rule is block-uniform and per log, so
+// members finish at different steps without coordination: a workgroup whose log has done set returns at once while
+// its neighbours run on, and no workgroup reads or waits on anything another one writes.
+template <class E, int ACT, int H0>
+__global__ __launch_bounds__(kRoThreads) void small_eval_batch_kernel(
+    const XpaSmallRolloutArgs *__restrict__ blocks, const XpaSmallRolloutHead *__restrict__ heads,
+    const XpaSmallEval *__restrict__ evals) {
+    XpaSmallRolloutArgs a = blocks[blockIdx.x];
+    const XpaSmallEval e = evals[blockIdx.x];
+    typename E::Head hd{};
+    if constexpr (!std::is_empty_v<typename E::Head>) {
+        const XpaSmallRolloutHead h = heads[blockIdx.x];
+        hd = typename E::Head{h.logstd, h.act_clip};
+    }
+    a.horizon = 1;
+    a.buf_act = e.scratch;
+    a.buf_logp = e.scratch + a.n_envs;
+    a.buf_val = e.scratch + 2 * a.n_envs;
+    a.stamps = nullptr;
+    small_rollout_body<E, ACT, H0, true>(a, hd, RoEval{e.log, e.capacity, eval_log_entries(e.snap_dim)});
+}
+
 // ---------------------------------------------------------------------------------------------
 // K33 — the closing of a K32 / K32W rollout in one launch (one workgroup per agent): the critic over the deferred
 // bootstrap rows, bootstrap_fixup_kernel's writes and the advantage scan (xpa_gae_scan's recurrence on the dense
@@ -2658,23 +2686,32 @@ void ro_dispatch(int64_t h0, int act_code, F launch) {
 // The checks and the launch shared by K32's entry points; E: the instantiation's env / head pair, k its head width.
 // K32E's checks and launch: only what the evaluation form dereferences is required (the training-only pointers of
 // XpaSmallRolloutArgs may be null); horizon 1 and the sampler's three stores into scratch [3 * n_envs]
+// The predicate is shared by the single-agent launch and the population's (one agent's block and its log / scratch).
 template <class E>
-int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd, int32_t *log, int64_t capacity,
-                      int64_t snap_dim, float *scratch, xpa_stream_t stream) {
+bool ro_eval_args_ok(const XpaSmallRolloutArgs *a0, int k, const int32_t *log, int64_t capacity, int64_t snap_dim,
+                     const float *scratch) {
     if (!a0 || !log || capacity <= 0 || capacity > 0x7fffffff || snap_dim < 0 || !scratch || ((uintptr_t)log % 16))
-        return (int)hipErrorInvalidValue;
-    XpaSmallRolloutArgs a = *a0;
+        return false;
+    const XpaSmallRolloutArgs &a = *a0;
     if (a.n_envs <= 0 || a.n_envs > 256 || a.steps <= 0 || a.d_in != E::D || (a.h0 != 32 && a.h0 != 64) ||
         (a.h1 != 32 && a.h1 != 64) || (a.h2 != 32 && a.h2 != 64) || a.k != k || a.act_code < 0 || a.act_code > 2 ||
         a.max_episode_steps <= 0 || a.ld_obs < E::D || a.ld_act < k)
-        return (int)hipErrorInvalidValue;
+        return false;
     if (!a.W0 || !a.b0 || !a.W1 || !a.b1 || !a.W2 || !a.b2 || !a.Wa || !a.ba || !a.Wc || !a.bc || !a.obs_mean ||
         !a.obs_var || !a.obs_count || !a.act_in || !a.env_state || !a.env_obs || !a.final_obs || !a.env_rew ||
         !a.env_term || !a.env_trunc || !a.ep_step || !a.ep_index || !a.ep_score || !a.ep_last_score || !a.ep_last_len ||
         !a.cursor)
-        return (int)hipErrorInvalidValue;
+        return false;
     const int64_t lf = xpa_small_rollout_lds_floats(a.n_envs, a.d_in, a.h0, a.h1, a.h2, a.k);
-    if (lf < 0 || lf > kRoLdsMax) return (int)hipErrorInvalidValue;
+    return lf >= 0 && lf <= kRoLdsMax;
+}
+
+template <class E>
+int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd, int32_t *log, int64_t capacity,
+                      int64_t snap_dim, float *scratch, xpa_stream_t stream) {
+    if (!ro_eval_args_ok<E>(a0, k, log, capacity, snap_dim, scratch)) return (int)hipErrorInvalidValue;
+    XpaSmallRolloutArgs a = *a0;
+    const int64_t lf = xpa_small_rollout_lds_floats(a.n_envs, a.d_in, a.h0, a.h1, a.h2, a.k);
     a.horizon = 1;
     a.buf_act = scratch;
     a.buf_logp = scratch + a.n_envs;
@@ -2752,6 +2789,50 @@ int small_rollout_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host
     ro_dispatch<true>(a->h0, a->act_code, [&](auto ACT, auto H0) {
         hipLaunchKernelGGL((small_rollout_batch_kernel<E, decltype(ACT)::value, decltype(H0)::value>),
                            dim3((unsigned)n_agents), dim3(kRoThreads), bytes, s, dev, dev_heads);
+    });
+    return xpa_launch_status();
+}
+
+// The non-pointer fields the evaluation form reads (seed apart): one instantiation, one LDS carve, one step count
+bool ro_eval_same_shape(const XpaSmallRolloutArgs &x, const XpaSmallRolloutArgs &y) {
+    return x.n_envs == y.n_envs && x.steps == y.steps && x.d_in == y.d_in && x.h0 == y.h0 && x.h1 == y.h1 &&
+           x.h2 == y.h2 && x.k == y.k && x.act_code == y.act_code && x.use_obsnorm == y.use_obsnorm &&
+           x.max_episode_steps == y.max_episode_steps && x.slope == y.slope && x.obs_clip == y.obs_clip &&
+           x.ld_obs == y.ld_obs && x.ld_act == y.ld_act;
+}
+
+// xpa_small_eval_batch for one env / head pair: every check on the host copies before any HIP call, the
+// instantiation (K32E's widths only) and the LDS size from block 0, one workgroup per agent
+template <class E>
+int small_eval_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host, const XpaSmallRolloutArgs *dev, int k,
+                            const XpaSmallRolloutHead *host_heads, const XpaSmallRolloutHead *dev_heads,
+                            const XpaSmallEval *host_evals, const XpaSmallEval *dev_evals, xpa_stream_t stream) {
+    constexpr bool kHead = !std::is_empty_v<typename E::Head>;
+    if (n_agents < 1 || n_agents > 0x7fffffff || !host || !dev || !host_evals || !dev_evals ||
+        (host_heads != nullptr) != kHead || (dev_heads != nullptr) != kHead)
+        return (int)hipErrorInvalidValue;
+    std::vector<uintptr_t> logs, scratches;
+    for (int64_t p = 0; p < n_agents; ++p) {
+        const XpaSmallEval &e = host_evals[p];
+        if (!ro_eval_args_ok<E>(host + p, k, e.log, e.capacity, e.snap_dim, e.scratch) ||
+            !ro_eval_same_shape(host[p], host[0]) || e.capacity != host_evals[0].capacity ||
+            e.snap_dim != host_evals[0].snap_dim)
+            return (int)hipErrorInvalidValue;
+        if (kHead && (!host_heads[p].logstd || !(host_heads[p].act_clip > 0.f))) return (int)hipErrorInvalidValue;
+        logs.push_back((uintptr_t)e.log);
+        scratches.push_back((uintptr_t)e.scratch);
+    }
+    for (auto *v : {&logs, &scratches}) {   // no two members share a log or a scratch
+        std::sort(v->begin(), v->end());
+        if (std::adjacent_find(v->begin(), v->end()) != v->end()) return (int)hipErrorInvalidValue;
+    }
+    const XpaSmallRolloutArgs *a = host;
+    const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
+    const size_t bytes = (size_t)lf * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    ro_dispatch<false>(a->h0, a->act_code, [&](auto ACT, auto H0) {
+        hipLaunchKernelGGL((small_eval_batch_kernel<E, decltype(ACT)::value, decltype(H0)::value>),
+                           dim3((unsigned)n_agents), dim3(kRoThreads), bytes, s, dev, dev_heads, dev_evals);
     });
     return xpa_launch_status();
 }
@@ -2878,6 +2959,28 @@ XPA_API int xpa_small_eval_mountaincar(const XpaSmallRolloutArgs *a, int32_t *lo
                                        float *scratch, xpa_stream_t stream) {
     return small_eval_launch<RoMountainCarCat>(a, 3, RoMountainCarCat::Head{}, log, capacity, snap_dim, scratch,
                                                stream);
+}
+
+XPA_API int xpa_small_eval_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                                 const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
+                                 const XpaSmallRolloutHead *dev_heads, const XpaSmallEval *host_evals,
+                                 const XpaSmallEval *dev_evals, xpa_stream_t stream) {
+    switch (env) {
+    case XPA_ENV_CARTPOLE:
+        return small_eval_batch_launch<RoCartPoleCat>(n_agents, host_blocks, dev_blocks, 2, host_heads, dev_heads,
+                                                      host_evals, dev_evals, stream);
+    case XPA_ENV_PENDULUM:
+        return small_eval_batch_launch<RoPendulumGauss>(n_agents, host_blocks, dev_blocks, 1, host_heads, dev_heads,
+                                                        host_evals, dev_evals, stream);
+    case XPA_ENV_ACROBOT:
+        return small_eval_batch_launch<RoAcrobotCat>(n_agents, host_blocks, dev_blocks, 3, host_heads, dev_heads,
+                                                     host_evals, dev_evals, stream);
+    case XPA_ENV_MOUNTAINCAR:
+        return small_eval_batch_launch<RoMountainCarCat>(n_agents, host_blocks, dev_blocks, 3, host_heads, dev_heads,
+                                                         host_evals, dev_evals, stream);
+    default:
+        return (int)hipErrorInvalidValue;
+    }
 }
 
 XPA_API int xpa_eval_post(int32_t *log, int64_t capacity, int64_t snap_dim, int64_t n_envs, const uint8_t *term,

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .small_path import small_close, small_close_args, small_close_batch, small_eval  # noqa: F401 (theirs)
+from .small_path import small_close, small_close_args, small_close_batch, small_eval, small_eval_batch  # noqa: F401
 
 ALGO = {"ppo": 0, "a2c": 1}
 DIST = {"gaussian": 0, "categorical": 1}
@@ -1551,6 +1551,29 @@ def eval_log_new(target, n_envs, snap_dim, device, capacity=None, guard=0):
     host[1], host[5], host[6] = int(target), capacity, int(snap_dim)
     host[total:] = -1
     return torch.as_tensor(host, device=device)
+
+
+def eval_logs_new(targets, n_envs, snap_dim, device, capacity=None, guard=0):
+    """A population's fresh logs in one tensor [P, eval_log_layout(capacity, snap_dim)[1] (+ guard)]: row p is member
+    p's log as eval_log_new makes it, with its own target targets[p]; one capacity for all (default max(targets) +
+    n_envs).  A row is a multiple of 16 B by construction (guard, in int32 words set to -1, must be a multiple of 4),
+    so every row is aligned as xpa_small_eval_batch requires."""
+    targets = [int(t) for t in targets]
+    capacity = max(targets) + int(n_envs) if capacity is None else int(capacity)
+    _, total = eval_log_layout(capacity, snap_dim)
+    if int(guard) % 4:
+        raise ValueError("guard: a multiple of 4 int32 words (the rows stay 16-B aligned)")
+    if device.type == "cuda" and int(lib().xpa_eval_log_ints(capacity, int(snap_dim))) != total:
+        raise _lib.XpaError("eval log layout: the library and ops.eval_log_layout disagree")
+    host = np.zeros((len(targets), total + int(guard)), np.int32)
+    host[:, 1], host[:, 5], host[:, 6] = targets, capacity, int(snap_dim)
+    host[:, total:] = -1
+    return torch.as_tensor(host, device=device)
+
+
+def eval_log_headers(logs):
+    """The header words of a population's logs [P, >= 8] as host ints [P, 8] (one D2H copy for all members)."""
+    return logs[:, :EVAL_LOG_HEADER].cpu().numpy()
 
 
 def eval_log_decode(words):

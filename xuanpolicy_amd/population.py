@@ -9,11 +9,16 @@ computing exactly what the single-agent launch computes.  So Population.train me
 bit for bit, and a member stays an ordinary agent before, between and after.
 
 plan_population decides eligibility from a facts record per member (host logic alone: no tensor, no device), in the
-style of rollout_plan.plan_rollout; there is no sequential fallback: an ineligible population raises."""
+style of rollout_plan.plan_rollout; there is no sequential fallback: an ineligible population raises.
+
+Evaluation is the same idea ("Population evaluation (K32EB)"): Population.test_device runs every member's
+test episodes through xpa_small_eval_batch — one launch per chunk for all members, each into its own row of one log
+tensor, and one read of the P headers — and means `[a.test_device(e, ...) for a, e in zip(agents, test_envs)]` bit for
+bit; plan_population_test decides its eligibility, and Population.test falls back to the loop over agent.test."""
 import ctypes
 from typing import NamedTuple
 
-from .rollout_plan import K32_DRIVERS, SMALL_BY_ENTRY
+from .rollout_plan import K32_DRIVERS, SMALL_BY_ENTRY, SMALL_ENVS, plan_test
 
 MAX_AGENTS = 65535   # the y extent of a launch grid (the update's agent dimension); not a function of the CU count
 
@@ -88,6 +93,59 @@ def plan_population(facts):
             seen[ptr] = i
     row = SMALL_BY_ENTRY[f0.entry]
     return PopulationPlan(len(facts), f0.entry, row.code, row.gaussian, f0.chunk, f0.gae == "K33")
+
+
+class EvalMemberFacts(NamedTuple):
+    """What plan_population_test decides from, one record per member and its test envs.  Population._test_facts
+    gathers it."""
+    eval: object             # the member's rollout_plan.EvalFacts for its test envs
+    activation: tuple        # (activation code, slope)
+    use_obsnorm: bool
+    obs_clip: float
+    max_episode_steps: int   # the test envs' time limit
+    tensors: tuple           # data pointers of the test envs' tensors and the member's obs statistics
+
+
+class PopulationTestPlan(NamedTuple):
+    n_agents: int
+    code: str            # the SMALL_ENVS row's XPA_ENV_* constant's name
+    gaussian: bool       # the head array (logstd, act_clip) is passed
+
+
+# the fields every member shares with member 0: (name in the error text, where it is read)
+_TEST_SHARED = (("env", lambda f: f.eval.env), ("dist", lambda f: f.eval.dist), ("small", lambda f: f.eval.small),
+                ("n_envs", lambda f: f.eval.n_envs), ("activation", lambda f: f.activation),
+                ("use_obsnorm", lambda f: f.use_obsnorm), ("obs_clip", lambda f: f.obs_clip),
+                ("max_episode_steps", lambda f: f.max_episode_steps))
+
+
+def plan_population_test(facts):
+    """The PopulationTestPlan of the members' evaluation facts (one K32EB launch serves them all), or ValueError naming
+    the first thing that rules it out.  The only place the population evaluation's eligibility is decided."""
+    facts = list(facts)
+    if not 1 <= len(facts) <= MAX_AGENTS:
+        raise ValueError("a population has 1 .. %d members, not %d" % (MAX_AGENTS, len(facts)))
+    for i, f in enumerate(facts):
+        if f.eval.world != 1:
+            raise ValueError("member %d: world size %d (a population is evaluated in one process: world must be 1)"
+                             % (i, f.eval.world))
+        tier = plan_test(f.eval)
+        if tier != "K32E":
+            raise ValueError("member %d: its test envs plan the %r tier, not the one-launch evaluation \"K32E\""
+                             % (i, tier))
+    f0 = facts[0]
+    for i, f in enumerate(facts[1:], 1):
+        for name, get in _TEST_SHARED:
+            if get(f) != get(f0):
+                raise ValueError("member %d differs from member 0 in %s: %r != %r" % (i, name, get(f), get(f0)))
+    seen = {}
+    for i, f in enumerate(facts):
+        for ptr in f.tensors:
+            if ptr in seen:
+                raise ValueError("members %d and %d share a tensor (data pointer 0x%x)" % (seen[ptr], i, ptr))
+        seen.update((ptr, i) for ptr in f.tensors)
+    row = SMALL_ENVS[f0.eval.env, f0.eval.dist]
+    return PopulationTestPlan(len(facts), row.code, row.gaussian)
 
 
 def _block_array(struct, blocks):
@@ -176,6 +234,7 @@ class Population:
         a0 = self.agents[0]
         self.device = a0.device
         self._blocks = _DeviceBlocks(self.device)
+        self._eval_blocks = _DeviceBlocks(self.device)   # test_device's arrays (they change with every set of test envs)
         self._perm = self._perm_keys = self._perm_host = None   # [P, n] permutations; (seeds, counters) on the device
         self._epochs = {}          # epoch key -> ["warm" | graph, per-slot launch arguments, their loss scalars]
         self._graph_pool = None
@@ -357,6 +416,112 @@ class Population:
                     a.update_log.extend(scalars[p, j].clone() for j in range(n_slots))
         for p, a in enumerate(agents):
             a._end_update(scalars[p, n_slots - 1])
+
+    # ---- evaluation ("Population evaluation (K32EB)") ------------------------------------------------
+    @staticmethod
+    def _test_facts(a, env):
+        f = a._eval_facts(env)
+        policy = a.learner.small_policy_layers()
+        tensors = ()
+        if plan_test(f) == "K32E":
+            ts = [env.state, env.obs, env.act_in, env.final_obs, env.rew, env.term, env.trunc, env.ep_step, env.ep_index,
+                  env.ep_score, env.ep_last_score, env.ep_last_len, a.obs_mean, a.obs_var, a.obs_count]
+            tensors = tuple(int(t.data_ptr()) for t in ts)
+        return EvalMemberFacts(f, (int(policy.code), float(policy.slope)) if policy else None, bool(a.use_obsnorm),
+                               float(a._obs_clip()), int(getattr(env, "max_episode_steps", 0) or 0), tensors)
+
+    def plan_test(self, test_envs):
+        """The PopulationTestPlan of the members over test_envs (one set of test envs per member), or ValueError."""
+        envs = list(test_envs)
+        if len(envs) != len(self.agents):
+            raise ValueError("test_envs: one set of test envs per member (%d members, %d sets)"
+                             % (len(self.agents), len(envs)))
+        return plan_population_test([self._test_facts(a, e) for a, e in zip(self.agents, envs)])
+
+    def test_device(self, test_envs, test_episode, chunk=None, rngs=None):
+        """[a.test_device(e, test_episode, chunk, rng) for a, e, rng in zip(agents, test_envs, rngs)] with every
+        member's steps in ONE launch per chunk (xpa_small_eval_batch) and one read of the P log headers after it:
+        each member's returned scores, last_test_log, obs statistics, test-env state and evaluation cursor are its own
+        call's, and nothing else of a member changes.  test_envs: one set of device envs per member; rngs: None or one
+        (seed, step) per member.  A member whose log is complete sits out the later launches (its workgroup returns at
+        once).  One stream, no graph capture; an ineligible population raises ValueError (plan_population_test): there
+        is no sequential fallback in here."""
+        import torch
+        from . import _lib, ops, small_path
+        agents, envs = self.agents, list(test_envs)
+        P = len(agents)
+        rngs = [None] * P if rngs is None else list(rngs)
+        if len(rngs) != P:
+            raise ValueError("rngs: None or one (seed, step) per member (%d members, %d given)" % (P, len(rngs)))
+        plan = self.plan_test(envs)
+        N, target = int(envs[0].num_envs), int(test_episode)
+        max_ep = int(getattr(envs[0], "max_episode_steps", 0) or 0)
+        if target < 1 or max_ep < 1:
+            raise ValueError("test_device: test_episode >= 1 and time-limited test envs (max_episode_steps)")
+        chunk = 128 if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("test_device: chunk >= 1")
+        dev = self.device
+        snap_dim = agents[0]._eval_scalars(envs[0])[0]   # one value: use_obsnorm and the observation width are shared
+        capacity = target + N
+        logs = ops.eval_logs_new([target] * P, N, snap_dim, dev)
+        scratch = torch.empty((P, 3 * N), dtype=torch.float32, device=dev)
+        blocks, heads, evals, cursors = [], [], [], []
+        for p, (a, env, rng) in enumerate(zip(agents, envs, rngs)):
+            env.reset()
+            seed, cursor = a._eval_stream(rng)
+            args, logstd = a._build_small_eval(env, seed, cursor)
+            args.steps = chunk
+            blocks.append(args)
+            cursors.append(cursor)   # an rng's cursor is this call's alone: alive until the last launch has run
+            if plan.gaussian:
+                heads.append(_lib.XpaSmallRolloutHead(logstd.data_ptr(), float(a._eval_scalars(env)[1])))
+            evals.append(_lib.XpaSmallEval(logs[p].data_ptr(), scratch[p].data_ptr(), capacity, snap_dim))
+        cache = self._eval_blocks
+        arrays = (cache.get(_block_array(_lib.XpaSmallRolloutArgs, blocks)),
+                  plan.gaussian and cache.get(_block_array(_lib.XpaSmallRolloutHead, heads)),
+                  cache.get(_block_array(_lib.XpaSmallEval, evals)))
+        bound = (target // N + 2) * max_ep
+        issued = 0
+        while True:
+            small_path.small_eval_batch(plan.code, P, *arrays, dev)
+            issued += chunk
+            head = ops.eval_log_headers(logs)   # [P, 8]: count, target, done, steps_run, overflow
+            for p in range(P):
+                if head[p, 4]:
+                    raise _lib.XpaError("test_device: member %d: the episode log overflowed (%d entries, capacity %d)"
+                                        % (p, head[p, 0], capacity))
+            if head[:, 2].all():
+                break
+            if issued >= bound:
+                p = int((head[:, 2] == 0).argmax())
+                raise RuntimeError("test_device: member %d: %d of %d episodes ended in %d steps (bound %d = "
+                                   "(test_episode // N + 2) * max_episode_steps)"
+                                   % (p, head[p, 0], target, head[p, 3], bound))
+        words = logs.cpu().numpy()
+        del cursors
+        scores = []
+        for p, a in enumerate(agents):
+            a.last_test_log = ops.eval_log_decode(words[p])
+            scores.append([float(s) for s in a.last_test_log["score"]])
+        return scores
+
+    def test(self, env_fn, test_episode):
+        """[a.test(env_fn, test_episode) for a in agents]: one env_fn() call per member, in member order.  Where every
+        member's config has device_test and plan_population_test admits the members over their test envs, the
+        evaluation is test_device's batch launches, followed by each member's own printing, log_infos and
+        test_envs.close() (agent._finish_test); otherwise it is that loop itself."""
+        from .agents import _cfg
+        agents = self.agents
+        if not all(bool(_cfg(a.config, "device_test", False)) for a in agents):
+            return [a.test(env_fn, test_episode) for a in agents]
+        envs = [env_fn() for _ in agents]
+        try:
+            self.plan_test(envs)
+        except ValueError:
+            return [a.test(lambda e=e: e, test_episode) for a, e in zip(agents, envs)]
+        scores = self.test_device(envs, test_episode)
+        return [a._finish_test(e, s) for a, e, s in zip(agents, envs, scores)]
 
     # ---- public API -------------------------------------------------------------------------------------------------
     def train(self, train_steps, log=True):

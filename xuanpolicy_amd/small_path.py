@@ -146,6 +146,15 @@ def small_eval(entry, args, log, capacity, snap_dim, scratch, logstd=None, act_c
               scratch.data_ptr(), _stream(log.device))
 
 
+def small_eval_batch(code, n_agents, blocks, heads, evals, device):
+    """K32EB (xpa_small_eval_batch): n_agents agents' K32E launches in one, each into its own log.  code: the
+    SMALL_ENVS row's; blocks, heads (None for a Categorical row) and evals (XpaSmallEval: log, scratch, capacity,
+    snap_dim per agent) as rollout_batch's: (ctypes array, its copy in device memory as a uint8 tensor)."""
+    _lib.call(_lib.load().xpa_small_eval_batch, _lib.ENV_CODES[code], n_agents, ctypes.addressof(blocks[0]),
+              blocks[1].data_ptr(), *_head_arrays(heads), ctypes.addressof(evals[0]), evals[1].data_ptr(),
+              _stream(device))
+
+
 def small_close(block, device):
     """K33 (xpa_small_close): one agent's closing — the deferred bootstraps' critic with K32's arithmetic, the
     fixup's writes and the advantage scan — in one launch.  block: small_close_args'."""
