@@ -809,6 +809,9 @@ class VecAgentRef:
         self.ret_rms = RunningMeanStdRef(())
         self.returns = np.zeros((self.n_envs,), np.float32)
         self.current_step = 0
+        # the return tracker's rule, the algorithm's own; the tests' negative controls give a loop the other one
+        self.mask_returns = algo == "ppo"
+        self.obs = None   # the raw observations the last train() call ended on (the loop's `obs`)
 
     def _proc_obs(self, obs):
         return process_observation(obs, self.obs_rms, self.obsnorm_range) if self.use_obsnorm else obs
@@ -849,7 +852,7 @@ class VecAgentRef:
                 if self.on_full is not None:
                     self.on_full(self)
                 self.memory.clear()
-            if self.algo == "ppo":
+            if self.mask_returns:
                 self.returns = (1 - terminals) * self.gamma * self.returns + rewards
             else:
                 self.returns = self.gamma * self.returns + rewards
@@ -869,6 +872,7 @@ class VecAgentRef:
                         self.memory.finish_path(vals[i], i)
                     obs[i] = infos[i]["reset_obs"]
             self.current_step += self.n_envs
+        self.obs = obs
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -23,14 +23,7 @@ import torch
 from oracle import cpu_ref
 from oracle.synth_env import DummyVecEnvRef, SynthAtariEnv, SynthBoxEnv, _Box, _Discrete
 from tests._oracle_replay import _load_by_order, replay_last_step_iteration
-from tests.test_gpu_kernels import _gae_close as _gae_close_kernels
-
-
-def _gae_close(got, ref, msg):
-    try:
-        _gae_close_kernels(got, ref)
-    except AssertionError as e:
-        raise AssertionError(msg + ": " + str(e)) from None
+from tests._vecloop_check import _check_rollout, _snapshot
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -41,58 +34,6 @@ def _setup():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cpu_ref.build_oracle()
-
-
-def _snapshot(mem):
-    out = {k: np.array(getattr(mem, k), copy=True) for k in ("observations", "actions", "rewards", "values", "terminals",
-                                                              "closed", "boot", "advantages", "returns")}
-    out["old_logp"] = np.array(mem.auxiliary_infos["old_logp"], copy=True) if "old_logp" in mem.auxiliary_infos else None
-    return out
-
-
-def _check_rollout(agent, ref, snap, it):
-    """The device buffer of one iteration against the reference loop's buffer at its full-buffer point."""
-    mem = agent.memory
-    msg = "iteration %d " % it
-    obs = mem.observations.cpu().numpy()
-    if obs.dtype == np.uint8:
-        np.testing.assert_array_equal(obs, snap["observations"], err_msg=msg + "frames")
-    else:
-        np.testing.assert_allclose(obs, snap["observations"], rtol=1e-5, atol=1e-5, err_msg=msg + "obs")
-    np.testing.assert_array_equal(mem.actions.cpu().numpy(), snap["actions"], err_msg=msg + "actions")
-    np.testing.assert_array_equal(mem.terminals.cpu().numpy(), snap["terminals"], err_msg=msg + "terminals")
-    np.testing.assert_array_equal(mem.closed.cpu().numpy(), snap["closed"], err_msg=msg + "closures")
-    np.testing.assert_allclose(mem.rewards.cpu().numpy(), snap["rewards"], rtol=1e-5, atol=1e-6, err_msg=msg + "rew")
-    np.testing.assert_allclose(mem.values.cpu().numpy(), snap["values"], rtol=1e-4, atol=1e-4, err_msg=msg + "values")
-    np.testing.assert_allclose(mem.boot.cpu().numpy(), snap["boot"], rtol=1e-4, atol=1e-4, err_msg=msg + "bootstraps")
-    if snap["old_logp"] is not None:
-        np.testing.assert_allclose(mem.auxiliary_infos["old_logp"].cpu().numpy(), snap["old_logp"], rtol=1e-4, atol=2e-4,
-                                   err_msg=msg + "old_logp")
-    # (1) the device's GAE of its own columns: the oracle's finish_path arithmetic at north_star's 1e-5
-    cols = [getattr(mem, k).cpu().numpy() for k in ("rewards", "values", "terminals", "closed", "boot")]
-    adv_d, ret_d = mem.advantages.cpu().numpy(), mem.returns.cpu().numpy()
-    adv_o, ret_o = cpu_ref.gae_rows(*cols, mem.gamma, mem.gae_lam)
-    _gae_close(adv_d, adv_o, msg + "adv (device columns)")
-    _gae_close(ret_d, ret_o, msg + "ret (device columns)")
-    # (2) against the reference loop's own finish_path results: the columns differ by the f32-vs-f64 rounding held
-    # above (values / bootstraps 1e-4, rewards 1e-5), and a discounted sum of such differences is bounded by the
-    # measured column differences propagated through the scan: |d adv| <= (|d r| + (1 + gamma) |d v| + gamma |d boot|)
-    # / (1 - gamma lambda) — an envelope measured on the case, not a blanket tolerance
-    g, lam = float(mem.gamma), float(mem.gae_lam)
-    dr = np.abs(cols[0] - snap["rewards"]).max()
-    dv = np.abs(cols[1] - snap["values"]).max()
-    db = np.abs(cols[4] - snap["boot"]).max()
-    env_adv = (dr + (1 + g) * dv + g * db) / (1 - g * lam) + 1e-6
-    np.testing.assert_allclose(adv_d, snap["advantages"], rtol=0, atol=env_adv, err_msg=msg + "adv (reference loop)")
-    np.testing.assert_allclose(ret_d, snap["returns"], rtol=0, atol=env_adv + dv, err_msg=msg + "ret (reference loop)")
-    assert env_adv < 2e-3, (msg, "envelope", env_adv)
-    if agent.use_obsnorm:
-        np.testing.assert_allclose(agent.obs_mean.cpu().numpy(), ref.obs_rms.mean, rtol=1e-5, atol=1e-6)
-        np.testing.assert_allclose(agent.obs_var.cpu().numpy(), ref.obs_rms.var, rtol=1e-5, atol=1e-6)
-        assert abs(float(agent.obs_count) - ref.obs_rms.count) < 1e-6
-    np.testing.assert_allclose(float(agent.ret_mean), float(ref.ret_rms.mean), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(float(agent.ret_var), float(ref.ret_rms.var), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(agent.returns.cpu().numpy(), ref.returns, rtol=1e-5, atol=1e-5)
 
 
 def _run(agent, host, ref_env, pol, algo, discrete, A, ent, n_epoch, n_mb, atari, first_calls):
