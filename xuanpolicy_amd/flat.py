@@ -7,7 +7,9 @@ Every parameter of the policy becomes a view into one contiguous fp32 buffer, an
     torch's per-tensor multi_tensor_apply kernels (ppoclip_learner.py:47-49 semantics, see optim.hip).
 The torch.optim.Adam object handed in by the runner (runner_drl.py:71) stays the source of truth for
 hyper-parameters (lr as stepped by LinearLR, betas, eps) and its .state holds views of the flat moment
-buffers, so optimizer.state_dict() / load_state_dict() keep working.
+buffers, so optimizer.state_dict() describes what the kernels write.  optimizer.load_state_dict() replaces those
+tensors; FusedClipAdam registers a load_state_dict post hook that copies the loaded moments into the flat buffers in
+place, takes the loaded step, re-points optimizer.state at the views and drops an open schedule window.
 """
 import torch
 
@@ -122,16 +124,36 @@ class FusedClipAdam:
         self.total_norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_count = 0
         self._step_t = torch.zeros((), dtype=torch.float32)  # shared CPU 'step' like torch's Adam state
-        for p, off in zip(flat.params, flat.offsets):
-            k = p.numel()
-            st = optimizer.state.get(p, {})
-            if "exp_avg" in st:  # migrate existing state
-                self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
-                self.step_count = int(float(st["step"]))
-            optimizer.state[p] = {"step": self._step_t, "exp_avg": self.exp_avg[off:off + k].view_as(p),
-                                  "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p)}
+        self._adopt_state(optimizer)                         # migrate existing state
+        optimizer.register_load_state_dict_post_hook(self._adopt_state)
+
+    def _adopt_state(self, optimizer):
+        """Make the flat buffers the optimizer's state again: at construction, and after every
+        optimizer.load_state_dict(), which replaces the tensors in optimizer.state[p].  The loaded moments are copied
+        into the existing buffers IN PLACE (their pointers are kernel arguments of captured graphs), step_count follows
+        the loaded step, optimizer.state[p] points at the views again and an open schedule window is dropped, so the
+        next ensure_window() refills it from the loaded step.  A parameter without loaded moments starts from zero."""
+        steps = set()
+        with torch.no_grad():
+            for p, off in zip(self.fs.params, self.fs.offsets):
+                k = p.numel()
+                m, v = self.exp_avg[off:off + k], self.exp_avg_sq[off:off + k]
+                st = optimizer.state.get(p, {})
+                if "exp_avg" in st:
+                    if st["exp_avg"].data_ptr() != m.data_ptr():
+                        m.copy_(st["exp_avg"].reshape(-1))
+                    if st["exp_avg_sq"].data_ptr() != v.data_ptr():
+                        v.copy_(st["exp_avg_sq"].reshape(-1))
+                    steps.add(int(float(st["step"])))
+                else:
+                    m.zero_()
+                    v.zero_()
+                optimizer.state[p] = {"step": self._step_t, "exp_avg": m.view_as(p), "exp_avg_sq": v.view_as(p)}
+        if len(steps) > 1:
+            raise ValueError("FusedClipAdam keeps one Adam step for all parameters (loaded: %s)" % sorted(steps))
+        self.step_count = steps.pop() if steps else 0
         self._step_t.fill_(float(self.step_count))
+        self._sched_lrs = None                               # _window_valid: the table no longer matches this state
 
     def step(self, max_norm, sq=None):
         """max_norm: the clip_grad_norm_ bound, or None for no clipping (max_norm = 0 zeroes the gradient,
