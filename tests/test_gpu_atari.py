@@ -213,7 +213,8 @@ def _replay_atari(g, env, conv_path, efac=3, rtol=1e-4, base_atol=1e-5, lockstep
     fcn = lrn._fused_cnn()
     assert fcn is not None, "the explicit CNN path (fused_cnn) must run"
     if filters[:2] == [32, 64]:   # the production first convs: K25 / K26 / K27
-        assert fcn.trunk_.u8_conv1 and fcn.trunk_._dgrad_ok(fcn.trunk_.convs[1][0])
+        plan = fcn.trunk_.plan(torch.empty((N * T // n_mb, 0), dtype=torch.uint8, device=DEV))   # (rows, kind)
+        assert plan.convs[0].fwd == "K25" and plan.convs[1].dgrad == "K27"
     buf = DummyOnPolicyBuffer_Atari(_Box(), _Disc(), {"old_logp": ()} if ppo else {}, N, T, True, True, 0.99, 0.95,
                                     device=DEV)
     assert buf.observations.dtype == torch.uint8

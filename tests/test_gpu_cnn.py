@@ -101,7 +101,8 @@ def test_fused_cnn_matches_autograd(B, conv_path):
     for p in pol.parameters():
         p.grad = torch.full_like(p, float("nan"))   # every gradient must be overwritten
     h2, _, v2, ctx = fc.forward(x)
-    (hs, _, flat, fouts), s_state, _, _ = ctx
+    tctx, s_state, _, _ = ctx
+    hs, flat, fouts = tctx.hs, tctx.flat, tctx.fouts
     # float64 CPU reference through the reference-layout modules (NCHW convs with bias, Flatten in (C, H, W)
     # order).  Its ReLUs take their masks from the explicit path's own activations: a unit within an ulp of the
     # kink may flip between two f32 paths (different conv algorithms), which would move that unit's whole
@@ -196,7 +197,8 @@ def test_fused_qnetwork_matches_autograd(B):
     q, ctx = fq.forward(x)
     tq = fq.target(x)
     torch.testing.assert_close(tq, q, rtol=1e-6, atol=1e-6)   # target = deep copy of eval at construction
-    (hs, am, _, _), s, outs = ctx
+    tctx, s, outs = ctx
+    hs, am = tctx.hs, tctx.am
     pol64 = copy.deepcopy(pol).to("cpu").double()
     masks = [(y > 0).permute(0, 3, 1, 2).cpu().double() for y in hs[1:]]
     h = (x.cpu().double() / 255.0).permute(0, 3, 1, 2)
@@ -493,7 +495,7 @@ def test_fc_act_fused_backward_equals_k22_path(monkeypatch):
         fc = FusedCNNActorCritic(pol)
         for p in pol.parameters():
             p.grad = torch.full_like(p, float("nan"))
-        assert fc.trunk_._fc_fuse_ok(B) == fuse
+        assert (fc.trunk_.plan(x).fc0_dx == "K40G-act") is fuse
         _, _, _, ctx = fc.forward(x)
         fc.backward(ctx, d_head, d_v)
         torch.cuda.synchronize()

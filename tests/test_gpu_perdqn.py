@@ -91,7 +91,8 @@ def test_perdqn_learner_replays_reference(golden, fixture, conv_path):
     fq = lrn._fused_q()
     assert fq is not None
     if net[:2] == [32, 64]:
-        assert fq.eval_trunk.u8_conv1 and fq.eval_trunk._dgrad_ok(fq.eval_trunk.convs[1][0])
+        plan = fq.eval_trunk.plan(torch.empty((B, 0), dtype=torch.uint8, device=DEV))   # (rows, kind)
+        assert plan.convs[0].fwd == "K25" and plan.convs[1].dgrad == "K27"
     for k in range(n_up):
         obs, act, rew, nxt, term = _perdqn_batch(seed, k, B, A)
         td, info = lrn.update(torch.as_tensor(obs, device=DEV), act, rew, torch.as_tensor(nxt, device=DEV), term)
@@ -112,7 +113,7 @@ def test_perdqn_learner_replays_reference(golden, fixture, conv_path):
 @pytest.mark.parametrize("filters", [[8, 8], [32, 64]])
 def test_perdqn_agent_loop_on_device(filters, conv_path):
     """[8, 8]: the r02 intermittent-fault configuration (4 / 8-channel convs), which since r03 runs K28 / K29 for every
-    conv — the small-channel MIOpen route it faulted on is refused (fused_cnn._library_conv_guard, tested below);
+    conv — the small-channel MIOpen route it faulted on is refused (cnn_plan.plan_cnn, tested below);
     [32, 64]: the production first two convs (K25 / K26 / K27; conv2's weight gradient on K29 or MIOpen per
     conv_path).  Every device error word stays 0."""
     from xuanpolicy_amd.runner import build_perdqn

@@ -376,8 +376,8 @@ def test_fc_weight_gradient_split_matches_library(monkeypatch):
     B = 16384
     x = torch.randint(0, 256, (B, 84, 84, 4), dtype=torch.int32, device=DEV).to(torch.uint8)
     s, ctx = tr.forward(x)
-    hs, am, flat, fouts = ctx
-    assert tr._fc_wsplit_rows(B)
+    flat = ctx.flat
+    assert ctx.plan.fc0_dw == "K41V"
     g = torch.randn(B, 512, device=DEV) * 1e-3
     tr._dw_tmp = torch.empty_like(tr.fc[0][0].weight)
     assert tr._fc0_wgrad_split(g, flat)

@@ -6,34 +6,60 @@ Flatten, fc blocks), Basic_CNN cnn.py:5-40 (conv blocks, AdaptiveMaxPool2d((1, 1
 xuance/torch/utils/layers.py:8-57, Categorical_AC_Policy xuance/torch/policies/categorical.py:61-85, BasicQnetwork
 deterministic.py:148-182; the learners' loss.backward() (a2c_learner.py:31-33, perdqn_learner.py:37-40).
 
-Every activation stays NHWC ([rows = B*H*W, C] row-major), the layout the uint8 frames arrive in:
-  forward   the first conv block: K25 xpa_conv1_u8_fwd (the 4 x 8 x 8 -> 32 conv on fp32 MFMA straight from the uint8
-            frames as sum x (w / 255) — one f32 rounding per term like the reference's sum float(x / 255) w —, bias
-            + ReLU in its epilogue); other first layers: K20 xpa_frames_to_f32 then MIOpen as below
-            -> per conv: MIOpen conv2d without bias on the channels-last view -> K21 xpa_bias_act (bias + ReLU
-               in place)
-            -> AC_CNN_Atari: Flatten in NHWC order — the first fc layer uses its weight with the columns permuted
-               from the reference's (C, H, W) order to (H, W, C) (one 13 MB copy per parameter update, instead of an
-               NHWC -> NCHW copy of the [B, 6400] activations every forward) -> fc: hipBLASLt GEMM (bias epilogue)
-               -> K21 ReLU in place;
-               Basic_CNN: K23 xpa_global_maxpool (max + argmax per (b, c), torch's tie rule)
-            -> heads / Q head (GEMMs)
-  backward  heads: GEMMs + K10 / K22 bias column sums -> AC_CNN_Atari fc: K22 xpa_act_bwd_bias (ReLU backward + bias
-            gradient) -> dW GEMM (permuted back into the reference layout) + dX GEMM; Basic_CNN: K24 (the pooled
-            gradient routed to the argmax, ReLU backward, bias gradient) -> per conv: K22 then MIOpen
-            convolution_backward (weight; data too except where K27 xpa_conv_dgrad_s2k takes the data gradient — the
-            4 x 4 stride-2 32 -> 64 conv); the first conv (no dX) after K25: K26 xpa_conv1_u8_wgrad_act from the uint8
-            frames with its ReLU backward + bias gradient folded in (no K22 pass) + the f64 column-sum finalizes (no
-            f32 frame copy anywhere).
+Every activation stays NHWC ([rows = B*H*W, C] row-major), the layout the uint8 frames arrive in.  A trunk's forward
+and backward run from a CnnPlan (cnn_plan.py): _Trunk.plan is the only reader of the switches and the only place a
+capability is tested, the stages dispatch on the plan's fields ("Where the CNN trunk's forms are
+decided"):
+  frames    "forward": K20 xpa_frames_to_f32 ahead of the first conv; "backward": K25 read the uint8 frames and only
+            the first conv's library weight gradient needs the f32 copy; "none": K25 + K26, no f32 frames anywhere
+  fwd       per conv block: "K25" xpa_conv1_u8_fwd (the 4 x 8 x 8 -> 32 conv on fp32 MFMA straight from the uint8
+            frames as sum x (w / 255) — one f32 rounding per term like the reference's sum float(x / 255) w —, bias +
+            activation in its epilogue), "K28" xpa_conv_fwd (the same epilogue; the last block's output with `slack`
+            floats after it), "miopen" (conv2d without bias on the channels-last view + K21 xpa_bias_act in place)
+  tail      AC_CNN_Atari: Flatten in NHWC order — the first fc layer uses its weight with the columns permuted from
+            the reference's (C, H, W) order to (H, W, C) (one 13 MB copy per parameter update, instead of an
+            NHWC -> NCHW copy of the [B, 6400] activations every forward); Basic_CNN: K23 xpa_global_maxpool (max +
+            argmax per (b, c), torch's tie rule)
+  fc0_fwd   "K40G" (the three-way split on the bf16 matrix cores + K21) or "linear" (hipBLASLt + K21)
+  fc0_dw    "K41V" / "K41V-padded" (split weight-gradient slices + the batched f64 finalize) or "mm"; permuted back into
+            the reference layout either way
+  fc0_dx    "K40G-act" (the last conv block's activation backward + bias partials in its epilogue), "K40G" or "mm"
+  act_bwd   who forms a conv block's dz and bias gradient: "K22" xpa_act_bwd_bias, "K24" (the pooled gradient routed
+            to the argmax), "K26" / "K29" (folded into the weight gradient), "K40G-act", "K28-dgrad" (the epilogue of
+            the following block's data gradient)
+  wgrad     "K26" xpa_conv1_u8_wgrad_act (from the uint8 frames), "K29" xpa_conv_wgrad, "miopen"
+  dgrad     "K27" xpa_conv_dgrad_s2k (the 4 x 4 stride-2 32 -> 64 conv), "K28" xpa_conv_dgrad, "miopen", "none"
+The heads / Q head are GEMMs + K21 forward, GEMMs + K10 / K22 bias column sums backward.
 Parameter gradients are written into the parameters' .grad views (allocated when missing).
 """
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .fused_mlp import _act_code, _parse
+from .cnn_plan import CnnFacts, CnnPlan, conv_facts, k22_width, out_hw, plan_cnn
+from .fused_mlp import _act_code, _no_form, _parse
 from .policies import AC_CNN_Atari, Basic_CNN, policy_discrete
+
+
+def _out_hw(conv, H, W):
+    return out_hw(H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+
+
+def _conv_facts(conv, code, igemm_ok=None):
+    return conv_facts(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
+                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok)
+
+
+class _Ctx(NamedTuple):
+    """What a trunk forward leaves for its backward."""
+    hs: list          # the uint8 frames (K25) or their f32 copy, then every conv block's output (NHWC)
+    am: object        # the max pool's argmax, or None
+    flat: object      # the first fc layer's input, or None
+    fouts: list       # the fc layers' outputs
+    plan: CnnPlan
 
 
 def _conv_layers(model):
@@ -100,7 +126,7 @@ def _act_bwd_bias(parts, code, g2d, h2d, slope, bias_grad):
     L, s = ops.lib(), ops._stream(g2d.device)
     if not g2d.is_contiguous():
         raise ValueError("gradient rows must be contiguous")
-    k22 = cols % 4 == 0 and 256 % (cols // 4) == 0
+    k22 = k22_width(cols)
     part = parts.get(rows, cols, g2d.device, k22)
     hp = ops._p(h2d) if code else None
     gp = ops._p(g2d) if code else None
@@ -115,7 +141,7 @@ def _chain(layers, x):
     outs, h = [], x
     for lin, code, slope in layers:
         h = F.linear(h, lin.weight, lin.bias)
-        if code and h.shape[1] % 4 == 0 and 256 % (h.shape[1] // 4) == 0:
+        if code and k22_width(h.shape[1]):
             _bias_act(code, h, None, slope)   # K21 in place
         elif code == 1:
             F.leaky_relu(h, slope, inplace=True)
@@ -141,19 +167,6 @@ def _chain_backward(parts, layers, inputs, outs, g, acc=None, need_dx=True):
     return g
 
 
-def _library_conv_guard(conv):
-    """The explicit CNN path refuses MIOpen for convolutions with fewer than 16 input or output channels.  The r02
-    intermittent hipErrorIllegalAddress of the PER-DQN agent loop (2 of 9 runs, 8-channel test net)
-    surfaced at the first host sync after one agent step whose only library convolutions were MIOpen's NHWC kernels
-    for 4 / 8-channel shapes; every hand-written kernel of that step carries a device error word since r03 and
-    reported 0 in every later run.  K28 / K29 take every such conv, so reaching MIOpen here means use_igemm was turned
-    off (or a shape K28 / K29 reject): an error instead of the unproven route."""
-    if min(conv.in_channels, conv.out_channels) < 16:
-        raise RuntimeError("conv %d -> %d channels: the small-channel MIOpen route is refused (r02 fault suspect); "
-                           "keep use_igemm on (K28 / K29 take convs with in_channels %% 4 == 0, <= 64 channels)"
-                           % (conv.in_channels, conv.out_channels))
-
-
 def _ensure_grads(params):
     for p in params:
         if p.grad is None:
@@ -173,14 +186,13 @@ class _Trunk:
         self.rep = rep
         self.convs, self.tail, self.fc = _conv_layers(rep.model)
         for conv, _, _ in self.convs:
-            if conv.out_channels % 4 or 256 % (conv.out_channels // 4):
+            if not k22_width(conv.out_channels):
                 raise ValueError("conv channels must be a multiple of 4 dividing 1024")
         C, H, W = rep.input_shape
         self.in_hwc = (H, W, C)
         shape = (C, H, W)
         for conv, _, _ in self.convs:
-            k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-            shape = (conv.out_channels, (shape[1] + 2 * p - k) // s + 1, (shape[2] + 2 * p - k) // s + 1)
+            shape = (conv.out_channels,) + _out_hw(conv, shape[1], shape[2])
         self._chw = shape
         if self.tail == "flatten" and self.fc[0][0].in_features != shape[0] * shape[1] * shape[2]:
             raise ValueError("fc input width does not match the conv output")
@@ -189,26 +201,87 @@ class _Trunk:
         self._fcs = None        # K40G planes of _w_hwc (forward k halves, data-gradient column blocks) + their version
         self.stale = True
         self._dw_tmp = None
+        self._fcq = ops.ColsumQueue()   # K41V's batched finalize
+        self.err = None         # K24's device error word (argmax outside [0, HW)), made by the first backward
+        self._plans = {}        # (switches, B, the input's kind, conv 0's gradient layout) -> CnnPlan
+        self.last_plan = None   # the plan of the latest forward
         self.parts = parts
         self.n_params = 2 * (len(self.convs) + len(self.fc))
+        # the static shape rules of K27 / K28 / K29, asked once (the library's xpa_conv_igemm_ok included)
+        igemm_ok = ops.lib().xpa_conv_igemm_ok
+        self.conv_facts = tuple(_conv_facts(conv, code, igemm_ok) for conv, code, _ in self.convs)
         # K25: the first conv block straight from the uint8 frames (4 channels, 8 x 8 kernel, 32 outputs: the Nature
         # CNN's first layer); the f32 frame copy (K20) is then only made in the backward, for MIOpen's weight gradient
-        c0 = self.convs[0][0]
-        self.u8_conv1 = (C == 4 and c0.in_channels == 4 and c0.out_channels == 32 and tuple(c0.kernel_size) == (8, 8)
-                         and c0.stride[0] == c0.stride[1] and c0.padding[0] == c0.padding[1]
-                         and c0.padding_mode == "zeros")
+        c0 = self.conv_facts[0]
+        self.u8_conv1 = C == 4 and c0.cin == 4 and c0.cout == 32 and c0.k == 8 and c0.square and c0.zeros
         # a small-channel conv (< 16 in or out) must run on K28 / K29 (forward, weight gradient and, past the first
-        # block, the data gradient): MIOpen's small-channel route is refused (_library_conv_guard).  A net with such
-        # a conv that K28 / K29 cannot take (e.g. a 3-channel RGB first conv, in_channels % 4 != 0) gets no explicit
-        # path: ValueError here sends the learner to the generic autograd path instead of failing mid-update.
-        for i, (conv, _, _) in enumerate(self.convs):
-            if min(conv.in_channels, conv.out_channels) >= 16 or (i == 0 and self.u8_conv1):
+        # block, the data gradient): the planner refuses MIOpen's small-channel route.  A net with such a conv that
+        # K28 / K29 cannot take (e.g. a 3-channel RGB first conv, in_channels % 4 != 0) gets no explicit path:
+        # ValueError here sends the learner to the generic autograd path instead of failing mid-update.
+        for i, c in enumerate(self.conv_facts):
+            if min(c.cin, c.cout) >= 16 or (i == 0 and self.u8_conv1):
                 continue
-            if not self._igemm_shape_ok(conv) or (i > 0 and not self._dgrad_ok(conv)
-                                                  and not self._igemm_dgrad_shape_ok(conv)):
+            if not c.igemm or (i > 0 and not c.k27 and not c.igemm_dgrad):
                 raise ValueError("conv %d -> %d channels (kernel %s): no K28 / K29 form and the small-channel "
-                                 "library route is refused" % (conv.in_channels, conv.out_channels,
-                                                              tuple(conv.kernel_size)))
+                                 "library route is refused" % (c.cin, c.cout, tuple(self.convs[i][0].kernel_size)))
+
+    # The switches (read by plan() alone).
+    # use_igemm: K28 / K29 for the convs they take (False: MIOpen for every conv, the r02 path).  They hold one weight
+    # image per CU and tile the output rows 32 at a time per wave, so below ~1 M output rows (igemm_min_rows) a launch
+    # has too few tiles per CU to balance (C5's batch 2048 = 800 rows per CU = 25 tiles over 16 waves) and MIOpen's
+    # kernels measure faster there (tools/c5_ab.py: 2.26 vs 2.65 ms per C5 learner step; C3's rollout forwards at 1024
+    # frames 71 vs 84-94 us).  Small-channel convs (< 16 in or out: the test nets, r02's fault suspect) always take
+    # K28 / K29.
+    use_igemm = True
+    igemm_min_rows = 1 << 20
+    # r05, fc_split: the first fc layer of the update's minibatches (C3: [16384, 6400] x [6400, 512]) on the bf16 matrix
+    # cores by the three-way split (K40G: one launch per GEMM; forward in 2 k halves x 256-column blocks, summed in a
+    # fixed order; the data gradient in 256-column blocks, the last one aligned to the end so no block is padded — the
+    # columns it shares with its neighbour come out bit-identical from both).  The rollout's 1024-frame forwards stay
+    # on hipBLASLt (fc_split_min_rows).
+    fc_split = True
+    fc_split_min_rows = 8192
+    # r05, fc_fuse_act: with the fc split, the data gradient's epilogue also applies the last conv block's activation
+    # backward and writes its bias-gradient partials (xpa_s3_gemm_group_act): that block's K22 pass over
+    # [B x H x W, C] is gone
+    fc_fuse_act = True
+    # r06, fc_wsplit: the first fc layer's weight gradient on the split too (was hipBLASLt's f32 GEMM: 822 us per C3
+    # minibatch, profiles/r05/r05k28b): dW^T = flat^T g as K41V slices per 256-column half of g (AC_CNN_Atari: flat
+    # [B, 6400] = 50 row tiles of 128; a width that is not a multiple of 128 takes the padded form, the columns past a
+    # row reading the next row or the slack the forward leaves after the last row, into output rows the finalize map
+    # drops); the batched f64 finalize writes the kept rows transposed into dW.  Same row rule as the forward's split.
+    fc_wsplit = True
+
+    def _grads0_contig(self):
+        """Conv 0's weight and bias gradients are contiguous, as K26 writes them (a missing one is allocated so)."""
+        c0 = self.convs[0][0]
+        return all(p.grad is None or p.grad.is_contiguous() for p in (c0.weight, c0.bias))
+
+    def _pass_facts(self, B, x_u8):
+        """What can differ between two passes of this trunk (CnnFacts' last fields, and the plan cache's key): the only
+        reader of the switches above and of ops.S3_GEMMS."""
+        return (B, x_u8, self._grads0_contig(), self.use_igemm, self.igemm_min_rows, self.fc_split,
+                self.fc_split_min_rows, self.fc_fuse_act, self.fc_wsplit, ops.S3_GEMMS)
+
+    def facts(self, B, x_u8=True):
+        """The CnnFacts of a pass over B frames (x_u8: a contiguous uint8 device tensor, what the agents feed)."""
+        lin = self.fc[0][0] if self.fc else None
+        return CnnFacts(self.conv_facts, self.in_hwc, self.tail,
+                        (lin.in_features, lin.out_features) if lin is not None else None,
+                        tuple((lin.out_features, code) for lin, code, _ in self.fc), self.u8_conv1,
+                        *self._pass_facts(B, x_u8))
+
+    def plan(self, x):
+        """The CnnPlan of one forward + backward over the frames x (of which only the rows, the dtype, the contiguity
+        and the device type are read).  Host logic alone (cnn_plan.plan_cnn), cached under every switch's value, B, the
+        input's kind and conv 0's gradient layout: a switch flipped later takes effect, a steady pass pays one
+        lookup."""
+        x_u8 = x.dtype == torch.uint8 and x.is_contiguous() and x.device.type == "cuda"
+        key = self._pass_facts(x.shape[0], x_u8)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = plan_cnn(self.facts(x.shape[0], x_u8))
+        return plan
 
     def params(self):
         out = []
@@ -233,21 +306,6 @@ class _Trunk:
             self.stale = False
             self._w_ver += 1
         return self._w_hwc
-
-    # r05: the first fc layer of the update's minibatches (C3: [16384, 6400] x [6400, 512]) on the bf16 matrix cores by
-    # the three-way split (K40G: one launch per GEMM; forward in 2 k halves x 256-column blocks, summed in a fixed
-    # order; the data gradient in 256-column blocks, the last one aligned to the end so no block is padded — the
-    # columns it shares with its neighbour come out bit-identical from both).  The rollout's 1024-frame forwards stay
-    # on hipBLASLt (fc_split_min_rows).  The weight gradient stays on hipBLASLt.
-    fc_split = True
-    fc_split_min_rows = 8192
-
-    def _fc_split_ok(self, rows):
-        if not (self.fc_split and ops.S3_GEMMS and self.tail == "flatten" and rows >= self.fc_split_min_rows):
-            return False
-        lin = self.fc[0][0]
-        return lin.out_features % 256 == 0 and lin.in_features % 32 == 0 and lin.in_features >= 512 and \
-            lin.out_features // 256 * 2 <= 32 and (lin.in_features + 255) // 256 <= 32
 
     def _fc_planes(self):
         """The split planes of the current _w_hwc: forward (column block j, k half p) and data-gradient column
@@ -285,16 +343,6 @@ class _Trunk:
         _bias_act(code, s, lin.bias, slope)
         return s
 
-    # r05: with the fc split, the data gradient's epilogue also applies the last conv block's activation backward and
-    # writes its bias-gradient partials (xpa_s3_gemm_group_act): that block's K22 pass over [B x H x W, C] is gone
-    fc_fuse_act = True
-
-    def _fc_fuse_ok(self, rows):
-        conv, code, _ = self.convs[-1]
-        in_f = self.fc[0][0].in_features
-        return (self.fc_fuse_act and self._fc_split_ok(rows) and in_f % 256 == 0 and conv.out_channels in (32, 64)
-                and code in (0, 1, 2))
-
     def _fc0_dgrad_split_act(self, g, y_flat):
         """dz of the last conv block (its output gradient x act'(its output)) from the fc's K40G data gradient, and
         that block's bias gradient (f64 finalize of the per-block partials)."""
@@ -310,31 +358,17 @@ class _Trunk:
         _lib.call(ops.lib().xpa_colsum_finalize, ops._p(part), G, C, ops._p(conv.bias.grad), ops._stream(g.device))
         return dz
 
-    # r06: the first fc layer's weight gradient on the split too (was hipBLASLt's f32 GEMM: 822 us per C3 minibatch,
-    # profiles/r05/r05k28b): dW^T = flat^T g as K41V slices per 256-column half of g (AC_CNN_Atari: flat [B, 6400] =
-    # 50 row tiles of 128; a width that is not a multiple of 128 takes the padded form, the columns past a row reading
-    # the next row or the slack the forward leaves after the last row, into output rows the finalize map drops); the
-    # batched f64 finalize writes the kept rows transposed into dW.  Same row rule as the forward's split
-    # (fc_split_min_rows).
-    fc_wsplit = True
-
-    def _fc_wsplit_rows(self, rows):
-        lin = self.fc[0][0] if self.fc else None
-        return (self.fc_wsplit and lin is not None and ops.S3_GEMMS and self.tail == "flatten"
-                and rows >= self.fc_split_min_rows and lin.out_features % 256 == 0 and lin.in_features % 4 == 0)
-
     def _fc0_wgrad_split(self, g, flat):
-        """self._dw_tmp = g^T flat ([out, in], the forward's (H, W, C) column order) on K41V; False (nothing done) where it
-        does not apply."""
+        """K41V / K41V-padded (by flat's width): self._dw_tmp = g^T flat ([out, in], the forward's (H, W, C) column
+        order).  Returns True; raises where the buffers do not meet the form (rows not contiguous, or a ragged width
+        without the forward's slack after the last row)."""
         rows, in_f = flat.shape
         m = (in_f + 127) // 128 * 128
-        if not (self._fc_wsplit_rows(rows) and g.is_contiguous() and flat.stride(1) == 1 and flat.stride(0) == in_f
+        if not (g.is_contiguous() and flat.stride(1) == 1 and flat.stride(0) == in_f
                 and flat.untyped_storage().nbytes() // 4 >= flat.storage_offset() + (rows - 1) * in_f + m):
-            return False
+            _no_form("the fc weight gradient on these buffers", "K41V" if m == in_f else "K41V-padded")
         out_f = g.shape[1]
         S = ops.s3_wgrad_slices(rows, m)
-        if getattr(self, "_fcq", None) is None:
-            self._fcq = ops.ColsumQueue()
         for h in range(out_f // 256):
             part = self.parts.buf(("fcw", h, S, m), (S, m, 256), g.device)
             ops.s3_wgrad(flat, g[:, 256 * h:256 * (h + 1)], out=part, slices=S, m=m if m != in_f else None)
@@ -364,7 +398,7 @@ class _Trunk:
         conv, code, slope = self.convs[0]
         B, H, W, C = xu.shape
         k, st, pd = 8, conv.stride[0], conv.padding[0]
-        OH, OW = (H + 2 * pd - k) // st + 1, (W + 2 * pd - k) // st + 1
+        OH, OW = _out_hw(conv, H, W)
         w = conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous()
         y = torch.empty((B, OH, OW, 32), dtype=torch.float32, device=xu.device)
         _lib.call(ops.lib().xpa_conv1_u8_fwd, code, ops._p(xu), B, H, W, C, k, st, pd, ops._p(w), ops._p(conv.bias), 32,
@@ -377,33 +411,25 @@ class _Trunk:
         as its first entry (backward converts them for the first conv's weight gradient)."""
         B = x.shape[0]
         xu = x.reshape((B,) + self.in_hwc)
-        if self.u8_conv1 and xu.dtype == torch.uint8 and xu.is_contiguous() and xu.device.type == "cuda":
-            h = self._conv1_u8(xu)
-            hs = [xu, h]
-            convs = self.convs[1:]
-        else:
-            h = self.frames(xu)
-            hs = [h]
-            convs = self.convs
-        last = convs[-1][0] if convs else None
-        for conv, code, slope in convs:
-            if self._igemm_ok(conv, h.numel(), self._out_rows(conv, h.shape)):   # K28 (bias + activation fused)
-                # r06: the last block's output (the fc layer's flat input) with slack after it where the split weight
-                # gradient will read it as 128-row tiles (_fc0_wgrad_split)
-                slack = 0
-                if conv is last and self.tail == "flatten" and self._fc_wsplit_rows(B):
-                    oh = (h.shape[1] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
-                    ow = (h.shape[2] + 2 * conv.padding[0] - conv.kernel_size[0]) // conv.stride[0] + 1
-                    width = oh * ow * conv.out_channels
-                    slack = (width + 127) // 128 * 128 - width   # 0 for AC_CNN_Atari's 10 x 10 x 64 = 6400
-                y = self._conv_fwd(conv, code, slope, h, slack=slack)
-            else:
-                _library_conv_guard(conv)
+        plan = self.last_plan = self.plan(xu)
+        h = self.frames(xu) if plan.frames == "forward" else xu
+        hs = [h]
+        last = len(self.convs) - 1
+        for i, (conv, code, slope) in enumerate(self.convs):
+            fwd = plan.convs[i].fwd
+            if fwd == "K25" and i == 0:
+                y = self._conv1_u8(h)
+            elif fwd == "K28":   # bias + activation fused; the last block's output (the fc layer's flat input) with
+                # the plan's slack after it, where the padded K41V reads it as 128-row tiles
+                y = self._conv_fwd(conv, code, slope, h, slack=plan.slack if i == last else 0)
+            elif fwd == "miopen":
                 z = F.conv2d(h.permute(0, 3, 1, 2), conv.weight, None, conv.stride, conv.padding)
                 y = z.permute(0, 2, 3, 1)
                 if not y.is_contiguous():
                     y = y.contiguous()
                 _bias_act(code, y.view(-1, y.shape[3]), conv.bias, slope)
+            else:
+                _no_form("conv block %d's forward" % i, fwd)
             hs.append(y)
             h = y
         if self.tail == "maxpool":
@@ -412,58 +438,24 @@ class _Trunk:
             am = torch.empty((B, Cl), dtype=torch.int32, device=x.device)
             _lib.call(ops.lib().xpa_global_maxpool, ops._p(h), B, h.shape[1] * h.shape[2], Cl, ops._p(s), ops._p(am),
                       ops._stream(x.device))
-            return s, (hs, am, None, [])
+            return s, _Ctx(hs, am, None, [], plan)
         flat = h.reshape(B, -1)                  # (H, W, C) order: no copy
         fouts = []
         s = flat
         for j, (lin, code, slope) in enumerate(self.fc):
-            if j == 0 and self._fc_split_ok(B) and flat.is_contiguous():
+            if j == 0 and plan.fc0_fwd == "K40G":
+                if not flat.is_contiguous():
+                    _no_form("the first fc layer on a strided input", "K40G")
                 s = self._fc0_forward_split(flat, lin, code, slope)
+            elif j == 0 and plan.fc0_fwd != "linear":
+                _no_form("the first fc layer's forward", plan.fc0_fwd)
             else:
                 w = self._fc0_weight() if j == 0 else lin.weight
                 s = F.linear(s, w, lin.bias)
                 if code:
                     _bias_act(code, s, None, slope)
             fouts.append(s)
-        return s, (hs, None, flat, fouts)
-
-    use_igemm = True   # K28 / K29 for the convs they take (False: MIOpen for every conv, the r02 path)
-    # K28 / K29 hold one weight image per CU and tile the output rows 32 at a time per wave, so below ~1 M output rows
-    # a launch has too few tiles per CU to balance (C5's batch 2048 = 800 rows per CU = 25 tiles over 16 waves) and
-    # MIOpen's kernels measure faster there (tools/c5_ab.py: 2.26 vs 2.65 ms per C5 learner step; C3's rollout
-    # forwards at 1024 frames 71 vs 84-94 us).  Small-channel convs (< 16 in or out: the test nets, r02's fault
-    # suspect) always take K28 / K29.
-    igemm_min_rows = 1 << 20
-
-    @staticmethod
-    def _igemm_shape_ok(conv):
-        """The shape part of K28 / K29's conditions (no size preference, no 2 GiB operand check)."""
-        k, st, pd = conv.kernel_size, conv.stride, conv.padding
-        return (k[0] == k[1] and st[0] == st[1] and pd[0] == pd[1] and conv.padding_mode == "zeros"
-                and conv.in_channels % 4 == 0 and conv.weight.is_contiguous()
-                and bool(ops.lib().xpa_conv_igemm_ok(conv.in_channels, conv.out_channels, k[0])))
-
-    @classmethod
-    def _igemm_dgrad_shape_ok(cls, conv):
-        k, st = conv.kernel_size, conv.stride
-        return (cls._igemm_shape_ok(conv) and st[0] <= 2 and conv.out_channels % 4 == 0
-                and bool(ops.lib().xpa_conv_igemm_ok(conv.out_channels, conv.in_channels, k[0])))
-
-    def _igemm_ok(self, conv, numel, rows=None):
-        """numel: the largest operand K28 / K29 load (32-bit buffer offsets: under 2 GiB); rows: the conv's output
-        pixels B x OH x OW (None: no size preference)."""
-        small_c = min(conv.in_channels, conv.out_channels) < 16
-        return (self.use_igemm and numel * 4 < 2 ** 31 and (rows is None or small_c or rows >= self.igemm_min_rows)
-                and self._igemm_shape_ok(conv))
-
-    def _igemm_dgrad_ok(self, conv, numel, rows=None):
-        return self._igemm_ok(conv, numel, rows) and self._igemm_dgrad_shape_ok(conv)
-
-    @staticmethod
-    def _out_rows(conv, shape):
-        B, H, W = shape[0], shape[1], shape[2]
-        k, st, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        return B * ((H + 2 * pd - k) // st + 1) * ((W + 2 * pd - k) // st + 1)
+        return s, _Ctx(hs, None, flat, fouts, plan)
 
     @staticmethod
     def _conv_fwd(conv, code, slope, h, slack=0):
@@ -471,7 +463,7 @@ class _Trunk:
         allocation after the output (readable, never written: the padded K41 reads them into output rows it drops)."""
         B, H, W, C = h.shape
         k, st, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        OH, OW = (H + 2 * pd - k) // st + 1, (W + 2 * pd - k) // st + 1
+        OH, OW = _out_hw(conv, H, W)
         h = h if h.is_contiguous() else h.contiguous()
         n = B * OH * OW * conv.out_channels
         y = torch.empty((n + slack,), dtype=torch.float32, device=h.device)[:n].view(B, OH, OW, conv.out_channels)
@@ -514,36 +506,30 @@ class _Trunk:
         _lib.call(L.xpa_colsum_finalize, ops._p(bpart), G, Cin, ops._p(bgrad), st)
         return dx
 
-    @staticmethod
-    def _k26_ok(conv, x0):
-        return x0.dtype == torch.uint8 and conv.weight.grad.is_contiguous() and conv.bias.grad.is_contiguous()
-
     def _conv1_wgrad(self, conv, g, xu, act=None):
         """K26 partials + the f64 column-sum finalize -> conv.weight.grad.  act None: g is d output after the
         activation backward (K22 / K24 ran); act = (code, slope, y): g is d loss / d y and K26 also forms the
         activation backward and the bias-gradient partials (-> conv.bias.grad)."""
+        if xu.dtype != torch.uint8 or not (conv.weight.grad.is_contiguous() and conv.bias.grad.is_contiguous()):
+            _no_form("the first conv's weight gradient without uint8 frames or contiguous gradients", "K26")
         L, st = ops.lib(), ops._stream(g.device)
         G = int(L.xpa_conv1_u8_wgrad_num_partials())
-        if getattr(self, "_wg_part", None) is None:
-            self._wg_part = torch.empty((G, 8192), dtype=torch.float32, device=g.device)
-            self._wb_part = torch.empty((G, 32), dtype=torch.float32, device=g.device)
+        wg_part = self.parts.buf(("k26w", G), (G, 8192), g.device)
+        wb_part = self.parts.buf(("k26b", G), (G, 32), g.device)
         g = g if g.is_contiguous() else g.contiguous()
         B, H, W, C = xu.shape
         code, slope, y = act if act is not None else (-1, 0.0, None)
         _lib.call(L.xpa_conv1_u8_wgrad_act, code, ops._p(g), ops._p(y) if y is not None else None, float(slope),
-                  ops._p(xu), B, H, W, C, 8, conv.stride[0], conv.padding[0], 32, ops._p(self._wg_part),
-                  ops._p(self._wb_part) if y is not None else None, st)
-        _lib.call(L.xpa_colsum_finalize, ops._p(self._wg_part), G, 8192, ops._p(conv.weight.grad), st)
+                  ops._p(xu), B, H, W, C, 8, conv.stride[0], conv.padding[0], 32, ops._p(wg_part),
+                  ops._p(wb_part) if y is not None else None, st)
+        _lib.call(L.xpa_colsum_finalize, ops._p(wg_part), G, 8192, ops._p(conv.weight.grad), st)
         if y is not None:
-            _lib.call(L.xpa_colsum_finalize, ops._p(self._wb_part), G, 32, ops._p(conv.bias.grad), st)
+            _lib.call(L.xpa_colsum_finalize, ops._p(wb_part), G, 32, ops._p(conv.bias.grad), st)
 
     @staticmethod
     def _dgrad_ok(conv):
-        """K27 takes the data gradient of 2s x 2s, stride-s (1, 2) convs with 32 -> 64 channels."""
-        k, st, pd = conv.kernel_size, conv.stride, conv.padding
-        return (conv.in_channels == 32 and conv.out_channels == 64 and k[0] == k[1] and st[0] == st[1]
-                and pd[0] == pd[1] and st[0] in (1, 2) and k[0] == 2 * st[0] and pd[0] < k[0]
-                and conv.padding_mode == "zeros" and conv.weight.is_contiguous())
+        """K27 takes conv's data gradient (ConvFacts.k27: the shape rule alone, what the planner reads)."""
+        return _conv_facts(conv, 0).k27
 
     @staticmethod
     def _dgrad(conv, g, in_shape):
@@ -557,93 +543,98 @@ class _Trunk:
     @torch.no_grad()
     def backward(self, ctx, ds):
         """ds: d loss / d state [B, d]; writes every trunk parameter's gradient."""
-        hs, am, flat, fouts = ctx
-        B = hs[0].shape[0]
-        parts = self.parts
+        hs, am, flat, fouts, plan = ctx
         g = ds
-        fused_dz = False   # g leaves the fc part as the last conv block's dz (its K22 done in the fc epilogue)
-        if self.tail == "flatten":
-            for j in range(len(self.fc) - 1, -1, -1):
-                lin, code, slope = self.fc[j]
-                x_in = flat if j == 0 else fouts[j - 1]
-                g = g.contiguous()
-                _act_bwd_bias(parts, code, g, fouts[j], slope, lin.bias.grad)
-                if j == 0:
-                    if self._dw_tmp is None:
-                        self._dw_tmp = torch.empty_like(lin.weight)
-                    if not self._fc0_wgrad_split(g, x_in):
-                        torch.mm(g.t(), x_in, out=self._dw_tmp)
-                    Cl, Hl, Wl = self._chw
-                    lin.weight.grad.view(lin.out_features, Cl, Hl, Wl).copy_(
-                        self._dw_tmp.view(lin.out_features, Hl, Wl, Cl).permute(0, 3, 1, 2))
-                    if self._fc_fuse_ok(g.shape[0]) and flat.is_contiguous():
-                        g = self._fc0_dgrad_split_act(g, flat)
-                        fused_dz = True
-                    elif self._fc_split_ok(g.shape[0]):
-                        g = self._fc0_dgrad_split(g)
-                    else:
-                        g = torch.mm(g, self._fc0_weight())
-                else:
-                    torch.mm(g.t(), x_in, out=lin.weight.grad)
-                    g = torch.mm(g, lin.weight)
-        # conv blocks, last to first.  g is the NHWC gradient of the block's output (after its activation), or — once
-        # a fused step has applied the activation backward (K24 for the max-pool tail, K28's data gradient epilogue) —
-        # its pre-activation gradient dz (g_dz), with that block's bias gradient already written.
-        g_dz = fused_dz
+        for j in range(len(self.fc) - 1, -1, -1):
+            lin, code, slope = self.fc[j]
+            g = g.contiguous()
+            _act_bwd_bias(self.parts, code, g, fouts[j], slope, lin.bias.grad)
+            if j > 0:
+                torch.mm(g.t(), fouts[j - 1], out=lin.weight.grad)
+                g = torch.mm(g, lin.weight)
+            else:
+                g = self._fc0_backward(plan, g, flat)
+        # conv blocks, last to first.  g is the NHWC gradient of the block's output (after its activation), or — where
+        # act_bwd names a stage upstream of the block (K40G-act, K24, K28-dgrad) — its pre-activation gradient dz, with
+        # the block's bias gradient already written.
         for i in range(len(self.convs) - 1, -1, -1):
             conv, code, slope = self.convs[i]
+            act_bwd, wgrad, dgrad = plan.convs[i][1:]
             y = hs[i + 1]
             Cy = y.shape[3]
-            if i == len(self.convs) - 1 and self.tail == "maxpool":
-                HW = y.shape[1] * y.shape[2]
-                dz = torch.empty_like(y)
-                part = parts.get(B * HW, Cy, y.device, True)
-                L, st = ops.lib(), ops._stream(y.device)
-                if getattr(self, "err", None) is None:
-                    self.err = torch.zeros((1,), dtype=torch.int32, device=y.device)   # argmax outside [0, HW)
-                _lib.call(L.xpa_maxpool_act_bwd_bias, code, ops._p(ds.contiguous()), ops._p(am), ops._p(y), B, HW, Cy,
-                          float(slope), ops._p(dz), ops._p(part), ops._p(self.err), st)
-                _lib.call(L.xpa_colsum_finalize, ops._p(part), part.shape[0], Cy, ops._p(conv.bias.grad), st)
-                g, g_dz = dz, True
+            if act_bwd == "K24":
+                g = self._maxpool_backward(ds, am, y, i)
             else:
                 g = g.reshape(y.shape)
                 if not g.is_contiguous():
                     g = g.contiguous()
-            if i == 0 and self._k26_ok(conv, hs[0]):
-                # K26 from the uint8 frames: with the activation backward + bias gradient folded in unless done
-                self._conv1_wgrad(conv, g, hs[0], act=None if g_dz else (code, slope, y))
-                break
-            x_in = self.frames(hs[i]) if hs[i].dtype == torch.uint8 else hs[i]
-            numel = max(x_in.numel(), g.numel())
-            rows = y.shape[0] * y.shape[1] * y.shape[2]
-            ig = self._igemm_ok(conv, numel, rows)
-            need_in = i > 0
-            if not g_dz and (need_in or not ig):
-                # the data gradient (and the library weight gradient) read dz: K22 in place, + the bias gradient
-                _act_bwd_bias(parts, code, g.view(-1, Cy), y.view(-1, Cy), slope, conv.bias.grad)
-                g_dz = True
-            if ig:   # K29 (with the activation backward + bias gradient folded in when g is not dz yet)
-                self._conv_wgrad(conv, g, -1 if g_dz else code, slope, y, x_in)
-            if not ig or (need_in and not self._dgrad_ok(conv) and not self._igemm_dgrad_ok(conv, numel, rows)):
-                k27 = need_in and self._dgrad_ok(conv)
-                _library_conv_guard(conv)
+            x_in = self.frames(hs[0]) if i == 0 and plan.frames == "backward" else hs[i]
+            if act_bwd == "K22":   # the data gradient and the library weight gradient read dz: in place, + the bias
+                _act_bwd_bias(self.parts, code, g.view(-1, Cy), y.view(-1, Cy), slope, conv.bias.grad)
+            elif act_bwd not in ("K24", "K40G-act", "K28-dgrad") and act_bwd != wgrad:   # upstream, or K26 / K29's own
+                _no_form("conv block %d's activation backward" % i, act_bwd)
+            # the weight gradient, with the activation backward + bias gradient folded in where act_bwd names it
+            if wgrad == "K26":
+                self._conv1_wgrad(conv, g, x_in, act=(code, slope, y) if act_bwd == "K26" else None)
+            elif wgrad == "K29":
+                self._conv_wgrad(conv, g, code if act_bwd == "K29" else -1, slope, y, x_in)
+            elif wgrad != "miopen":
+                _no_form("conv block %d's weight gradient" % i, wgrad)
+            if "miopen" in (wgrad, dgrad):
                 gx, gw, _ = torch.ops.aten.convolution_backward(
                     g.permute(0, 3, 1, 2), x_in.permute(0, 3, 1, 2), conv.weight, None, list(conv.stride),
-                    list(conv.padding), [1, 1], False, [0, 0], 1, [need_in and not k27, not ig, False])
-                if not ig:
+                    list(conv.padding), [1, 1], False, [0, 0], 1, [dgrad == "miopen", wgrad == "miopen", False])
+                if wgrad == "miopen":
                     conv.weight.grad.copy_(gw)
-                if need_in and not k27:
-                    g, g_dz = gx.permute(0, 2, 3, 1), False
-                    continue
-            if not need_in:
-                break
-            if self._dgrad_ok(conv):   # K27 (the stride-2 32 -> 64 conv): the previous block's g, not dz
-                g, g_dz = self._dgrad(conv, g, x_in.shape), False
-            else:                      # K28's data gradient with the previous block's activation backward + bias
+            if dgrad == "miopen":
+                g = gx.permute(0, 2, 3, 1)
+            elif dgrad == "K27":   # (the stride-2 32 -> 64 conv): the previous block's g, not dz
+                g = self._dgrad(conv, g, x_in.shape)
+            elif dgrad == "K28":   # with the previous block's activation backward + bias gradient
                 pconv, pcode, pslope = self.convs[i - 1]
                 g = self._conv_dgrad(conv, g, tuple(x_in.shape), (pcode, pslope, hs[i], pconv.bias.grad))
-                g_dz = True
+            elif dgrad != "none" or i > 0:
+                _no_form("conv block %d's data gradient" % i, dgrad)
         self.stale = True   # the optimizer step that follows changes the fc weight
+
+    def _fc0_backward(self, plan, g, flat):
+        """The first fc layer's weight gradient (permuted back into the reference's (C, H, W) column order) and its
+        data gradient, which plan.fc0_dx "K40G-act" returns as the last conv block's dz."""
+        lin = self.fc[0][0]
+        if self._dw_tmp is None:
+            self._dw_tmp = torch.empty_like(lin.weight)
+        if plan.fc0_dw in ("K41V", "K41V-padded"):
+            self._fc0_wgrad_split(g, flat)
+        elif plan.fc0_dw == "mm":
+            torch.mm(g.t(), flat, out=self._dw_tmp)
+        else:
+            _no_form("the first fc layer's weight gradient", plan.fc0_dw)
+        Cl, Hl, Wl = self._chw
+        lin.weight.grad.view(lin.out_features, Cl, Hl, Wl).copy_(
+            self._dw_tmp.view(lin.out_features, Hl, Wl, Cl).permute(0, 3, 1, 2))
+        if plan.fc0_dx == "K40G-act":
+            if not flat.is_contiguous():
+                _no_form("the first fc layer's data gradient on a strided input", "K40G-act")
+            return self._fc0_dgrad_split_act(g, flat)
+        if plan.fc0_dx == "K40G":
+            return self._fc0_dgrad_split(g)
+        if plan.fc0_dx != "mm":
+            _no_form("the first fc layer's data gradient", plan.fc0_dx)
+        return torch.mm(g, self._fc0_weight())
+
+    def _maxpool_backward(self, ds, am, y, i):
+        """K24: the last block's dz (the pooled gradient routed to the argmax, times act'(y)) and its bias gradient."""
+        conv, code, slope = self.convs[i]
+        B, HW, Cy = y.shape[0], y.shape[1] * y.shape[2], y.shape[3]
+        dz = torch.empty_like(y)
+        part = self.parts.get(B * HW, Cy, y.device, True)
+        L, st = ops.lib(), ops._stream(y.device)
+        if self.err is None:
+            self.err = torch.zeros((1,), dtype=torch.int32, device=y.device)   # argmax outside [0, HW)
+        _lib.call(L.xpa_maxpool_act_bwd_bias, code, ops._p(ds.contiguous()), ops._p(am), ops._p(y), B, HW, Cy,
+                  float(slope), ops._p(dz), ops._p(part), ops._p(self.err), st)
+        _lib.call(L.xpa_colsum_finalize, ops._p(part), part.shape[0], Cy, ops._p(conv.bias.grad), st)
+        return dz
 
 
 class FusedCNNActorCritic:
