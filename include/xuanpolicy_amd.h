@@ -40,7 +40,8 @@ typedef struct ihipStream_t *xpa_stream_t; /* == hipStream_t */
  * ~300 blocks counting on one int serialised their atomics).
  * Added since without a version change (new entry points only, no existing signature or struct touched): the
  * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch; K33's xpa_small_close and
- * xpa_small_close_batch (XpaSmallCloseArgs); the population evaluation xpa_small_eval_batch (XpaSmallEval). */
+ * xpa_small_close_batch (XpaSmallCloseArgs); the population evaluation xpa_small_eval_batch (XpaSmallEval); K29's shape
+ * predicate xpa_conv_wgrad_ok. */
 #define XPA_ABI_VERSION 4
 #define XPA_COLSUM_TICKET_INTS 4096
 
@@ -1199,7 +1200,8 @@ int xpa_maxpool_act_bwd_bias(int act, const float *dout, const int32_t *argmax, 
  * [out_c][in_c][kernel][kernel]; in_c a multiple of 4, <= 64; out_c <= 64; xpa_conv_igemm_ok(in_c, out_c, kernel)
  * tells whether the weight image fits the 160 KiB LDS (the forward and, with the channel counts swapped, the data
  * gradient).  act: 0 identity, 1 LeakyReLU(slope) / ReLU (slope 0), 2 tanh.
- * The operands must each be under 2 GiB (32-bit buffer offsets).
+ * Every operand and every output must be under 2 GiB (32-bit buffer byte offsets): xpa_conv_fwd checks x and y,
+ * xpa_conv_dgrad dy and dx, xpa_conv_wgrad x and g, each in bytes.
  * xpa_conv_fwd: y = act(conv(x, w) + bias) [batch, OH, OW, out_c] (bias nullable).
  * xpa_conv_dgrad: dx [batch, in_h, in_w, in_c] = the data gradient of the conv from dy [batch, out_h, out_w, out_c]
  *   (stride 1 or 2); with act_prev >= 0, dx = that * act'(y_prev) (the previous block's activation backward, act' from
@@ -1209,6 +1211,10 @@ int xpa_maxpool_act_bwd_bias(int act, const float *dout, const int32_t *argmax, 
  *   dW = sum over output pixels of dz x (xpa_colsum_finalize -> the weight gradient, weight layout); dz = g, or with
  *   act >= 0, g * act'(y) (y = the block's forward output) and then bias_partial [num_partials][out_c] too. */
 int xpa_conv_igemm_ok(int64_t in_channels, int64_t out_channels, int64_t kernel);
+/* K29's own shape rule, the one xpa_conv_wgrad checks: out_c <= 64 and the ceil(kernel^2 in_c / 16) column tiles in at
+ * most 4 waves of at most 9 tiles, i.e. kernel^2 in_c <= 576.  Host only.  A conv is on the K28 / K29 path when both
+ * predicates take it (Conv2d(32, 32, 5) passes the first alone). */
+int xpa_conv_wgrad_ok(int64_t in_channels, int64_t out_channels, int64_t kernel);
 int xpa_conv_fwd(int act, const float *x, int64_t batch, int64_t in_h, int64_t in_w, int64_t in_c, const float *w,
                  const float *bias, int64_t out_c, int64_t kernel, int64_t stride, int64_t pad, float slope, float *y,
                  xpa_stream_t stream);

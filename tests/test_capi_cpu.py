@@ -69,6 +69,29 @@ def test_invalid_arguments_rejected_before_launch(lib):
     assert trunk_actor(h_out=ctypes.c_void_p(260)) == 1
     assert lib.xpa_head_gemm_trunk_critic(1, 64, 256, P, 21, 21, P, P, 0.01, None, 256, P, P, 512, P, P, 0.01, P, 100,
                                           P, 0.25, P, P, P, P, P, 16, None) == 1
+    # K28 / K29: every operand AND every output under 2 GiB (32-bit buffer byte offsets), checked in bytes before any
+    # launch; the sizes sit just either side of the bound, and the same call just under it fails only on what is
+    # checked later (K29's tiling), never on the size
+    def conv_fwd(batch, hw, in_c=4, out_c=64, x=P):
+        return lib.xpa_conv_fwd(1, x, batch, hw, hw, in_c, P, P, out_c, 1, 1, 0, 0.0, P, None)
+    assert 8 * 1024 * 1024 * 64 * 4 == 1 << 31 and 8 * 1024 * 1024 * 4 * 4 < 1 << 31
+    assert conv_fwd(8, 1024) == 1                          # x 128 MiB, y exactly 2 GiB
+    assert conv_fwd(8, 1024, in_c=64, out_c=4) == 1        # the input bound, as before
+    assert conv_fwd(1, 4, x=ctypes.c_void_p(260)) == 1     # x's alignment
+
+    def conv_dgrad(batch, hw, in_c, out_c):
+        return lib.xpa_conv_dgrad(P, batch, hw, hw, out_c, P, in_c, 1, 1, 0, hw, hw, -1, None, 0.0, P, None, None)
+    assert conv_dgrad(8, 1024, 64, 4) == 1                 # dx exactly 2 GiB (2^29 elements), dy 128 MiB
+    assert conv_dgrad(8, 1024, 4, 64) == 1                 # dy exactly 2 GiB
+
+    def conv_wgrad(in_c, out_c, k, batch=1, hw=16):
+        return lib.xpa_conv_wgrad(-1, P, None, 0.0, P, batch, hw, hw, in_c, out_c, k, 1, 0, P, None, None)
+    assert conv_wgrad(32, 32, 5) == 1 and not lib.xpa_conv_wgrad_ok(32, 32, 5)     # 800 columns: 50 tiles
+    assert conv_wgrad(16, 16, 8) == 1 and not lib.xpa_conv_wgrad_ok(16, 16, 8)
+    assert conv_wgrad(64, 65, 3) == 1 and not lib.xpa_conv_wgrad_ok(64, 65, 3)
+    assert lib.xpa_conv_wgrad_ok(64, 64, 3) and lib.xpa_conv_wgrad_ok(36, 64, 4) and not lib.xpa_conv_wgrad_ok(40, 64, 4)
+    assert conv_wgrad(64, 4, 1, batch=8, hw=1024) == 1     # x exactly 2 GiB
+    assert conv_wgrad(4, 64, 1, batch=8, hw=1024) == 1     # g exactly 2 GiB
     # the gather-only K13 form needs the rows output when h is NULL
     assert lib.xpa_thin_linear_act_fwd_gather(1, P, 17, 100, P, 64, 17, 256, P, P, 0.01, None, 256, P, P, None,
                                               None) == 1

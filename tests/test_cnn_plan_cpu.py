@@ -5,6 +5,7 @@
     data-gradient column block is aligned to the row's end (overlapping its neighbour, never padded);
   * the named production plans (C3 at the update's and the rollout's batch, C5, the 8-channel test net, the padded
     K41V) and the plan's invariants over every switch;
+  * a conv whose output reaches 2 GiB while its input does not is not planned K28;
   * the grouped split GEMM entries refuse host tensors (no CPU path);
   * the conv forms' defaults: K25B / K26B / K27B on, K28B off."""
 import itertools
@@ -25,6 +26,11 @@ def _trunk(hw):
 
 def _basic(filters):
     rep = Basic_CNN((84, 84, 4), [8, 4], [4, 2], filters, None, None, torch.nn.ReLU, "cpu")
+    return fused_cnn._Trunk(rep, fused_cnn._Part())
+
+
+def _basic_ks(kernels, strides, filters):
+    rep = Basic_CNN((84, 84, 4), kernels, strides, filters, None, None, torch.nn.ReLU, "cpu")
     return fused_cnn._Trunk(rep, fused_cnn._Part())
 
 
@@ -131,6 +137,21 @@ def test_strided_conv0_gradients_move_the_frame_copy_into_the_backward():
     assert p.convs[0] == ConvForm("K25", "K29", "K29", "none") and p.frames == "backward"
     assert p.launches("backward")[-4:] == ["xpa_frames_to_f32", "xpa_conv_wgrad", "xpa_colsum_finalize",
                                            "xpa_colsum_finalize"]
+
+
+def test_conv_output_of_2_gib_is_not_planned_k28():
+    """K28 stores through a 32-bit buffer record as it loads through one: a stride-1 conv with more output than input
+    channels (32 -> 64, 21 x 21) whose output reaches 2 GiB while its input stays at half that is the library's in the
+    forward too.  Facts only: no tensor of that size exists."""
+    t = _basic_ks([8, 3], [4, 1], [32, 64])
+    c = t.conv_facts[1]
+    assert c.igemm and c.igemm_dgrad and (c.cin, c.cout, c.k, c.s, c.p) == (32, 64, 3, 1, 1)
+    for B, over in ((19000, False), (19021, False), (19022, True), (20000, True)):
+        x_bytes, y_bytes = B * 21 * 21 * 32 * 4, B * 21 * 21 * 64 * 4
+        assert x_bytes < 2 ** 31 and (y_bytes >= 2 ** 31) == over, B
+        form = _plan(t, B).convs[1]
+        assert form == (ConvForm("miopen", "K24", "miopen", "miopen") if over else
+                        ConvForm("K28", "K24", "K29", "K28")), (B, form)
 
 
 # ---- invariants over every switch ------------------------------------------------------------------------------------

@@ -26,18 +26,21 @@ class ConvFacts(NamedTuple):
     zeros: bool         # padding_mode "zeros"
     w_contig: bool      # the weight is contiguous
     act: int            # the activation code
-    igemm: bool         # K28 forward / K29 take the shape (xpa_conv_igemm_ok included)
+    igemm: bool         # K28 forward and K29 both take the shape (xpa_conv_igemm_ok and xpa_conv_wgrad_ok included)
     igemm_dgrad: bool   # K28's data gradient takes it
     k27: bool           # K27 takes the data gradient: 2s x 2s, stride s (1, 2), 32 -> 64 channels
 
 
-def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_ok=None):
-    """The ConvFacts of one Conv2d: the static shape rules of K27 / K28 / K29.  igemm_ok(in, out, k) is the library's
-    xpa_conv_igemm_ok, asked by the caller's hand (the planner never asks; None: not asked, no K28 / K29)."""
+def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_ok=None, wgrad_ok=None):
+    """The ConvFacts of one Conv2d: the static shape rules of K27 / K28 / K29.  igemm_ok(in, out, k) and
+    wgrad_ok(in, out, k) are the library's xpa_conv_igemm_ok (K28's weight image) and xpa_conv_wgrad_ok (K29's tiling),
+    asked by the caller's hand (the planner never asks; None: not asked, no K28 / K29).  A block is on the K28 / K29
+    path only when both take it: one that K29 cannot take plans the library route in all three directions."""
     k, s, p = kernel[0], stride[0], padding[0]
     square = kernel[0] == kernel[1] and stride[0] == stride[1] and padding[0] == padding[1]
     plain = square and zeros and w_contig
-    igemm = bool(plain and cin % 4 == 0 and igemm_ok is not None and igemm_ok(cin, cout, k))
+    igemm = bool(plain and cin % 4 == 0 and igemm_ok is not None and wgrad_ok is not None
+                 and igemm_ok(cin, cout, k) and wgrad_ok(cin, cout, k))
     dgrad = bool(igemm and s <= 2 and cout % 4 == 0 and igemm_ok(cout, cin, k))
     k27 = plain and cin == 32 and cout == 64 and s in (1, 2) and k == 2 * s and p < k
     return ConvFacts(cin, cout, k, s, p, square, zeros, w_contig, act, igemm, dgrad, k27)
@@ -149,15 +152,16 @@ def plan_cnn(f):
     numel = [f.B * h * w * ch for h, w, ch in shapes]
 
     def igemm(i, operand):
-        """K28 / K29 for block i: operand is the largest tensor they load (32-bit buffer offsets: under 2 GiB); the
-        row preference is waived for small-channel blocks, which MIOpen must not take."""
+        """K28 / K29 for block i: operand is the largest tensor they load or store (32-bit buffer offsets: under
+        2 GiB); the row preference is waived for small-channel blocks, which MIOpen must not take."""
         c = f.convs[i]
         rows = f.B * shapes[i + 1][0] * shapes[i + 1][1]
         return (f.use_igemm and operand * 4 < 2 ** 31 and (min(c.cin, c.cout) < 16 or rows >= f.igemm_min_rows)
                 and c.igemm)
 
-    # forward: the operand is the block's input
-    fwd = ["K25" if i == 0 and f.u8_conv1 and f.x_u8 else "K28" if igemm(i, numel[i]) else "miopen" for i in range(n)]
+    # forward: the operand is the larger of the block's input and its output (K28 stores through a buffer record too)
+    fwd = ["K25" if i == 0 and f.u8_conv1 and f.x_u8 else "K28" if igemm(i, max(numel[i], numel[i + 1])) else "miopen"
+           for i in range(n)]
     # the first fc layer
     fc0_fwd, fc0_dw, fc0_dx, slack, halves, fcs = None, "mm", "mm", 0, 0, ()
     if f.tail == "flatten":

@@ -894,10 +894,22 @@ int ig_dispatch(const IgArgs &args, int cinp, int nt, hipStream_t s) {
 
 // CINP = CIN rounded up to 8, 16, 32 or 64; NT = COUT rounded up to 32 / 32; the weight image must fit the LDS
 bool ig_shape(int64_t cin, int64_t cout, int64_t k, int &cinp, int &nt) {
-    if (cin < 1 || cin > 64 || cout < 1 || cout > 64 || k < 1 || cin % 4) return false;
+    if (cin < 1 || cin > 64 || cout < 1 || cout > 64 || k < 1 || k > 12 || cin % 4) return false;   // 12^2 x 8 x 32 fits
     cinp = cin <= 8 ? 8 : cin <= 16 ? 16 : cin <= 32 ? 32 : 64;
     nt = cout <= 32 ? 1 : 2;
     return k * k * cinp * 32 * nt <= kIgLdsFloats;
+}
+
+// K29's tiling: TN = ceil(COUT / 16) rounded to 1 / 2 / 4 row tiles (COUT <= 64); the ceil(K K CIN / 16) column tiles
+// over up to 4 waves of TC = ceil(tiles / 4) rounded to 2 / 4 / 8 / 9 each: at most 36 tiles, K K CIN <= 576
+bool wg_shape(int64_t cin, int64_t cout, int64_t k, int &tn, int &tc, int &waves) {
+    if (cin < 1 || cout < 1 || cout > 64 || k < 1 || k > 24 || cin > 576) return false;
+    tn = cout <= 16 ? 1 : cout <= 32 ? 2 : 4;
+    const int64_t nct = (k * k * cin + 15) / 16;
+    tc = (int)((nct + 3) / 4);
+    tc = tc <= 2 ? 2 : tc <= 4 ? 4 : tc <= 8 ? 8 : 9;
+    waves = (int)((nct + tc - 1) / tc);
+    return waves <= 4;
 }
 
 }  // namespace
@@ -905,6 +917,11 @@ bool ig_shape(int64_t cin, int64_t cout, int64_t k, int &cinp, int &nt) {
 XPA_API int xpa_conv_igemm_ok(int64_t in_channels, int64_t out_channels, int64_t kernel) {
     int cinp, nt;
     return ig_shape(in_channels, out_channels, kernel, cinp, nt) ? 1 : 0;
+}
+
+XPA_API int xpa_conv_wgrad_ok(int64_t in_channels, int64_t out_channels, int64_t kernel) {
+    int tn, tc, waves;
+    return wg_shape(in_channels, out_channels, kernel, tn, tc, waves) ? 1 : 0;
 }
 
 // r05: K28's arithmetic — bit 0: K28B (bf16 matrix cores, six split products; taken where the GEMM's input channels
@@ -923,7 +940,9 @@ XPA_API int xpa_conv_fwd(int act, const float *x, int64_t batch, int64_t in_h, i
         !ig_shape(in_c, out_c, kernel, cinp, nt) || ((uintptr_t)x % 16))
         return (int)hipErrorInvalidValue;
     const int64_t OH = (in_h + 2 * pad - kernel) / stride + 1, OW = (in_w + 2 * pad - kernel) / stride + 1;
-    if (OH < 1 || OW < 1 || batch * in_h * in_w * in_c * 4 >= ((int64_t)1 << 31) || batch * OH * OW >= ((int64_t)1 << 31))
+    // the input's and the output's buffer records and their 32-bit byte offsets: both under 2 GiB
+    if (OH < 1 || OW < 1 || batch * in_h * in_w * in_c * 4 >= ((int64_t)1 << 31) ||
+        batch * OH * OW * out_c * 4 >= ((int64_t)1 << 31))
         return (int)hipErrorInvalidValue;
     IgArgs a{};
     a.in = x; a.in_bytes = batch * in_h * in_w * in_c * 4; a.w = w; a.bias = bias; a.out = y;
@@ -951,7 +970,7 @@ XPA_API int xpa_conv_dgrad(const float *dy, int64_t batch, int64_t out_h, int64_
         !ig_shape(out_c, in_c, kernel, cinp, nt) || ((uintptr_t)dy % 16) ||
         out_h != (in_h + 2 * pad - kernel) / stride + 1 || out_w != (in_w + 2 * pad - kernel) / stride + 1 ||
         out_h < 1 || out_w < 1 || (act_prev >= 0 && !y_prev) ||
-        batch * in_h * in_w * in_c >= ((int64_t)1 << 31) || batch * out_h * out_w * out_c * 4 >= ((int64_t)1 << 31))
+        batch * in_h * in_w * in_c * 4 >= ((int64_t)1 << 31) || batch * out_h * out_w * out_c * 4 >= ((int64_t)1 << 31))
         return (int)hipErrorInvalidValue;
     IgArgs a{};
     a.in = dy; a.in_bytes = batch * out_h * out_w * out_c * 4; a.w = w;
@@ -974,18 +993,13 @@ XPA_API void xpa_conv_wgrad_force_stream(int on) { g_wgrad_stream_only = on != 0
 XPA_API int xpa_conv_wgrad(int act, const float *g, const float *y, float slope, const float *x, int64_t batch,
                            int64_t in_h, int64_t in_w, int64_t in_c, int64_t out_c, int64_t kernel, int64_t stride,
                            int64_t pad, float *partial, float *bias_partial, xpa_stream_t stream) {
-    if (batch <= 0 || in_h <= 0 || in_w <= 0 || in_c < 1 || out_c < 1 || out_c > 64 || kernel < 1 || stride < 1 ||
-        pad < 0 || act < -1 || act > 2 || !g || !x || !partial || (act >= 0 && !y))
+    int tn, tc, waves;
+    if (batch <= 0 || in_h <= 0 || in_w <= 0 || stride < 1 || pad < 0 || act < -1 || act > 2 || !g || !x || !partial ||
+        (act >= 0 && !y) || !wg_shape(in_c, out_c, kernel, tn, tc, waves))
         return (int)hipErrorInvalidValue;
     const int64_t OH = (in_h + 2 * pad - kernel) / stride + 1, OW = (in_w + 2 * pad - kernel) / stride + 1;
     const int64_t ncols = kernel * kernel * in_c;
-    const int tn = out_c <= 16 ? 1 : out_c <= 32 ? 2 : 4;
-    // 16-column tiles over 4 waves (more waves only past 4 x 9 tiles): TC = ceil(tiles / 4), rounded to 2 / 4 / 8 / 9
-    const int64_t nct = (ncols + 15) / 16;
-    int tc = (int)((nct + 3) / 4);
-    tc = tc <= 2 ? 2 : tc <= 4 ? 4 : tc <= 8 ? 8 : 9;
-    const int64_t waves = (nct + tc - 1) / tc;
-    if (OH < 1 || OW < 1 || waves > 4 || batch * in_h * in_w * in_c * 4 >= ((int64_t)1 << 31) ||
+    if (OH < 1 || OW < 1 || batch * in_h * in_w * in_c * 4 >= ((int64_t)1 << 31) ||
         batch * OH * OW * out_c * 4 >= ((int64_t)1 << 31))
         return (int)hipErrorInvalidValue;
     WgArgs a{};

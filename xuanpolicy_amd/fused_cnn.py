@@ -48,9 +48,9 @@ def _out_hw(conv, H, W):
     return out_hw(H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
 
 
-def _conv_facts(conv, code, igemm_ok=None):
+def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None):
     return conv_facts(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
-                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok)
+                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok, wgrad_ok)
 
 
 class _Ctx(NamedTuple):
@@ -207,9 +207,10 @@ class _Trunk:
         self.last_plan = None   # the plan of the latest forward
         self.parts = parts
         self.n_params = 2 * (len(self.convs) + len(self.fc))
-        # the static shape rules of K27 / K28 / K29, asked once (the library's xpa_conv_igemm_ok included)
-        igemm_ok = ops.lib().xpa_conv_igemm_ok
-        self.conv_facts = tuple(_conv_facts(conv, code, igemm_ok) for conv, code, _ in self.convs)
+        # the static shape rules of K27 / K28 / K29, asked once (the library's xpa_conv_igemm_ok and xpa_conv_wgrad_ok
+        # included)
+        igemm_ok, wgrad_ok = ops.lib().xpa_conv_igemm_ok, ops.lib().xpa_conv_wgrad_ok
+        self.conv_facts = tuple(_conv_facts(conv, code, igemm_ok, wgrad_ok) for conv, code, _ in self.convs)
         # K25: the first conv block straight from the uint8 frames (4 channels, 8 x 8 kernel, 32 outputs: the Nature
         # CNN's first layer); the f32 frame copy (K20) is then only made in the backward, for MIOpen's weight gradient
         c0 = self.conv_facts[0]
