@@ -41,7 +41,7 @@ typedef struct ihipStream_t *xpa_stream_t; /* == hipStream_t */
  * Added since without a version change (new entry points only, no existing signature or struct touched): the
  * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch; K33's xpa_small_close and
  * xpa_small_close_batch (XpaSmallCloseArgs); the population evaluation xpa_small_eval_batch (XpaSmallEval); K29's shape
- * predicate xpa_conv_wgrad_ok. */
+ * predicate xpa_conv_wgrad_ok; K40H's xpa_s3_head_critic_mask and its form switch xpa_head_critic_form. */
 #define XPA_ABI_VERSION 4
 #define XPA_COLSUM_TICKET_INTS 4096
 
@@ -883,6 +883,22 @@ int xpa_head_gemm_s3q_critic_mask(int act, int64_t batch, int64_t hidden, const 
                                   float vf_coef, float *dz, float *partial_dw, float *partial_db_hidden,
                                   float *partial_db_out, float *loss_partials, int64_t loss_width, xpa_stream_t stream,
                                   unsigned *mask, float *dv);
+/* K40H — xpa_head_gemm_s3q_critic_mask's arguments and outputs on the split GEMM's 256-row block (8 waves, each 32
+ * rows x all 256 columns) with the critic head as a register epilogue: the value, the value-loss terms, dv and the mask
+ * words (one wave ballot per row and 32-column block) without an h tile in LDS, Wh_c^T's planes streamed once per 256
+ * rows instead of once per 64.  Taken (xpa_head_critic_form 1, the default) where hidden == 256, act == 1 (LeakyReLU /
+ * ReLU), dz == NULL, x and the planes are 16-B aligned and batch <= 131072 (a partial row per block); every other
+ * call, and form 0, runs xpa_head_gemm_s3q_critic_mask and returns its result.  The partial arrays keep their shapes
+ * ([xpa_head_fused_num_partials(batch)] rows, every row written); sums are in a fixed order (two launches: the same
+ * bits), v / dv / the partials agree with K16Q's to f32 rounding of a different summation order.
+ * xpa_head_critic_form: form < 0 only reads, 0 = always K16Q, 1 = K40H where admitted; returns the previous form. */
+int xpa_s3_head_critic_mask(int act, int64_t batch, int64_t hidden, const float *x, int64_t ldx,
+                            const float *w_hidden_split, const float *b_hidden, int64_t ld_dz, const float *w,
+                            const float *b, float slope, const int64_t *idx, int64_t n_rows, const float *ret,
+                            float vf_coef, float *dz, float *partial_dw, float *partial_db_hidden,
+                            float *partial_db_out, float *loss_partials, int64_t loss_width, xpa_stream_t stream,
+                            unsigned *mask, float *dv);
+int xpa_head_critic_form(int form);
 int xpa_s3_split_batch_scaled(int n_mat, const float *const *b, const int64_t *k, const int64_t *sk, const int64_t *sn,
                               void *const *out, const float *const *rs_w, const float *rs_a, const int64_t *rs_from,
                               float *cs_out, float cs_slope, xpa_stream_t stream);

@@ -1424,6 +1424,186 @@ __global__ __launch_bounds__(512, 1) void s3_trunk_bwd_crit_kernel(
                                dz_out, ld_out);
 }
 
+// ---- K40H: the mask-writing critic head on K40's 256-row block ----------------------------------------------------
+// Under the factored critic (K41P / K42C) the critic head stores no dz: per row it owes v, the value-loss terms, dv =
+// d loss / d v and the 256 sign bits of its hidden activations, per block the column partials of dW_out / db_hidden,
+// db_out and two loss sums.  K16Q's 64-row tile (an h tile in LDS for the dz phases) is not needed for any of that,
+// and it streams all 384 KiB of Wh_c^T's planes per 64 rows.  Here K40's block (8 waves, wave w = rows 32 w .. + 31 x
+// all 256 columns, acc[8]) runs the hidden GEMM — the 3-stage ring + chunk<8, 0> of K42C's actor half, a quarter of
+// K16Q's plane stream — and every wave finishes its 32 rows in registers:
+//   a = leaky(acc + bh); word cb of a row's mask = the wave ballot of a > 0 (lanes 0-31: the row, lanes 32-63: the row
+//   + 4); v = the lane's 8 columns in column-block order (one fmaf chain), then the 32 lanes of its row half in K40V's
+//   butterfly, + b; the row's loss terms as HeadEpi<2>::loss; dW_out[c] += dv a, db_hidden[c] += (dv wc[c]) act'(a)
+//   over the lane's 16 rows in r order, then the two lane halves, then the 8 waves through LDS in wave order.
+// Every sum has a fixed order: two launches give the same bits.  ret[idx[r]] and the row's validity are read by thread
+// r (< 256) behind the first two chunks' DMAs and handed over through LDS once the ring is free.  Partial rows: block b
+// writes row b (gridDim.x <= G, checked by the entry) and zeros in rows b + gridDim.x, b + 2 gridDim.x .. < G.
+__device__ __forceinline__ float hc_row_loss(float v, float retv, bool ok, float vf_coef, float inv_b, float &sum0,
+                                             float &sum1, float &dbo) {
+#pragma clang fp contract(off)  // HeadEpi<2>::loss's roundings
+    const float diff = v - retv;
+    const float dvr = ok ? vf_coef * 2.0f * diff * inv_b : 0.f;
+    sum0 += ok ? diff * diff : 0.f;
+    sum1 += ok ? v : 0.f;
+    dbo += dvr;
+    return dvr;
+}
+
+__global__ __launch_bounds__(512, 1) void s3_head_critic_kernel(
+    const float *__restrict__ a, int64_t lda, const __bf16 *__restrict__ bs, int64_t M, const float *__restrict__ bh,
+    const float *__restrict__ wo, const float *__restrict__ bo, float slope, const int64_t *__restrict__ idx,
+    int64_t n_rows, const float *__restrict__ ret, float vf_coef, float *__restrict__ p_dw, float *__restrict__ p_dbh,
+    float *__restrict__ p_dbo, float *__restrict__ p_loss, int loss_width, int64_t G, unsigned *__restrict__ mask,
+    float *__restrict__ dv) {
+    using Gm = S3Geom<8>;
+    constexpr int kNch = kN / kKC;
+    __shared__ __attribute__((aligned(16))) char lds[3 * Gm::kStage];
+    const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_char_t *)lds);
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int64_t blk = blockIdx.x, r0 = blk * Gm::kRows;
+    f32x16 acc[8];
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[cb][r] = 0.f;
+    const float *ar[2];
+    {   // the lane's two A rows (rows past the batch re-read its last row; nothing of them is stored or summed)
+        const int rr = lane >> 2, p = lane & 3;
+        const int q = p ^ ((rr >> 2) & 3);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            int64_t row = r0 + wave * 32 + i * 16 + rr;
+            row = row < M ? row : M - 1;
+            ar[i] = a + row * lda + 4 * q;
+        }
+    }
+    issue_rows<8>(base, ar[0], ar[1], bs, 0, lane, wave);
+    issue_rows<8>(base + Gm::kStage, ar[0], ar[1], bs, 1, lane, wave);
+    float retv = 0.f, okf = 0.f;
+    if (t < Gm::kRows && r0 + t < M) {
+        const int64_t row = idx ? idx[r0 + t] : r0 + t;
+        if (row >= 0 && row < n_rows) {
+            retv = ret[row];
+            okf = 1.f;
+        }
+    }
+    asm volatile("" ::"v"(retv), "v"(okf));   // landed here: no load of this kernel's own flies under the counted vmcnt
+    // K42C's ring: measured against K40's ping-pong pp_loop here, 51.4 against 51.6 us at 65 536 rows
+#pragma unroll 1
+    for (int ch = 0; ch < kNch; ++ch) {
+        if (ch + 1 < kNch) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(Gm::kDma) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+        if (ch + 2 < kNch) issue_rows<8>(base + ((ch + 2) % 3) * Gm::kStage, ar[0], ar[1], bs, ch + 2, lane, wave);
+        chunk<8, 0>(lds + (ch % 3) * Gm::kStage, acc, lane, wave);
+    }
+    __syncthreads();   // every wave done with the ring: its LDS carries the row inputs and the cross-wave sums
+    float *s_ret = reinterpret_cast<float *>(lds);   // [256]
+    float *s_ok = s_ret + 256;                       // [256]
+    float *s_dw = s_ok + 256;                        // [8 waves][256]
+    float *s_dbh = s_dw + 8 * 256;                   // [8 waves][256]
+    float *s_sc = s_dbh + 8 * 256;                   // [8 waves][3]: sum (v - ret)^2, sum v, db_out
+    if (t < Gm::kRows) {
+        s_ret[t] = retv;
+        s_ok[t] = okf;
+    }
+    __syncthreads();
+    const int h = lane >> 5, col = lane & 31;
+    float bv[8], wv[8], dwc[8], dbc[8];
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) {
+        bv[cb] = bh[cb * 32 + col];
+        wv[cb] = wo[cb * 32 + col];
+        dwc[cb] = dbc[cb] = 0.f;
+    }
+    const float b_out = bo[0], inv_b = 1.0f / (float)M;
+    float sum0 = 0.f, sum1 = 0.f, dbo = 0.f;
+#pragma unroll   // acc[cb][r] with a run-time index would put the accumulators in scratch
+    for (int r = 0; r < 16; ++r) {
+        const int rl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int64_t row = r0 + rl;
+        float p = 0.f;
+        unsigned mw = 0u;
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) {
+            const float z = acc[cb][r] + bv[cb];
+            const float av = z > 0.f ? z : z * slope;
+            acc[cb][r] = av;
+            // K16Q's bit: the activation is positive (= z > 0 for a slope >= 0)
+            const unsigned long long bl = __ballot(av > 0.f);
+            const unsigned wbits = h ? (unsigned)(bl >> 32) : (unsigned)bl;
+            mw = col == cb ? wbits : mw;
+            p = fmaf(av, wv[cb], p);
+        }
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+        const float dvr = hc_row_loss(p + b_out, s_ret[rl], s_ok[rl] != 0.f, vf_coef, inv_b, sum0, sum1, dbo);
+        if (row < M) {
+            if (col < 8) mask[row * 8 + col] = mw;
+            if (col == 8) dv[row] = dvr;
+        }
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) {
+            const float av = acc[cb][r];
+            dwc[cb] = fmaf(dvr, av, dwc[cb]);
+            dbc[cb] += (dvr * wv[cb]) * (av > 0.f ? 1.f : slope);
+        }
+        // a row at a time: the rows' compare masks (SGPR pairs) are not interleaved across rows (some still spill to
+        // VGPR lanes here, none in the k loop; no scratch)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) {
+        dwc[cb] += __shfl_xor(dwc[cb], 32, 64);
+        dbc[cb] += __shfl_xor(dbc[cb], 32, 64);
+        if (h == 0) {
+            s_dw[wave * 256 + cb * 32 + col] = dwc[cb];
+            s_dbh[wave * 256 + cb * 32 + col] = dbc[cb];
+        }
+    }
+    // every lane of a row half carries that half's row sums: lane 0 adds the other half's
+    sum0 += __shfl_xor(sum0, 32, 64);
+    sum1 += __shfl_xor(sum1, 32, 64);
+    dbo += __shfl_xor(dbo, 32, 64);
+    if (lane == 0) {
+        s_sc[wave * 3] = sum0;
+        s_sc[wave * 3 + 1] = sum1;
+        s_sc[wave * 3 + 2] = dbo;
+    }
+    __syncthreads();
+    const int64_t nblk = gridDim.x;
+    if (t < 256) {
+        float sw = s_dw[t], sb = s_dbh[t];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) {
+            sw += s_dw[w * 256 + t];
+            sb += s_dbh[w * 256 + t];
+        }
+        p_dw[blk * 256 + t] = sw;
+        p_dbh[blk * 256 + t] = sb;
+        for (int64_t zb = blk + nblk; zb < G; zb += nblk) {
+            p_dw[zb * 256 + t] = 0.f;
+            p_dbh[zb * 256 + t] = 0.f;
+        }
+    } else if (t == 256) {
+        float s0 = s_sc[0], s1 = s_sc[1], s2 = s_sc[2];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) {
+            s0 += s_sc[w * 3];
+            s1 += s_sc[w * 3 + 1];
+            s2 += s_sc[w * 3 + 2];
+        }
+        p_loss[blk * loss_width + 1] = s0;
+        p_loss[blk * loss_width + 4] = s1;
+        p_dbo[blk] = s2;
+        for (int64_t zb = blk + nblk; zb < G; zb += nblk) {
+            p_loss[zb * loss_width + 1] = 0.f;
+            p_loss[zb * loss_width + 4] = 0.f;
+            p_dbo[zb] = 0.f;
+        }
+    }
+}
+
 // ---- K41: weight gradients dW = A^T B over the batch (K = rows), split-K -----------------------------------
 // out[s] [M, 256] = A[rows of slice s]^T . B[rows of slice s], A [rows, M] (dz), B [rows, 256] (the layer input);
 // the slices are summed by the caller (the learner's fixed-order f64 column-sum finalize), as the batched f32 GEMM
@@ -2612,6 +2792,44 @@ XPA_API int xpa_s3_gemm_value(const float *a, int64_t lda, const void *b_split, 
     if (act == 0) s3_gemm_value_kernel<2, 4><<<grid, block, 0, s>>>(a, lda, bs, v, m, nch, bias, slope, w_out, b_out);
     else if (act == 1) s3_gemm_value_kernel<2, 5><<<grid, block, 0, s>>>(a, lda, bs, v, m, nch, bias, slope, w_out, b_out);
     else s3_gemm_value_kernel<2, 6><<<grid, block, 0, s>>>(a, lda, bs, v, m, nch, bias, slope, w_out, b_out);
+    return xpa_launch_status();
+}
+
+// K40H: xpa_head_gemm_s3q_critic_mask's arguments and outputs (the "K16Q-mask" critic of ops.HEAD_FORMS).  Form 1 (the
+// default) runs K40H where it is admitted — LeakyReLU / ReLU hidden layer of 256, no dz, 16-B aligned x and planes, and
+// a partial row for every 256-row block (batch <= 131 072: G = xpa_head_fused_num_partials stops at 512) — and the
+// K16Q kernel everywhere else; form 0 always runs K16Q.  The K16Q path returns xpa_head_gemm_s3q_critic_mask's result.
+namespace {
+int g_head_critic_form = 1;
+}
+XPA_API int xpa_head_critic_form(int form) {
+    const int prev = g_head_critic_form;
+    if (form >= 0) g_head_critic_form = form != 0 ? 1 : 0;
+    return prev;
+}
+
+XPA_API int xpa_s3_head_critic_mask(int act, int64_t batch, int64_t hidden, const float *x, int64_t ldx,
+                                    const float *w_hidden_split, const float *b_hidden, int64_t ld_dz, const float *w,
+                                    const float *b, float slope, const int64_t *idx, int64_t n_rows, const float *ret,
+                                    float vf_coef, float *dz, float *partial_dw, float *partial_db_hidden,
+                                    float *partial_db_out, float *loss_partials, int64_t loss_width, xpa_stream_t stream,
+                                    unsigned *mask, float *dv) {
+    const int64_t nblk = batch > 0 ? (batch + 255) / 256 : 0;
+    const bool args_ok = batch > 0 && x && w_hidden_split && b_hidden && w && b && ret && partial_dw &&
+                         partial_db_hidden && partial_db_out && loss_partials && loss_width >= 5 &&
+                         loss_width <= 0x7fffffff && n_rows > 0 && (idx || n_rows >= batch) && ldx >= kN &&
+                         (ldx & 3) == 0 && ld_dz >= kN;
+    const bool k40h = g_head_critic_form == 1 && args_ok && hidden == kN && act == 1 && !dz && mask && dv &&
+                      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_hidden_split)) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(mask) & 3) == 0 && nblk <= xpa_head_fused_num_partials(batch);
+    if (!k40h)
+        return xpa_head_gemm_s3q_critic_mask(act, batch, hidden, x, ldx, w_hidden_split, b_hidden, ld_dz, w, b, slope,
+                                             idx, n_rows, ret, vf_coef, dz, partial_dw, partial_db_hidden,
+                                             partial_db_out, loss_partials, loss_width, stream, mask, dv);
+    s3_head_critic_kernel<<<dim3((unsigned)nblk), dim3(512), 0, (hipStream_t)stream>>>(
+        x, ldx, reinterpret_cast<const __bf16 *>(w_hidden_split), batch, b_hidden, w, b, slope, idx, n_rows, ret, vf_coef,
+        partial_dw, partial_db_hidden, partial_db_out, loss_partials, (int)loss_width,
+        xpa_head_fused_num_partials(batch), mask, dv);
     return xpa_launch_status();
 }
 

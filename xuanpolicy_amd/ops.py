@@ -1013,7 +1013,8 @@ HEAD_FORMS = {
     "K16S": ("xpa_head_gemm_s3_actor", "xpa_head_gemm_s3_critic"),
     "K16P": ("xpa_head_gemm_s3p_actor", "xpa_head_gemm_s3p_critic"),
     "K16Q": ("xpa_head_gemm_s3q_actor", "xpa_head_gemm_s3q_critic"),
-    "K16Q-mask": ("xpa_head_gemm_s3q_actor", "xpa_head_gemm_s3q_critic_mask"),
+    # the mask-writing critic in its production form: K40H where admitted (xpa_head_critic_form), else the K16Q kernel
+    "K16Q-mask": ("xpa_head_gemm_s3q_actor", "xpa_s3_head_critic_mask"),
     "K16W": ("xpa_head_gemm_ws_actor", "xpa_head_gemm_ws_critic"),
     "K16S+W": ("xpa_head_gemm_s3_actor", "xpa_head_gemm_ws_critic"),
     "K16+W": ("xpa_head_gemm_actor", "xpa_head_gemm_ws_critic"),
