@@ -41,7 +41,8 @@ typedef struct ihipStream_t *xpa_stream_t; /* == hipStream_t */
  * Added since without a version change (new entry points only, no existing signature or struct touched): the
  * population forms xpa_small_rollout_batch, xpa_small_mlp_update_batch, xpa_random_permutation_batch; K33's xpa_small_close and
  * xpa_small_close_batch (XpaSmallCloseArgs); the population evaluation xpa_small_eval_batch (XpaSmallEval); K29's shape
- * predicate xpa_conv_wgrad_ok; K40H's xpa_s3_head_critic_mask and its form switch xpa_head_critic_form. */
+ * predicate xpa_conv_wgrad_ok; K40H's xpa_s3_head_critic_mask and its form switch xpa_head_critic_form; the 128-wide
+ * evaluation xpa_small_eval_wide / xpa_small_eval_wide_batch and the batched test-env reset xpa_small_env_reset_batch. */
 #define XPA_ABI_VERSION 4
 #define XPA_COLSUM_TICKET_INTS 4096
 
@@ -303,7 +304,8 @@ int xpa_mountaincar_step(int64_t n_envs, const float *act_in, int64_t ld_act, do
  * use_obsnorm = 0: the statistics are read, not updated (the agent's use_obsnorm False).
  * K32W — the same entry points at h0 == h1 == h2 == 128 (no other width beside K32's): the forward keeps one
  * representation row per thread and four 16-unit tiles of hidden weight rows per wave, and forms h0 of a 16-env tile
- * once into LDS; every other stage is K32's code.  The evaluation form (xpa_small_eval_*) takes K32's widths only. */
+ * once into LDS; every other stage is K32's code.  The evaluation form (xpa_small_eval_*) takes K32's widths only;
+ * K32W's has entry points of its own (xpa_small_eval_wide, xpa_small_eval_wide_batch). */
 typedef struct XpaSmallRolloutArgs {
     int n_envs, horizon, steps, d_in, h0, h1, h2, k, act_code, use_obsnorm, n_slots, mask_returns, use_rewnorm;
     int max_episode_steps;
@@ -463,6 +465,32 @@ int xpa_small_eval_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *h
                          const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
                          const XpaSmallRolloutHead *dev_heads, const XpaSmallEval *host_evals,
                          const XpaSmallEval *dev_evals, xpa_stream_t stream);
+/* K32WE — K32E at K32W's widths (h0 == h1 == h2 == 128): the same body with the evaluation switch and K32W's forward
+ * together, so a step is bit for bit the step xpa_small_rollout_<env> takes on the same block and the log, the stop
+ * rule and the writes at the end are K32E's.  env: XPA_ENV_*; head: NULL exactly for the Categorical envs (else its
+ * logstd non-NULL and act_clip > 0); log, capacity, snap_dim, scratch as xpa_small_eval_<env> takes them.  Every check
+ * is K32E's with the width condition replaced by all-128 (the K32 widths are refused here as 128 is refused there)
+ * and runs before any HIP call.  LDS: xpa_small_rollout_lds_floats(...) <= 16384, as in K32W's training form. */
+int xpa_small_eval_wide(int env, const XpaSmallRolloutArgs *args, const XpaSmallRolloutHead *head, int32_t *log,
+                        int64_t capacity, int64_t snap_dim, float *scratch, xpa_stream_t stream);
+/* K32WEB — K32WE for a population: xpa_small_eval_batch's arguments, host checks and per-workgroup overrides, with the
+ * width condition replaced by all-128; agent p's tensors end bit for bit as xpa_small_eval_wide(env, &host_blocks[p],
+ * ...) leaves them. */
+int xpa_small_eval_wide_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                              const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
+                              const XpaSmallRolloutHead *dev_heads, const XpaSmallEval *host_evals,
+                              const XpaSmallEval *dev_evals, xpa_stream_t stream);
+/* The device half of P env sets' reset() in ONE launch, over the blocks an evaluation launch takes (workgroup p = agent
+ * p, thread n = env n, looping past 256): env_state becomes the episode-0 reset state of (env_seed, n) from the env
+ * body's own reset arithmetic, env_obs (row stride ld_obs) the observation formed from it (MountainCar: the reset frame
+ * four times); ep_step, ep_index, ep_score, ep_last_score, ep_last_len, env_rew, env_term and env_trunc become 0, and —
+ * for every env but CartPole, whose reset() leaves it — the k columns of act_in (row stride ld_act).  final_obs and
+ * everything else of a block is neither read nor written: what the env class's reset() touches, and no more (its
+ * `resets` counter is the host's).  Every check runs on host_blocks before any HIP call: 1 <= n_agents <= 2^31 - 1, a
+ * valid env code, every block's n_envs in 1 .. 256 and equal to block 0's, d_in / k the env's, ld_obs >= d_in,
+ * ld_act >= k, none of the pointers named above NULL, no two blocks sharing env_state.  Plain vector stores only. */
+int xpa_small_env_reset_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                              const XpaSmallRolloutArgs *dev_blocks, xpa_stream_t stream);
 /* The generic tier's log writer, one launch per env step after the env's step kernel (one workgroup over all envs, so
  * a step's entries land in env order): appends the envs with term || trunc (atari_lifeloss = 1: not those that did
  * not truncate), steps_run += 1, cursor->step += 1 (ptr stays 0).  At the step where count first reaches target it

@@ -38,7 +38,8 @@ from .buffer import DummyOnPolicyBuffer, DummyOnPolicyBuffer_Atari
 from .fused_mlp import FusedActorCritic, Rows, _no_form
 from .learners import A2C_Learner, PerDQN_Learner, PPOCLIP_Learner
 from .policies import policy_discrete, policy_heads, space_shape
-from .rollout_plan import K32_DRIVERS, EvalFacts, RolloutFacts, eval_entry, plan_rollout, plan_test
+from .rollout_plan import (EVAL_TIERS, K32_DRIVERS, SMALL_ENVS, EvalFacts, RolloutFacts, eval_entry, plan_rollout,
+                           plan_test)
 
 FLOAT_MAX = 3.0e38
 # test_device's action stream: the counter hash keyed by seed ^ EVAL_SALT and a step counter of its own
@@ -972,7 +973,8 @@ class _OnPolicyAgent:
         return EvalFacts(cuda=self.device.type == "cuda", env=getattr(test_envs, "kind", "device") if device else "host",
                          dist=self.dist, small=small, n_envs=n, obs_dim=self.obs_dim, raw_obs=self.raw_obs,
                          world=self.world, sync_obs_rms=True if self.sync_obs_rms else
-                         "rollout" if self.sync_obs_rms_rollout else False)
+                         "rollout" if self.sync_obs_rms_rollout else False,
+                         wide_eval=bool(_cfg(self.config, "device_test_wide", False)))
 
     def _eval_stream(self, rng):
         """(seed, cursor) of the evaluation's action stream: seed ^ EVAL_SALT and a step counter of its own that
@@ -1017,7 +1019,8 @@ class _OnPolicyAgent:
                       cursor, stats=stats)
 
     def plan_test(self, test_envs):
-        """The tier test_device would evaluate these envs on: "K32E" | "steps" | "host" (rollout_plan.plan_test)."""
+        """The tier test_device would evaluate these envs on: "K32E" | "K32WE" | "steps" | "host"
+        (rollout_plan.plan_test)."""
         return plan_test(self._eval_facts(test_envs))
 
     def test_device(self, test_envs, test_episode, chunk=None, rng=None):
@@ -1027,6 +1030,7 @@ class _OnPolicyAgent:
         Actions come from the counter-hash sampler on the evaluation's own stream (_eval_stream).
           tier "K32E"   xpa_small_eval_*: `chunk` steps per launch (default 128, a training K32 launch), the log's
                         header read after each launch; the kernel stops at the completing step itself
+          tier "K32WE"  xpa_small_eval_wide: K32E at 128-wide layers (config.device_test_wide), run the same way
           tier "steps"  _eval_step, `chunk` steps (default 8) between header reads; steps past the completing one
                         still update obs_rms, which is then restored from the log's snapshot.  The eager step is
                         bound by the host's launch rate (~250 us at C2's nets), so a read every 8 steps waits for
@@ -1048,14 +1052,18 @@ class _OnPolicyAgent:
         capacity = target + N
         log = ops.eval_log_new(target, N, snap_dim, dev)
         bound = (target // N + 2) * max_ep
-        if tier == "K32E":
+        if tier in EVAL_TIERS:
             chunk = 128 if chunk is None else int(chunk)
             args, logstd = self._build_small_eval(env, seed, cursor)
             args.steps, entry = chunk, eval_entry(f)
             scratch = torch.empty((3 * N,), dtype=torch.float32, device=dev)
+            code = SMALL_ENVS[f.env, f.dist].code
 
             def step():
-                small_path.small_eval(entry, args, log, capacity, snap_dim, scratch, logstd, act_clip)
+                if tier == "K32WE":
+                    small_path.small_eval_wide(code, args, log, capacity, snap_dim, scratch, logstd, act_clip)
+                else:
+                    small_path.small_eval(entry, args, log, capacity, snap_dim, scratch, logstd, act_clip)
         else:
             chunk = 8 if chunk is None else int(chunk)
             A = env.act_in.shape[1]

@@ -1680,6 +1680,81 @@ __global__ __launch_bounds__(kRoThreads) void small_eval_batch_kernel(
     small_rollout_body<E, ACT, H0, true>(a, hd, RoEval{e.log, e.capacity, eval_log_entries(e.snap_dim)});
 }
 
+// The device half of the env classes' reset() for P env sets in one launch (xpa_small_env_reset_batch): workgroup p
+// is agent p, thread n env n.  ro_reset0: env n's episode-0 state from the env body's own reset draw (what its step
+// draws after a done, at episode 0) and the observation the class forms from it.
+// CartPole's draw is restated: cartpole::reset_dim carries no contraction pragma and compiles to one v_fma_f64, while
+// reset() forms u * 0.1 - 0.05 in numpy, the product and the difference each rounded — the f64 state this must equal.
+__device__ __forceinline__ void ro_reset0(const XpaCartPoleEnv &e, int n) {
+#pragma clang fp contract(off)
+    double *st = e.state + 4 * n;
+    float *o = e.obs + n * e.ld_obs;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const double u = (double)xpa_u01(xpa_hash4(e.seed ^ cartpole::kSaltCartPole, (uint32_t)n, 0u, (uint32_t)d));
+        const double v = u * 0.1 - 0.05;
+        st[d] = v;
+        o[d] = (float)v;
+    }
+}
+__device__ __forceinline__ void ro_reset0(const XpaPendulumEnv &e, int n) {
+    const double th = pendulum::reset_dim(e.seed, (uint32_t)n, 0u, 0u);
+    const double thdot = pendulum::reset_dim(e.seed, (uint32_t)n, 0u, 1u);
+    double *st = e.state + 2 * n;
+    float *o = e.obs + n * e.ld_obs;
+    st[0] = th;
+    st[1] = thdot;
+    o[0] = (float)cos(th);
+    o[1] = (float)sin(th);
+    o[2] = (float)thdot;
+}
+__device__ __forceinline__ void ro_reset0(const XpaAcrobotEnv &e, int n) {
+    double s[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) s[d] = acrobot::reset_dim(e.seed, (uint32_t)n, 0u, (uint32_t)d);
+    double *st = e.state + 4 * n;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) st[d] = s[d];
+    float f[6];
+    acrobot::obs_of(s[0], s[1], s[2], s[3], f);
+    float *o = e.obs + n * e.ld_obs;
+#pragma unroll
+    for (int d = 0; d < 6; ++d) o[d] = f[d];
+}
+__device__ __forceinline__ void ro_reset0(const XpaMountainCarEnv &e, int n) {
+    const double pos = mountaincar::reset_pos(e.seed, (uint32_t)n, 0u);
+    double *st = e.state + 2 * n;
+    float *o = e.obs + n * e.ld_obs;
+    st[0] = pos;
+    st[1] = 0.0;
+#pragma unroll
+    for (int k = 0; k < mountaincar::kStack; ++k) {   // the reset frame four times
+        o[2 * k] = (float)pos;
+        o[2 * k + 1] = 0.f;
+    }
+}
+
+// ZERO_ACT: the class's reset() zeroes its action input (every env's but CartPole's)
+template <class E, bool ZERO_ACT>
+__global__ __launch_bounds__(kRoThreads) void small_env_reset_batch_kernel(
+    const XpaSmallRolloutArgs *__restrict__ blocks) {
+    const XpaSmallRolloutArgs a = blocks[blockIdx.x];
+    const typename E::Env env = E::env(a);
+    for (int n = threadIdx.x; n < a.n_envs; n += kRoThreads) {
+        ro_reset0(env, n);
+        env.ep_step[n] = 0;
+        env.ep_index[n] = 0u;
+        env.ep_score[n] = 0.f;
+        env.ep_last_score[n] = 0.f;
+        env.ep_last_len[n] = 0;
+        env.rew[n] = 0.f;
+        env.term[n] = 0;
+        env.trunc[n] = 0;
+        if constexpr (ZERO_ACT)
+            for (int j = 0; j < a.k; ++j) a.act_in[n * a.ld_act + j] = 0.f;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // K33 — the closing of a K32 / K32W rollout in one launch (one workgroup per agent): the critic over the deferred
 // bootstrap rows, bootstrap_fixup_kernel's writes and the advantage scan (xpa_gae_scan's recurrence on the dense
@@ -2687,15 +2762,17 @@ void ro_dispatch(int64_t h0, int act_code, F launch) {
 // K32E's checks and launch: only what the evaluation form dereferences is required (the training-only pointers of
 // XpaSmallRolloutArgs may be null); horizon 1 and the sampler's three stores into scratch [3 * n_envs]
 // The predicate is shared by the single-agent launch and the population's (one agent's block and its log / scratch).
+// wide: the widths admitted are K32W's (all 128: K32WE) and not K32's (each of 32, 64: K32E); nothing else differs.
 template <class E>
-bool ro_eval_args_ok(const XpaSmallRolloutArgs *a0, int k, const int32_t *log, int64_t capacity, int64_t snap_dim,
-                     const float *scratch) {
+bool ro_eval_args_ok_at(bool wide, const XpaSmallRolloutArgs *a0, int k, const int32_t *log, int64_t capacity,
+                        int64_t snap_dim, const float *scratch) {
     if (!a0 || !log || capacity <= 0 || capacity > 0x7fffffff || snap_dim < 0 || !scratch || ((uintptr_t)log % 16))
         return false;
     const XpaSmallRolloutArgs &a = *a0;
-    if (a.n_envs <= 0 || a.n_envs > 256 || a.steps <= 0 || a.d_in != E::D || (a.h0 != 32 && a.h0 != 64) ||
-        (a.h1 != 32 && a.h1 != 64) || (a.h2 != 32 && a.h2 != 64) || a.k != k || a.act_code < 0 || a.act_code > 2 ||
-        a.max_episode_steps <= 0 || a.ld_obs < E::D || a.ld_act < k)
+    const bool widths = wide ? a.h0 == kRoWide && a.h1 == kRoWide && a.h2 == kRoWide
+                             : (a.h0 == 32 || a.h0 == 64) && (a.h1 == 32 || a.h1 == 64) && (a.h2 == 32 || a.h2 == 64);
+    if (a.n_envs <= 0 || a.n_envs > 256 || a.steps <= 0 || a.d_in != E::D || !widths || a.k != k || a.act_code < 0 ||
+        a.act_code > 2 || a.max_episode_steps <= 0 || a.ld_obs < E::D || a.ld_act < k)
         return false;
     if (!a.W0 || !a.b0 || !a.W1 || !a.b1 || !a.W2 || !a.b2 || !a.Wa || !a.ba || !a.Wc || !a.bc || !a.obs_mean ||
         !a.obs_var || !a.obs_count || !a.act_in || !a.env_state || !a.env_obs || !a.final_obs || !a.env_rew ||
@@ -2705,11 +2782,17 @@ bool ro_eval_args_ok(const XpaSmallRolloutArgs *a0, int k, const int32_t *log, i
     const int64_t lf = xpa_small_rollout_lds_floats(a.n_envs, a.d_in, a.h0, a.h1, a.h2, a.k);
     return lf >= 0 && lf <= kRoLdsMax;
 }
-
 template <class E>
+bool ro_eval_args_ok(const XpaSmallRolloutArgs *a0, int k, const int32_t *log, int64_t capacity, int64_t snap_dim,
+                     const float *scratch) {
+    return ro_eval_args_ok_at<E>(false, a0, k, log, capacity, snap_dim, scratch);
+}
+
+// WIDE: K32WE (the all-128 widths and the ladder's 128-wide column) in place of K32E
+template <class E, bool WIDE = false>
 int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd, int32_t *log, int64_t capacity,
                       int64_t snap_dim, float *scratch, xpa_stream_t stream) {
-    if (!ro_eval_args_ok<E>(a0, k, log, capacity, snap_dim, scratch)) return (int)hipErrorInvalidValue;
+    if (!ro_eval_args_ok_at<E>(WIDE, a0, k, log, capacity, snap_dim, scratch)) return (int)hipErrorInvalidValue;
     XpaSmallRolloutArgs a = *a0;
     const int64_t lf = xpa_small_rollout_lds_floats(a.n_envs, a.d_in, a.h0, a.h1, a.h2, a.k);
     a.horizon = 1;
@@ -2720,7 +2803,7 @@ int small_eval_launch(const XpaSmallRolloutArgs *a0, int k, typename E::Head hd,
     const RoEval ev{log, capacity, eval_log_entries(snap_dim)};
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    ro_dispatch<false>(a.h0, a.act_code, [&](auto ACT, auto H0) {
+    ro_dispatch<WIDE>(a.h0, a.act_code, [&](auto ACT, auto H0) {
         hipLaunchKernelGGL((small_rollout_kernel<E, decltype(ACT)::value, decltype(H0)::value, true>), dim3(1),
                            dim3(kRoThreads), bytes, s, a, hd, ev);
     });
@@ -2802,8 +2885,8 @@ bool ro_eval_same_shape(const XpaSmallRolloutArgs &x, const XpaSmallRolloutArgs 
 }
 
 // xpa_small_eval_batch for one env / head pair: every check on the host copies before any HIP call, the
-// instantiation (K32E's widths only) and the LDS size from block 0, one workgroup per agent
-template <class E>
+// instantiation (K32E's widths only; WIDE: K32WEB, K32W's only) and the LDS size from block 0, one workgroup per agent
+template <class E, bool WIDE = false>
 int small_eval_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host, const XpaSmallRolloutArgs *dev, int k,
                             const XpaSmallRolloutHead *host_heads, const XpaSmallRolloutHead *dev_heads,
                             const XpaSmallEval *host_evals, const XpaSmallEval *dev_evals, xpa_stream_t stream) {
@@ -2814,7 +2897,7 @@ int small_eval_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host, c
     std::vector<uintptr_t> logs, scratches;
     for (int64_t p = 0; p < n_agents; ++p) {
         const XpaSmallEval &e = host_evals[p];
-        if (!ro_eval_args_ok<E>(host + p, k, e.log, e.capacity, e.snap_dim, e.scratch) ||
+        if (!ro_eval_args_ok_at<E>(WIDE, host + p, k, e.log, e.capacity, e.snap_dim, e.scratch) ||
             !ro_eval_same_shape(host[p], host[0]) || e.capacity != host_evals[0].capacity ||
             e.snap_dim != host_evals[0].snap_dim)
             return (int)hipErrorInvalidValue;
@@ -2830,7 +2913,7 @@ int small_eval_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host, c
     const int64_t lf = xpa_small_rollout_lds_floats(a->n_envs, a->d_in, a->h0, a->h1, a->h2, a->k);
     const size_t bytes = (size_t)lf * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
-    ro_dispatch<false>(a->h0, a->act_code, [&](auto ACT, auto H0) {
+    ro_dispatch<WIDE>(a->h0, a->act_code, [&](auto ACT, auto H0) {
         hipLaunchKernelGGL((small_eval_batch_kernel<E, decltype(ACT)::value, decltype(H0)::value>),
                            dim3((unsigned)n_agents), dim3(kRoThreads), bytes, s, dev, dev_heads, dev_evals);
     });
@@ -2981,6 +3064,82 @@ XPA_API int xpa_small_eval_batch(int env, int64_t n_agents, const XpaSmallRollou
     default:
         return (int)hipErrorInvalidValue;
     }
+}
+
+// ---- K32WE / K32WEB and the batched test-env reset ------------------------------------------------------------------
+namespace {
+// f(E{}, k) for the env code's env / head pair and its head width; an unknown code is an error before any HIP call
+template <class F>
+int ro_by_env(int env, F f) {
+    switch (env) {
+    case XPA_ENV_CARTPOLE:
+        return f(RoCartPoleCat{}, 2);
+    case XPA_ENV_PENDULUM:
+        return f(RoPendulumGauss{}, 1);
+    case XPA_ENV_ACROBOT:
+        return f(RoAcrobotCat{}, 3);
+    case XPA_ENV_MOUNTAINCAR:
+        return f(RoMountainCarCat{}, 3);
+    default:
+        return (int)hipErrorInvalidValue;
+    }
+}
+
+// xpa_small_env_reset_batch for one env: the checks on the host copies, then one workgroup per agent
+template <class E>
+int small_env_reset_batch_launch(int64_t n_agents, const XpaSmallRolloutArgs *host, const XpaSmallRolloutArgs *dev,
+                                 int k, xpa_stream_t stream) {
+    if (n_agents < 1 || n_agents > 0x7fffffff || !host || !dev) return (int)hipErrorInvalidValue;
+    std::vector<uintptr_t> states;
+    for (int64_t p = 0; p < n_agents; ++p) {
+        const XpaSmallRolloutArgs &a = host[p];
+        if (a.n_envs < 1 || a.n_envs > 256 || a.n_envs != host[0].n_envs || a.d_in != E::D || a.k != k ||
+            a.ld_obs < E::D || a.ld_act < k)
+            return (int)hipErrorInvalidValue;
+        if (!a.act_in || !a.env_state || !a.env_obs || !a.env_rew || !a.env_term || !a.env_trunc || !a.ep_step ||
+            !a.ep_index || !a.ep_score || !a.ep_last_score || !a.ep_last_len)
+            return (int)hipErrorInvalidValue;
+        states.push_back((uintptr_t)a.env_state);
+    }
+    std::sort(states.begin(), states.end());   // no two members share an env set
+    if (std::adjacent_find(states.begin(), states.end()) != states.end()) return (int)hipErrorInvalidValue;
+    constexpr bool kZeroAct = !std::is_same_v<E, RoCartPoleCat>;
+    hipLaunchKernelGGL((small_env_reset_batch_kernel<E, kZeroAct>), dim3((unsigned)n_agents), dim3(kRoThreads), 0,
+                       (hipStream_t)stream, dev);
+    return xpa_launch_status();
+}
+}  // namespace
+
+XPA_API int xpa_small_eval_wide(int env, const XpaSmallRolloutArgs *a, const XpaSmallRolloutHead *head, int32_t *log,
+                                int64_t capacity, int64_t snap_dim, float *scratch, xpa_stream_t stream) {
+    return ro_by_env(env, [&](auto e, int k) {
+        using E = decltype(e);
+        typename E::Head hd{};
+        if constexpr (std::is_empty_v<typename E::Head>) {
+            if (head) return (int)hipErrorInvalidValue;
+        } else {
+            if (!head || !head->logstd || !(head->act_clip > 0.f)) return (int)hipErrorInvalidValue;
+            hd = typename E::Head{head->logstd, head->act_clip};
+        }
+        return small_eval_launch<E, true>(a, k, hd, log, capacity, snap_dim, scratch, stream);
+    });
+}
+
+XPA_API int xpa_small_eval_wide_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                                      const XpaSmallRolloutArgs *dev_blocks, const XpaSmallRolloutHead *host_heads,
+                                      const XpaSmallRolloutHead *dev_heads, const XpaSmallEval *host_evals,
+                                      const XpaSmallEval *dev_evals, xpa_stream_t stream) {
+    return ro_by_env(env, [&](auto e, int k) {
+        return small_eval_batch_launch<decltype(e), true>(n_agents, host_blocks, dev_blocks, k, host_heads, dev_heads,
+                                                          host_evals, dev_evals, stream);
+    });
+}
+
+XPA_API int xpa_small_env_reset_batch(int env, int64_t n_agents, const XpaSmallRolloutArgs *host_blocks,
+                                      const XpaSmallRolloutArgs *dev_blocks, xpa_stream_t stream) {
+    return ro_by_env(env, [&](auto e, int k) {
+        return small_env_reset_batch_launch<decltype(e)>(n_agents, host_blocks, dev_blocks, k, stream);
+    });
 }
 
 XPA_API int xpa_eval_post(int32_t *log, int64_t capacity, int64_t snap_dim, int64_t n_envs, const uint8_t *term,

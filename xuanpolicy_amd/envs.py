@@ -335,8 +335,12 @@ class CartPoleVecEnv:
     def buf_obs(self):
         return self._obs
 
-    def reset(self):
+    def reset_host(self):
+        """reset()'s host-only half, for a caller whose device half ran in small_path.env_reset_batch's launch."""
         self.resets = getattr(self, "resets", 0) + 1   # agents re-arm a folded obs-RMS merge (K8R)
+
+    def reset(self):
+        self.reset_host()
         s0 = cartpole_reset_states(self.noise_seed, np.arange(self.num_envs), np.zeros(self.num_envs))
         self.state.copy_(torch.as_tensor(s0, device=self.device))
         self._obs.copy_(self.state.float())
@@ -445,8 +449,12 @@ class PendulumVecEnv:
     def buf_obs(self):
         return self._obs
 
-    def reset(self):
+    def reset_host(self):
+        """reset()'s host-only half, for a caller whose device half ran in small_path.env_reset_batch's launch."""
         self.resets = getattr(self, "resets", 0) + 1   # agents re-arm a folded obs-RMS merge (K8R)
+
+    def reset(self):
+        self.reset_host()
         s0 = pendulum_reset_states(self.noise_seed, np.arange(self.num_envs), np.zeros(self.num_envs))
         self.state.copy_(torch.as_tensor(s0, device=self.device))
         o0 = np.stack([np.cos(s0[:, 0]), np.sin(s0[:, 0]), s0[:, 1]], axis=1).astype(np.float32)
@@ -558,8 +566,12 @@ class _Discrete3VecEnv:
     def buf_obs(self):
         return self._obs
 
-    def reset(self):
+    def reset_host(self):
+        """reset()'s host-only half, for a caller whose device half ran in small_path.env_reset_batch's launch."""
         self.resets = getattr(self, "resets", 0) + 1   # agents re-arm a folded obs-RMS merge (K8R)
+
+    def reset(self):
+        self.reset_host()
         s0 = self.reset_states(self.noise_seed, np.arange(self.num_envs), np.zeros(self.num_envs))
         self.state.copy_(torch.as_tensor(s0, device=self.device))
         self._obs.copy_(torch.as_tensor(self.obs_of_reset(s0), device=self.device))

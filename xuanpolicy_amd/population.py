@@ -18,7 +18,7 @@ bit; plan_population_test decides its eligibility, and Population.test falls bac
 import ctypes
 from typing import NamedTuple
 
-from .rollout_plan import K32_DRIVERS, SMALL_BY_ENTRY, SMALL_ENVS, plan_test
+from .rollout_plan import EVAL_TIERS, K32_DRIVERS, SMALL_BY_ENTRY, SMALL_ENVS, plan_test
 
 MAX_AGENTS = 65535   # the y extent of a launch grid (the update's agent dimension); not a function of the CU count
 
@@ -110,6 +110,7 @@ class PopulationTestPlan(NamedTuple):
     n_agents: int
     code: str            # the SMALL_ENVS row's XPA_ENV_* constant's name
     gaussian: bool       # the head array (logstd, act_clip) is passed
+    wide: bool = False   # every member plans "K32WE": the launch is xpa_small_eval_wide_batch (K32WEB)
 
 
 # the fields every member shares with member 0: (name in the error text, where it is read)
@@ -120,8 +121,9 @@ _TEST_SHARED = (("env", lambda f: f.eval.env), ("dist", lambda f: f.eval.dist), 
 
 
 def plan_population_test(facts):
-    """The PopulationTestPlan of the members' evaluation facts (one K32EB launch serves them all), or ValueError naming
-    the first thing that rules it out.  The only place the population evaluation's eligibility is decided."""
+    """The PopulationTestPlan of the members' evaluation facts (one K32EB launch serves them all; K32WEB where they all
+    plan "K32WE"), or ValueError naming the first thing that rules it out.  The only place the population evaluation's
+    eligibility is decided."""
     facts = list(facts)
     if not 1 <= len(facts) <= MAX_AGENTS:
         raise ValueError("a population has 1 .. %d members, not %d" % (MAX_AGENTS, len(facts)))
@@ -130,10 +132,15 @@ def plan_population_test(facts):
             raise ValueError("member %d: world size %d (a population is evaluated in one process: world must be 1)"
                              % (i, f.eval.world))
         tier = plan_test(f.eval)
-        if tier != "K32E":
+        if tier not in EVAL_TIERS:
             raise ValueError("member %d: its test envs plan the %r tier, not the one-launch evaluation \"K32E\""
                              % (i, tier))
     f0 = facts[0]
+    tier0 = plan_test(f0.eval)
+    for i, f in enumerate(facts[1:], 1):
+        if plan_test(f.eval) != tier0:
+            raise ValueError("member %d: its test envs plan the %r tier, member 0's the %r tier (one launch serves one "
+                             "tier)" % (i, plan_test(f.eval), tier0))
     for i, f in enumerate(facts[1:], 1):
         for name, get in _TEST_SHARED:
             if get(f) != get(f0):
@@ -145,7 +152,7 @@ def plan_population_test(facts):
                 raise ValueError("members %d and %d share a tensor (data pointer 0x%x)" % (seen[ptr], i, ptr))
         seen.update((ptr, i) for ptr in f.tensors)
     row = SMALL_ENVS[f0.eval.env, f0.eval.dist]
-    return PopulationTestPlan(len(facts), row.code, row.gaussian)
+    return PopulationTestPlan(len(facts), row.code, row.gaussian, tier0 == "K32WE")
 
 
 def _block_array(struct, blocks):
@@ -423,7 +430,7 @@ class Population:
         f = a._eval_facts(env)
         policy = a.learner.small_policy_layers()
         tensors = ()
-        if plan_test(f) == "K32E":
+        if plan_test(f) in EVAL_TIERS:
             ts = [env.state, env.obs, env.act_in, env.final_obs, env.rew, env.term, env.trunc, env.ep_step, env.ep_index,
                   env.ep_score, env.ep_last_score, env.ep_last_len, a.obs_mean, a.obs_var, a.obs_count]
             tensors = tuple(int(t.data_ptr()) for t in ts)
@@ -438,14 +445,17 @@ class Population:
                              % (len(self.agents), len(envs)))
         return plan_population_test([self._test_facts(a, e) for a, e in zip(self.agents, envs)])
 
-    def test_device(self, test_envs, test_episode, chunk=None, rngs=None):
+    def test_device(self, test_envs, test_episode, chunk=None, rngs=None, batch_reset=False):
         """[a.test_device(e, test_episode, chunk, rng) for a, e, rng in zip(agents, test_envs, rngs)] with every
-        member's steps in ONE launch per chunk (xpa_small_eval_batch) and one read of the P log headers after it:
+        member's steps in ONE launch per chunk (xpa_small_eval_batch; xpa_small_eval_wide_batch for members that plan
+        "K32WE") and one read of the P log headers after it:
         each member's returned scores, last_test_log, obs statistics, test-env state and evaluation cursor are its own
         call's, and nothing else of a member changes.  test_envs: one set of device envs per member; rngs: None or one
         (seed, step) per member.  A member whose log is complete sits out the later launches (its workgroup returns at
-        once).  One stream, no graph capture; an ineligible population raises ValueError (plan_population_test): there
-        is no sequential fallback in here."""
+        once).  batch_reset: the members' env.reset() calls are one xpa_small_env_reset_batch launch over the
+        evaluation's own blocks plus each env's host half (reset_host), leaving every env as reset() does.  One stream,
+        no graph capture; an ineligible population raises ValueError (plan_population_test): there is no sequential
+        fallback in here."""
         import torch
         from . import _lib, ops, small_path
         agents, envs = self.agents, list(test_envs)
@@ -468,7 +478,8 @@ class Population:
         scratch = torch.empty((P, 3 * N), dtype=torch.float32, device=dev)
         blocks, heads, evals, cursors = [], [], [], []
         for p, (a, env, rng) in enumerate(zip(agents, envs, rngs)):
-            env.reset()
+            if not batch_reset:
+                env.reset()
             seed, cursor = a._eval_stream(rng)
             args, logstd = a._build_small_eval(env, seed, cursor)
             args.steps = chunk
@@ -481,10 +492,15 @@ class Population:
         arrays = (cache.get(_block_array(_lib.XpaSmallRolloutArgs, blocks)),
                   plan.gaussian and cache.get(_block_array(_lib.XpaSmallRolloutHead, heads)),
                   cache.get(_block_array(_lib.XpaSmallEval, evals)))
+        if batch_reset:
+            small_path.env_reset_batch(plan.code, P, arrays[0], dev)
+            for env in envs:
+                env.reset_host()
+        launch = small_path.small_eval_wide_batch if plan.wide else small_path.small_eval_batch
         bound = (target // N + 2) * max_ep
         issued = 0
         while True:
-            small_path.small_eval_batch(plan.code, P, *arrays, dev)
+            launch(plan.code, P, *arrays, dev)
             issued += chunk
             head = ops.eval_log_headers(logs)   # [P, 8]: count, target, done, steps_run, overflow
             for p in range(P):
@@ -510,7 +526,10 @@ class Population:
         """[a.test(env_fn, test_episode) for a in agents]: one env_fn() call per member, in member order.  Where every
         member's config has device_test and plan_population_test admits the members over their test envs, the
         evaluation is test_device's batch launches, followed by each member's own printing, log_infos and
-        test_envs.close() (agent._finish_test); otherwise it is that loop itself."""
+        test_envs.close() (agent._finish_test); otherwise it is that loop itself.  128-wide members take the batch
+        launches where every member's config has device_test_wide (a member's own flag decides its tier, so a
+        population that mixes them is not admitted and loops); where every member's config has device_test_batch_reset
+        the batch path resets the members' test envs in one launch (test_device's batch_reset)."""
         from .agents import _cfg
         agents = self.agents
         if not all(bool(_cfg(a.config, "device_test", False)) for a in agents):
@@ -520,7 +539,8 @@ class Population:
             self.plan_test(envs)
         except ValueError:
             return [a.test(lambda e=e: e, test_episode) for a, e in zip(agents, envs)]
-        scores = self.test_device(envs, test_episode)
+        batch_reset = all(bool(_cfg(a.config, "device_test_batch_reset", False)) for a in agents)
+        scores = self.test_device(envs, test_episode, batch_reset=batch_reset)
         return [a._finish_test(e, s) for a, e, s in zip(agents, envs, scores)]
 
     # ---- public API -------------------------------------------------------------------------------------------------

@@ -251,19 +251,26 @@ class EvalFacts(NamedTuple):
     raw_obs: bool
     world: int
     sync_obs_rms: object      # as RolloutFacts.sync_obs_rms
+    wide_eval: bool = False   # the switch (config.device_test_wide): 128-wide nets evaluate in one launch (K32WE)
 
 
 def plan_test(f):
-    """The tier agent.test_device evaluates on: "K32E" (whole steps in one launch: xpa_small_eval_*), "steps" (the
-    multi-kernel step, eager, + xpa_eval_post) or "host" (the reference's Python loop).  The only place it is decided."""
+    """The tier agent.test_device evaluates on: "K32E" (whole steps in one launch: xpa_small_eval_*), "K32WE" (the same
+    at K32W's widths, xpa_small_eval_wide; opt-in: wide_eval), "steps" (the multi-kernel step, eager, + xpa_eval_post)
+    or "host" (the reference's Python loop).  The only place it is decided."""
     if not f.cuda or f.env == "host" or (f.sync_obs_rms is True and f.world > 1):   # the per-step collective
         return "host"
     if (f.env, f.dist) in SMALL_ENVS and not f.raw_obs and 0 < f.n_envs <= 256 and f.small is not None:
         d_in, h0, h1, h2, k, lds = f.small
-        if (h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64) and (d_in, k) == SMALL_ENVS[f.env, f.dist][:2]
-                and d_in == f.obs_dim and 0 < lds <= 16384):
-            return "K32E"
+        if (d_in, k) == SMALL_ENVS[f.env, f.dist][:2] and d_in == f.obs_dim and 0 < lds <= 16384:
+            if h0 in (32, 64) and h1 in (32, 64) and h2 in (32, 64):
+                return "K32E"
+            if f.wide_eval and (h0, h1, h2) == (128, 128, 128):
+                return "K32WE"
     return "steps"
+
+
+EVAL_TIERS = ("K32E", "K32WE")   # the one-launch evaluation's tiers: the same body, run the same way
 
 
 def eval_entry(f):

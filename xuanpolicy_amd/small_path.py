@@ -155,6 +155,37 @@ def small_eval_batch(code, n_agents, blocks, heads, evals, device):
               _stream(device))
 
 
+def small_eval_wide(code, args, log, capacity, snap_dim, scratch, logstd=None, act_clip=1.0):
+    """K32WE (xpa_small_eval_wide): small_eval at K32W's widths (h0 = h1 = h2 = 128).  code: the SMALL_ENVS row's; the
+    other arguments as small_eval's (logstd / act_clip: a Gaussian row's head)."""
+    from .ops import _eval_log_dims, _req
+    _eval_log_dims(log, capacity, snap_dim)
+    _req(scratch, "scratch", torch.float32, (3 * int(args.n_envs),))
+    row = next((r for r in SMALL_ENVS.values() if r.code == code), None)
+    if row is None:
+        raise _lib.XpaError("no one-launch evaluation for the env code %r" % (code,))
+    head = None
+    if row.gaussian:
+        head = ctypes.byref(_lib.XpaSmallRolloutHead(_p(_req(logstd, "logstd", torch.float32, (1,))), float(act_clip)))
+    _lib.call(_lib.load().xpa_small_eval_wide, _lib.ENV_CODES[code], ctypes.byref(args), head, log.data_ptr(),
+              int(capacity), int(snap_dim), scratch.data_ptr(), _stream(log.device))
+
+
+def small_eval_wide_batch(code, n_agents, blocks, heads, evals, device):
+    """K32WEB (xpa_small_eval_wide_batch): small_eval_batch at K32W's widths; the same arguments."""
+    _lib.call(_lib.load().xpa_small_eval_wide_batch, _lib.ENV_CODES[code], n_agents, ctypes.addressof(blocks[0]),
+              blocks[1].data_ptr(), *_head_arrays(heads), ctypes.addressof(evals[0]), evals[1].data_ptr(),
+              _stream(device))
+
+
+def env_reset_batch(code, n_agents, blocks, device):
+    """xpa_small_env_reset_batch: the device half of env.reset() for n_agents env sets in one launch, over the blocks an
+    evaluation launch takes ((ctypes array, its copy in device memory as a uint8 tensor)); the caller owes each env
+    its host half (env.reset_host())."""
+    _lib.call(_lib.load().xpa_small_env_reset_batch, _lib.ENV_CODES[code], n_agents, ctypes.addressof(blocks[0]),
+              blocks[1].data_ptr(), _stream(device))
+
+
 def small_close(block, device):
     """K33 (xpa_small_close): one agent's closing — the deferred bootstraps' critic with K32's arithmetic, the
     fixup's writes and the advantage scan — in one launch.  block: small_close_args'."""
