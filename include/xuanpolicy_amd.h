@@ -1273,6 +1273,22 @@ int xpa_conv_wgrad(int act, const float *g, const float *y, float slope, const f
 /* Diagnostics: on != 0 makes xpa_conv_wgrad take its streaming form (operands straight from global memory) even where
  * the LDS-slab form applies (both give the same sums up to f32 association; process-global, not thread-safe). */
 void xpa_conv_wgrad_force_stream(int on);
+/* K28R — xpa_conv_fwd for the small row counts K28 leaves to the library (the rollout's 1024-frame forwards, the
+ * Q-learner's batch-2048 forwards; csrc/igemm_small.hip): the same y = act(conv(x, w) + bias), pixel map, activation
+ * codes and NHWC output, on the bf16 matrix cores with both operands in the exact three-way split (six products, the
+ * f32 GEMM's accuracy), 128-row blocks, several per CU, and the weights streamed tap by tap from planes split ahead of
+ * the launch.  in_c 16, 32 or 64; 1 <= out_c <= 64; 1 <= kernel <= 12 (xpa_conv_small_ok; host only).  Correct at any
+ * row count; bit-identical between launches, and a row's value does not depend on the batch around it.
+ * xpa_conv_wsplit: w [out_c][in_c][kernel][kernel] (f32, torch's layout) -> planes (xpa_conv_wsplit_bytes(in_c, out_c,
+ *   kernel) bytes, 16-B aligned; 0 for a shape outside the envelope): once per weight version.
+ * xpa_conv_fwd_small: x 16-B aligned, x and y under 2 GiB each, bias nullable; hipErrorInvalidValue for anything
+ *   outside the envelope, a NULL pointer or a misaligned operand, before any launch. */
+int xpa_conv_small_ok(int64_t in_c, int64_t out_c, int64_t kernel);
+int64_t xpa_conv_wsplit_bytes(int64_t in_c, int64_t out_c, int64_t kernel);
+int xpa_conv_wsplit(const float *w, int64_t in_c, int64_t out_c, int64_t kernel, void *planes, xpa_stream_t stream);
+int xpa_conv_fwd_small(int act, const float *x, int64_t batch, int64_t in_h, int64_t in_w, int64_t in_c,
+                       const void *planes, const float *bias, int64_t out_c, int64_t kernel, int64_t stride,
+                       int64_t pad, float slope, float *y, xpa_stream_t stream);
 
 /* r06, K14F — one device env step's last launch: xpa_rollout_policy_head_synthbox (policy heads, sample, store, SynthBox
  * env step) and K8's deferred + normalised post step (xpa_rollout_post_deferred_norm; with obs_count non-NULL also the

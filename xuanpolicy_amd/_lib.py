@@ -18,7 +18,7 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 LIB_PATH = os.path.join(PKG_DIR, "libxuanpolicy_amd.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["gae.hip", "loss.hip", "rollout.hip", "optim.hip", "mlp.hip", "head.hip", "thin.hip", "per.hip", "atari.hip",
-           "classic.hip", "dqn.hip", "conv.hip", "igemm.hip", "smallmlp.hip", "sgemm3.hip"]
+           "classic.hip", "dqn.hip", "conv.hip", "igemm.hip", "igemm_small.hip", "smallmlp.hip", "sgemm3.hip"]
 HEADER = os.path.join(REPO_DIR, "include", "xuanpolicy_amd.h")
 
 
@@ -84,6 +84,8 @@ ABI_VERSION, COLSUM_TICKET_INTS = _constants["XPA_ABI_VERSION"], _constants["XPA
 ENV_CODES = {n: v for n, v in _constants.items() if n.startswith("XPA_ENV_")}   # xpa_small_rollout_batch's `env`
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall"]
+# per-source additions: K28R is generated without the packed-f32 VALU forms (v_pk_add / mul / fma_f32)
+EXTRA_FLAGS = {"igemm_small.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 OBJ_DIR = os.path.join(PKG_DIR, "_obj")
 
 _lib = None
@@ -115,13 +117,14 @@ def build_library(force=False, verbose=False, jobs=None):
 
     def compile_one(src):
         obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
-        want = _digest([src], hdr_digest)
+        extra = EXTRA_FLAGS.get(os.path.basename(src), [])
+        want = _digest([src], hdr_digest + " ".join(extra))
         stamp = obj + ".sha256"
         if not force and os.path.exists(obj) and os.path.exists(stamp):
             with open(stamp) as f:
                 if f.read().strip() == want:
                     return obj
-        cmd = [hipcc] + HIPCC_FLAGS + ["-c", "-o", obj + ".tmp", src]
+        cmd = [hipcc] + HIPCC_FLAGS + extra + ["-c", "-o", obj + ".tmp", src]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)

@@ -29,13 +29,15 @@ class ConvFacts(NamedTuple):
     igemm: bool         # K28 forward and K29 both take the shape (xpa_conv_igemm_ok and xpa_conv_wgrad_ok included)
     igemm_dgrad: bool   # K28's data gradient takes it
     k27: bool           # K27 takes the data gradient: 2s x 2s, stride s (1, 2), 32 -> 64 channels
+    small: bool = False  # K28R takes the forward (xpa_conv_small_ok: 16 / 32 / 64 input channels, <= 64 outputs)
 
 
-def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_ok=None, wgrad_ok=None):
+def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_ok=None, wgrad_ok=None, small_ok=None):
     """The ConvFacts of one Conv2d: the static shape rules of K27 / K28 / K29.  igemm_ok(in, out, k) and
     wgrad_ok(in, out, k) are the library's xpa_conv_igemm_ok (K28's weight image) and xpa_conv_wgrad_ok (K29's tiling),
     asked by the caller's hand (the planner never asks; None: not asked, no K28 / K29).  A block is on the K28 / K29
-    path only when both take it: one that K29 cannot take plans the library route in all three directions."""
+    path only when both take it: one that K29 cannot take plans the library route in all three directions.
+    small_ok(in, out, k) is xpa_conv_small_ok (K28R's envelope; None: not asked, no K28R)."""
     k, s, p = kernel[0], stride[0], padding[0]
     square = kernel[0] == kernel[1] and stride[0] == stride[1] and padding[0] == padding[1]
     plain = square and zeros and w_contig
@@ -43,7 +45,8 @@ def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_o
                  and igemm_ok(cin, cout, k) and wgrad_ok(cin, cout, k))
     dgrad = bool(igemm and s <= 2 and cout % 4 == 0 and igemm_ok(cout, cin, k))
     k27 = plain and cin == 32 and cout == 64 and s in (1, 2) and k == 2 * s and p < k
-    return ConvFacts(cin, cout, k, s, p, square, zeros, w_contig, act, igemm, dgrad, k27)
+    small = bool(plain and small_ok is not None and small_ok(cin, cout, k))
+    return ConvFacts(cin, cout, k, s, p, square, zeros, w_contig, act, igemm, dgrad, k27, small)
 
 
 class CnnFacts(NamedTuple):
@@ -66,17 +69,19 @@ class CnnFacts(NamedTuple):
     fc_fuse_act: bool
     fc_wsplit: bool
     s3_gemms: bool            # ops.S3_GEMMS
+    small_conv: bool = False  # K28R for the forwards below igemm_min_rows
 
 
 class ConvForm(NamedTuple):
-    fwd: str       # "K25" | "K28" | "miopen" (+ K21)
+    fwd: str       # "K25" | "K28" | "K28R" (the forward below igemm_min_rows, opt-in) | "miopen" (+ K21)
     act_bwd: str   # who forms this block's dz and bias gradient: "K22" | "K24" (the max pool's) | "K26" | "K29" |
                    # "K40G-act" (the fc data gradient's epilogue) | "K28-dgrad" (the next block's data gradient's)
     wgrad: str     # "K26" | "K29" | "miopen"
     dgrad: str     # "none" (the first block) | "K27" | "K28" | "miopen"
 
 
-_FWD = {"K25": ("xpa_conv1_u8_fwd",), "K28": ("xpa_conv_fwd",), "miopen": ("xpa_bias_act",)}
+_FWD = {"K25": ("xpa_conv1_u8_fwd",), "K28": ("xpa_conv_fwd",), "K28R": ("xpa_conv_fwd_small",),
+        "miopen": ("xpa_bias_act",)}
 _ACT_BWD = {"K22": ("xpa_act_bwd_bias", "xpa_colsum_finalize"), "K10": ("xpa_act_bwd_colsum", "xpa_colsum_finalize"),
             "K24": ("xpa_maxpool_act_bwd_bias", "xpa_colsum_finalize")}
 # (the weight gradient's finalize, + the bias gradient's where the kernel also forms the activation backward)
@@ -102,8 +107,8 @@ class CnnPlan(NamedTuple):
 
     def launches(self, direction):
         """The library entry points of one trunk "forward" or "backward", in order.  MIOpen's, hipBLASLt's and torch's
-        launches are not counted, nor is the re-split of the first fc weight's planes after an optimizer step
-        (xpa_s3_split_batch: state, not plan)."""
+        launches are not counted, nor is the re-split of the first fc weight's planes (xpa_s3_split_batch) or of
+        K28R's conv weight planes (xpa_conv_wsplit) after an optimizer step: state, not plan."""
         out = []
         if direction == "forward":
             if self.frames == "forward":
@@ -162,6 +167,11 @@ def plan_cnn(f):
     # forward: the operand is the larger of the block's input and its output (K28 stores through a buffer record too)
     fwd = ["K25" if i == 0 and f.u8_conv1 and f.x_u8 else "K28" if igemm(i, max(numel[i], numel[i + 1])) else "miopen"
            for i in range(n)]
+    # K28R (opt-in): the forward of a block the library route would take, i.e. one K28 left for its row count.  The
+    # backward forms below do not read it
+    if f.small_conv:
+        fwd = ["K28R" if w == "miopen" and f.convs[i].small and max(numel[i], numel[i + 1]) * 4 < 2 ** 31 else w
+               for i, w in enumerate(fwd)]
     # the first fc layer
     fc0_fwd, fc0_dw, fc0_dx, slack, halves, fcs = None, "mm", "mm", 0, 0, ()
     if f.tail == "flatten":
@@ -174,10 +184,10 @@ def plan_cnn(f):
         fc0_fwd = "K40G" if split else "linear"
         fc0_dx = "K40G-act" if fuse else "K40G" if split else "mm"
         # K41V reads the flat input as 128-row tiles: a ragged width needs slack after the last row, which only K28's
-        # output can carry
+        # (or K28R's) output can carry
         pad = -in_f % 128
         if f.fc_wsplit and rows_ok and out_f % 256 == 0 and in_f % 4 == 0:
-            slack = pad if fwd[-1] == "K28" else 0
+            slack = pad if fwd[-1] in ("K28", "K28R") else 0
             fc0_dw = "K41V" if not pad else "K41V-padded" if slack else "mm"
             halves = out_f // 256 if fc0_dw != "mm" else 0
         fcs = tuple(("K21" if code or (j == 0 and split) else None, "K22" if k22_width(width) else "K10")

@@ -15,7 +15,9 @@ decided"):
   fwd       per conv block: "K25" xpa_conv1_u8_fwd (the 4 x 8 x 8 -> 32 conv on fp32 MFMA straight from the uint8
             frames as sum x (w / 255) — one f32 rounding per term like the reference's sum float(x / 255) w —, bias +
             activation in its epilogue), "K28" xpa_conv_fwd (the same epilogue; the last block's output with `slack`
-            floats after it), "miopen" (conv2d without bias on the channels-last view + K21 xpa_bias_act in place)
+            floats after it), "K28R" xpa_conv_fwd_small (K28's output from the conv's split weight planes: the opt-in
+            form of the forwards below igemm_min_rows), "miopen" (conv2d without bias on the channels-last view + K21
+            xpa_bias_act in place)
   tail      AC_CNN_Atari: Flatten in NHWC order — the first fc layer uses its weight with the columns permuted from
             the reference's (C, H, W) order to (H, W, C) (one 13 MB copy per parameter update, instead of an
             NHWC -> NCHW copy of the [B, 6400] activations every forward); Basic_CNN: K23 xpa_global_maxpool (max +
@@ -48,9 +50,9 @@ def _out_hw(conv, H, W):
     return out_hw(H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
 
 
-def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None):
+def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None, small_ok=None):
     return conv_facts(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
-                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok, wgrad_ok)
+                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok, wgrad_ok, small_ok)
 
 
 class _Ctx(NamedTuple):
@@ -200,6 +202,8 @@ class _Trunk:
         self._w_ver = 0         # bumped whenever _w_hwc is re-derived (the fc split planes follow it)
         self._fcs = None        # K40G planes of _w_hwc (forward k halves, data-gradient column blocks) + their version
         self.stale = True
+        self._cw_ver = 1        # the conv weights' version: bumped by refresh() and by backward() (an optimizer step
+        self._cws = {}          # follows); conv index -> [version, planes]: K28R's split weight planes
         self._dw_tmp = None
         self._fcq = ops.ColsumQueue()   # K41V's batched finalize
         self.err = None         # K24's device error word (argmax outside [0, HW)), made by the first backward
@@ -207,10 +211,11 @@ class _Trunk:
         self.last_plan = None   # the plan of the latest forward
         self.parts = parts
         self.n_params = 2 * (len(self.convs) + len(self.fc))
-        # the static shape rules of K27 / K28 / K29, asked once (the library's xpa_conv_igemm_ok and xpa_conv_wgrad_ok
-        # included)
-        igemm_ok, wgrad_ok = ops.lib().xpa_conv_igemm_ok, ops.lib().xpa_conv_wgrad_ok
-        self.conv_facts = tuple(_conv_facts(conv, code, igemm_ok, wgrad_ok) for conv, code, _ in self.convs)
+        # the static shape rules of K27 / K28 / K29 / K28R, asked once (the library's xpa_conv_igemm_ok,
+        # xpa_conv_wgrad_ok and xpa_conv_small_ok included)
+        L = ops.lib()
+        self.conv_facts = tuple(_conv_facts(conv, code, L.xpa_conv_igemm_ok, L.xpa_conv_wgrad_ok, L.xpa_conv_small_ok)
+                                for conv, code, _ in self.convs)
         # K25: the first conv block straight from the uint8 frames (4 channels, 8 x 8 kernel, 32 outputs: the Nature
         # CNN's first layer); the f32 frame copy (K20) is then only made in the backward, for MIOpen's weight gradient
         c0 = self.conv_facts[0]
@@ -235,6 +240,12 @@ class _Trunk:
     # K28 / K29.
     use_igemm = True
     igemm_min_rows = 1 << 20
+    # small_conv: K28R (xpa_conv_fwd_small) for the forwards K28 leaves to the library for their row count (C3's
+    # rollout: 1024 frames = 102 400 rows per conv; C5's batch-2048 eval / target forwards and its action selection):
+    # 128-row blocks, three per CU, the weights split once per weight version (_conv_planes) and streamed tap by tap
+    # through LDS.  Forward only: the backward below igemm_min_rows stays where it is.  Off by default; the config key
+    # conv_small_rows sets it on the trunks of the agent being built (tools/conv_small_ab.py measures it).
+    small_conv = False
     # r05, fc_split: the first fc layer of the update's minibatches (C3: [16384, 6400] x [6400, 512]) on the bf16 matrix
     # cores by the three-way split (K40G: one launch per GEMM; forward in 2 k halves x 256-column blocks, summed in a
     # fixed order; the data gradient in 256-column blocks, the last one aligned to the end so no block is padded — the
@@ -262,7 +273,7 @@ class _Trunk:
         """What can differ between two passes of this trunk (CnnFacts' last fields, and the plan cache's key): the only
         reader of the switches above and of ops.S3_GEMMS."""
         return (B, x_u8, self._grads0_contig(), self.use_igemm, self.igemm_min_rows, self.fc_split,
-                self.fc_split_min_rows, self.fc_fuse_act, self.fc_wsplit, ops.S3_GEMMS)
+                self.fc_split_min_rows, self.fc_fuse_act, self.fc_wsplit, ops.S3_GEMMS, self.small_conv)
 
     def facts(self, B, x_u8=True):
         """The CnnFacts of a pass over B frames (x_u8: a contiguous uint8 device tensor, what the agents feed)."""
@@ -293,9 +304,32 @@ class _Trunk:
         return out
 
     def refresh(self):
+        """The weights changed (an optimizer step, a target copy, a loaded checkpoint): re-derive what is kept of them
+        now — the (H, W, C)-ordered first fc weight and, with small_conv, every K28R conv's planes — so that the
+        forwards that follow (a captured rollout's among them) launch no split."""
         self.stale = True
+        self._cw_ver += 1
         if self.tail == "flatten":
             self._fc0_weight()
+        if self.small_conv:
+            for i, c in enumerate(self.conv_facts):
+                if c.small and not (i == 0 and self.u8_conv1):
+                    self._conv_planes(i)
+
+    def _conv_planes(self, i):
+        """K28R's planes of conv i's weight: allocated on first use, re-split (one xpa_conv_wsplit launch) when their
+        version lags the conv weights'."""
+        conv = self.convs[i][0]
+        ent = self._cws.get(i)
+        if ent is None:
+            nb = int(ops.lib().xpa_conv_wsplit_bytes(conv.in_channels, conv.out_channels, conv.kernel_size[0]))
+            ent = self._cws[i] = [0, torch.empty(nb, dtype=torch.uint8, device=conv.weight.device)]
+        if ent[0] != self._cw_ver:
+            w = conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous()
+            _lib.call(ops.lib().xpa_conv_wsplit, ops._p(w), conv.in_channels, conv.out_channels, conv.kernel_size[0],
+                      ops._p(ent[1]), ops._stream(w.device))
+            ent[0] = self._cw_ver
+        return ent[1]
 
     def _fc0_weight(self):
         if self.stale or self._w_hwc is None:
@@ -423,6 +457,9 @@ class _Trunk:
             elif fwd == "K28":   # bias + activation fused; the last block's output (the fc layer's flat input) with
                 # the plan's slack after it, where the padded K41V reads it as 128-row tiles
                 y = self._conv_fwd(conv, code, slope, h, slack=plan.slack if i == last else 0)
+            elif fwd == "K28R":   # the same output and slack, from the conv's split planes
+                y = self._conv_fwd(conv, code, slope, h, slack=plan.slack if i == last else 0,
+                                   planes=self._conv_planes(i))
             elif fwd == "miopen":
                 z = F.conv2d(h.permute(0, 3, 1, 2), conv.weight, None, conv.stride, conv.padding)
                 y = z.permute(0, 2, 3, 1)
@@ -459,16 +496,18 @@ class _Trunk:
         return s, _Ctx(hs, None, flat, fouts, plan)
 
     @staticmethod
-    def _conv_fwd(conv, code, slope, h, slack=0):
+    def _conv_fwd(conv, code, slope, h, slack=0, planes=None):
         """K28 forward: act(conv(h) + b), h NHWC f32 [B, H, W, C] -> NHWC [B, OH, OW, out].  slack: floats of the same
-        allocation after the output (readable, never written: the padded K41 reads them into output rows it drops)."""
+        allocation after the output (readable, never written: the padded K41 reads them into output rows it drops).
+        planes: the weight's xpa_conv_wsplit planes: K28R instead."""
         B, H, W, C = h.shape
         k, st, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
         OH, OW = _out_hw(conv, H, W)
         h = h if h.is_contiguous() else h.contiguous()
         n = B * OH * OW * conv.out_channels
         y = torch.empty((n + slack,), dtype=torch.float32, device=h.device)[:n].view(B, OH, OW, conv.out_channels)
-        _lib.call(ops.lib().xpa_conv_fwd, code, ops._p(h), B, H, W, C, ops._p(conv.weight), ops._p(conv.bias),
+        fn = ops.lib().xpa_conv_fwd if planes is None else ops.lib().xpa_conv_fwd_small
+        _lib.call(fn, code, ops._p(h), B, H, W, C, ops._p(conv.weight if planes is None else planes), ops._p(conv.bias),
                   conv.out_channels, k, st, pd, float(slope), ops._p(y), ops._stream(h.device))
         return y
 
@@ -597,6 +636,7 @@ class _Trunk:
             elif dgrad != "none" or i > 0:
                 _no_form("conv block %d's data gradient" % i, dgrad)
         self.stale = True   # the optimizer step that follows changes the fc weight
+        self._cw_ver += 1   # and the conv weights (K28R's planes)
 
     def _fc0_backward(self, plan, g, flat):
         """The first fc layer's weight gradient (permuted back into the reference's (C, H, W) column order) and its
@@ -662,6 +702,8 @@ class FusedCNNActorCritic:
     @stale.setter
     def stale(self, v):
         self.trunk_.stale = v
+        if v:
+            self.trunk_._cw_ver += 1
 
     def refresh(self):
         """Re-derive the (H, W, C)-ordered first fc weight now (the agent calls it before a captured rollout, whose
@@ -722,6 +764,8 @@ class FusedQNetwork:
 
     @torch.no_grad()
     def target(self, x):
+        """targetQ [B, A].  The target trunk's K28R planes follow copy_target through refresh(), which the learner
+        calls after every hard update (the flatten tail's fc copy is re-derived on every call, as before)."""
         if self.target_trunk.tail == "flatten":
             self.target_trunk.stale = True   # copy_target() may have changed it since the last call
         s, _ = self.target_trunk.forward(x)

@@ -35,6 +35,7 @@ class Learner:
         self.iterations = 0
         self.grad_sync = None  # set by xuanpolicy_amd.distributed for data-parallel training
         self.fused_cnn_enabled = True
+        self.conv_small_rows = False   # config key conv_small_rows: K28R on the trunks this learner builds (small_conv)
         self._fc = None        # fused_cnn.FusedCNNActorCritic once built (False: the policy does not take it)
 
     def save_model(self, model_path):
@@ -51,6 +52,8 @@ class Learner:
         self.policy.load_state_dict(torch.load(os.path.join(path, names[-1]), map_location=dev, weights_only=True))
         if self._fc:
             self._fc.stale = True
+        if getattr(self, "_fq", None):
+            self._fq.refresh()
 
     def update(self, *args):
         raise NotImplementedError
@@ -120,6 +123,7 @@ class _FusedPolicyGradient(Learner):
                 from .fused_cnn import FusedCNNActorCritic
                 try:
                     fc = FusedCNNActorCritic(self.policy)
+                    fc.trunk_.small_conv = bool(self.conv_small_rows)
                 except ValueError:
                     fc = False
             self._fc = fc
@@ -627,6 +631,7 @@ class PerDQN_Learner(Learner):
                 from .fused_cnn import FusedQNetwork
                 try:
                     fq = FusedQNetwork(self.policy)
+                    fq.eval_trunk.small_conv = fq.target_trunk.small_conv = bool(self.conv_small_rows)
                 except ValueError:
                     fq = False
             self._fq = fq
@@ -667,6 +672,8 @@ class PerDQN_Learner(Learner):
             self.scheduler.step()
         if self.iterations % self.sync_frequency == 0:
             self.policy.copy_target()
+            if fq is not None:
+                fq.target_trunk.refresh()   # what the target trunk keeps of its weights (K28R's planes) follows
         lr = self.optimizer.param_groups[0]["lr"]
         if not sync_info:   # the agent's hot loop: scalars stay on the device
             return td_abs, {"Qloss": sc[0], "learning_rate": lr, "predictQ": sc[1]}
