@@ -1289,6 +1289,28 @@ int xpa_conv_wsplit(const float *w, int64_t in_c, int64_t out_c, int64_t kernel,
 int xpa_conv_fwd_small(int act, const float *x, int64_t batch, int64_t in_h, int64_t in_w, int64_t in_c,
                        const void *planes, const float *bias, int64_t out_c, int64_t kernel, int64_t stride,
                        int64_t pad, float slope, float *y, xpa_stream_t stream);
+/* K28R-D — xpa_conv_dgrad for the same small row counts: dx [batch, in_h, in_w, in_c] = the data gradient of the conv
+ * from dz [batch, out_h, out_w, out_c], times act'(y_prev) with act_prev >= 0 (K28's codes; act' from the previous
+ * block's OUTPUT), K28R's arithmetic and blocks.  The conv's out_c (the GEMM's k) 16, 32 or 64; 1 <= in_c <= 64;
+ * 1 <= kernel <= 12; stride 1 or 2 (xpa_conv_small_dgrad_ok; host only).  Stride 2 runs as one stride-1 map per residue
+ * class of the input pixels, each block inside one class and streaming that class's taps alone; every dx element is
+ * written (a class without taps, an input row no output reaches: act' x 0).  Bit-identical between launches; a pixel's
+ * value does not depend on the batch around it.
+ * xpa_conv_wsplit_t: w [out_c][in_c][kernel][kernel] -> the transposed planes W'[n = ci][c = co][tap]
+ *   (xpa_conv_wsplit_t_bytes(in_c, out_c, kernel) bytes, 16-B aligned; 0 outside the envelope): once per weight version.
+ * xpa_conv_dgrad_small: dz and the planes 16-B aligned, dz and dx under 2 GiB each, out_h / out_w the forward's output
+ *   size; act_prev = -1: the plain dx, y_prev and bias_partial unused; act_prev >= 0 needs y_prev and, with bias_partial
+ *   non-NULL, writes each block's column sums to bias_partial[xpa_conv_dgrad_small_num_partials(batch, in_h, in_w,
+ *   stride)][in_c] (xpa_colsum_finalize -> the previous block's bias gradient).  hipErrorInvalidValue before any launch
+ *   for anything outside these. */
+int xpa_conv_small_dgrad_ok(int64_t in_c, int64_t out_c, int64_t kernel, int64_t stride);
+int64_t xpa_conv_wsplit_t_bytes(int64_t in_c, int64_t out_c, int64_t kernel);
+int xpa_conv_wsplit_t(const float *w, int64_t in_c, int64_t out_c, int64_t kernel, void *planes, xpa_stream_t stream);
+int64_t xpa_conv_dgrad_small_num_partials(int64_t batch, int64_t in_h, int64_t in_w, int64_t stride);
+int xpa_conv_dgrad_small(const float *dz, int64_t batch, int64_t out_h, int64_t out_w, int64_t out_c,
+                         const void *planes, int64_t in_c, int64_t kernel, int64_t stride, int64_t pad, int64_t in_h,
+                         int64_t in_w, int act_prev, const float *y_prev, float slope, float *dx, float *bias_partial,
+                         xpa_stream_t stream);
 
 /* r06, K14F — one device env step's last launch: xpa_rollout_policy_head_synthbox (policy heads, sample, store, SynthBox
  * env step) and K8's deferred + normalised post step (xpa_rollout_post_deferred_norm; with obs_count non-NULL also the

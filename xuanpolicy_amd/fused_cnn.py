@@ -27,10 +27,12 @@ decided"):
             the reference layout either way
   fc0_dx    "K40G-act" (the last conv block's activation backward + bias partials in its epilogue), "K40G" or "mm"
   act_bwd   who forms a conv block's dz and bias gradient: "K22" xpa_act_bwd_bias, "K24" (the pooled gradient routed
-            to the argmax), "K26" / "K29" (folded into the weight gradient), "K40G-act", "K28-dgrad" (the epilogue of
-            the following block's data gradient)
+            to the argmax), "K26" / "K29" (folded into the weight gradient), "K40G-act", "K28-dgrad" / "K28R-dgrad" (the
+            epilogue of the following block's data gradient)
   wgrad     "K26" xpa_conv1_u8_wgrad_act (from the uint8 frames), "K29" xpa_conv_wgrad, "miopen"
-  dgrad     "K27" xpa_conv_dgrad_s2k (the 4 x 4 stride-2 32 -> 64 conv), "K28" xpa_conv_dgrad, "miopen", "none"
+  dgrad     "K27" xpa_conv_dgrad_s2k (the 4 x 4 stride-2 32 -> 64 conv), "K28" xpa_conv_dgrad, "K28R"
+            xpa_conv_dgrad_small (K28's result from the conv's transposed split planes: the opt-in form below
+            igemm_min_rows), "miopen", "none"
 The heads / Q head are GEMMs + K21 forward, GEMMs + K10 / K22 bias column sums backward.
 Parameter gradients are written into the parameters' .grad views (allocated when missing).
 """
@@ -50,9 +52,10 @@ def _out_hw(conv, H, W):
     return out_hw(H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
 
 
-def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None, small_ok=None):
+def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None, small_ok=None, small_dgrad_ok=None):
     return conv_facts(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
-                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok, wgrad_ok, small_ok)
+                      conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok, wgrad_ok, small_ok,
+                      small_dgrad_ok)
 
 
 class _Ctx(NamedTuple):
@@ -204,6 +207,7 @@ class _Trunk:
         self.stale = True
         self._cw_ver = 1        # the conv weights' version: bumped by refresh() and by backward() (an optimizer step
         self._cws = {}          # follows); conv index -> [version, planes]: K28R's split weight planes
+        self._cwts = {}         # the same for K28R-D's transposed planes
         self._dw_tmp = None
         self._fcq = ops.ColsumQueue()   # K41V's batched finalize
         self.err = None         # K24's device error word (argmax outside [0, HW)), made by the first backward
@@ -214,8 +218,8 @@ class _Trunk:
         # the static shape rules of K27 / K28 / K29 / K28R, asked once (the library's xpa_conv_igemm_ok,
         # xpa_conv_wgrad_ok and xpa_conv_small_ok included)
         L = ops.lib()
-        self.conv_facts = tuple(_conv_facts(conv, code, L.xpa_conv_igemm_ok, L.xpa_conv_wgrad_ok, L.xpa_conv_small_ok)
-                                for conv, code, _ in self.convs)
+        self.conv_facts = tuple(_conv_facts(conv, code, L.xpa_conv_igemm_ok, L.xpa_conv_wgrad_ok, L.xpa_conv_small_ok,
+                                            L.xpa_conv_small_dgrad_ok) for conv, code, _ in self.convs)
         # K25: the first conv block straight from the uint8 frames (4 channels, 8 x 8 kernel, 32 outputs: the Nature
         # CNN's first layer); the f32 frame copy (K20) is then only made in the backward, for MIOpen's weight gradient
         c0 = self.conv_facts[0]
@@ -246,6 +250,12 @@ class _Trunk:
     # through LDS.  Forward only: the backward below igemm_min_rows stays where it is.  Off by default; the config key
     # conv_small_rows sets it on the trunks of the agent being built (tools/conv_small_ab.py measures it).
     small_conv = False
+    # small_conv_bwd: K28R-D (xpa_conv_dgrad_small) for the data gradients K28 leaves to the library for their row
+    # count (C5's batch-2048 learner step, a small-minibatch PPO / A2C update), the previous block's activation backward
+    # and bias partials in its epilogue as in K28's (no K22 launch for that block); the transposed planes are split
+    # once per weight version (_conv_planes_t).  Independent of small_conv; off by default; the config key
+    # conv_small_rows_bwd sets it (tools/conv_small_bwd_ab.py measures it).
+    small_conv_bwd = False
     # r05, fc_split: the first fc layer of the update's minibatches (C3: [16384, 6400] x [6400, 512]) on the bf16 matrix
     # cores by the three-way split (K40G: one launch per GEMM; forward in 2 k halves x 256-column blocks, summed in a
     # fixed order; the data gradient in 256-column blocks, the last one aligned to the end so no block is padded — the
@@ -273,7 +283,8 @@ class _Trunk:
         """What can differ between two passes of this trunk (CnnFacts' last fields, and the plan cache's key): the only
         reader of the switches above and of ops.S3_GEMMS."""
         return (B, x_u8, self._grads0_contig(), self.use_igemm, self.igemm_min_rows, self.fc_split,
-                self.fc_split_min_rows, self.fc_fuse_act, self.fc_wsplit, ops.S3_GEMMS, self.small_conv)
+                self.fc_split_min_rows, self.fc_fuse_act, self.fc_wsplit, ops.S3_GEMMS, self.small_conv,
+                self.small_conv_bwd)
 
     def facts(self, B, x_u8=True):
         """The CnnFacts of a pass over B frames (x_u8: a contiguous uint8 device tensor, what the agents feed)."""
@@ -327,6 +338,21 @@ class _Trunk:
         if ent[0] != self._cw_ver:
             w = conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous()
             _lib.call(ops.lib().xpa_conv_wsplit, ops._p(w), conv.in_channels, conv.out_channels, conv.kernel_size[0],
+                      ops._p(ent[1]), ops._stream(w.device))
+            ent[0] = self._cw_ver
+        return ent[1]
+
+    def _conv_planes_t(self, i):
+        """K28R-D's transposed planes of conv i's weight, kept as _conv_planes keeps the forward's: one
+        xpa_conv_wsplit_t launch per weight version, none while the version stands."""
+        conv = self.convs[i][0]
+        ent = self._cwts.get(i)
+        if ent is None:
+            nb = int(ops.lib().xpa_conv_wsplit_t_bytes(conv.in_channels, conv.out_channels, conv.kernel_size[0]))
+            ent = self._cwts[i] = [0, torch.empty(nb, dtype=torch.uint8, device=conv.weight.device)]
+        if ent[0] != self._cw_ver:
+            w = conv.weight if conv.weight.is_contiguous() else conv.weight.contiguous()
+            _lib.call(ops.lib().xpa_conv_wsplit_t, ops._p(w), conv.in_channels, conv.out_channels, conv.kernel_size[0],
                       ops._p(ent[1]), ops._stream(w.device))
             ent[0] = self._cw_ver
         return ent[1]
@@ -528,21 +554,23 @@ class _Trunk:
         if act >= 0:
             _lib.call(L.xpa_colsum_finalize, ops._p(bpart), G, cout, ops._p(conv.bias.grad), st)
 
-    def _conv_dgrad(self, conv, dz, x_shape, prev):
+    def _conv_dgrad(self, conv, dz, x_shape, prev, planes=None):
         """K28 data gradient from dz (the block's pre-activation gradient, NHWC) into the block's input; prev = (code,
         slope, y_prev, bias_grad_prev) of the previous block: its activation backward and bias gradient fused in (the
-        result is then that block's dz)."""
+        result is then that block's dz).  planes: the weight's xpa_conv_wsplit_t planes: K28R-D instead."""
         L, st = ops.lib(), ops._stream(dz.device)
         B, H, W, Cin = x_shape
         k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
         OH, OW = dz.shape[1], dz.shape[2]
         dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dz.device)
         code, slope, y_prev, bgrad = prev
-        G = int(L.xpa_conv_dgrad_num_partials(B, H, W))
-        bpart = self.parts.buf(("dgb", B * H * W, Cin), (G, Cin), dz.device)
+        small = planes is not None
+        G = int(L.xpa_conv_dgrad_small_num_partials(B, H, W, s) if small else L.xpa_conv_dgrad_num_partials(B, H, W))
+        bpart = self.parts.buf(("dgbs" if small else "dgb", B * H * W, Cin, s), (G, Cin), dz.device)
         dz = dz if dz.is_contiguous() else dz.contiguous()
-        _lib.call(L.xpa_conv_dgrad, ops._p(dz), B, OH, OW, conv.out_channels, ops._p(conv.weight), Cin, k, s, p, H, W,
-                  code, ops._p(y_prev), float(slope), ops._p(dx), ops._p(bpart), st)
+        _lib.call(L.xpa_conv_dgrad_small if small else L.xpa_conv_dgrad, ops._p(dz), B, OH, OW, conv.out_channels,
+                  ops._p(planes if small else conv.weight), Cin, k, s, p, H, W, code, ops._p(y_prev), float(slope),
+                  ops._p(dx), ops._p(bpart), st)
         _lib.call(L.xpa_colsum_finalize, ops._p(bpart), G, Cin, ops._p(bgrad), st)
         return dx
 
@@ -611,7 +639,7 @@ class _Trunk:
             x_in = self.frames(hs[0]) if i == 0 and plan.frames == "backward" else hs[i]
             if act_bwd == "K22":   # the data gradient and the library weight gradient read dz: in place, + the bias
                 _act_bwd_bias(self.parts, code, g.view(-1, Cy), y.view(-1, Cy), slope, conv.bias.grad)
-            elif act_bwd not in ("K24", "K40G-act", "K28-dgrad") and act_bwd != wgrad:   # upstream, or K26 / K29's own
+            elif act_bwd not in ("K24", "K40G-act", "K28-dgrad", "K28R-dgrad") and act_bwd != wgrad:   # upstream, or K26 / K29's own
                 _no_form("conv block %d's activation backward" % i, act_bwd)
             # the weight gradient, with the activation backward + bias gradient folded in where act_bwd names it
             if wgrad == "K26":
@@ -630,9 +658,10 @@ class _Trunk:
                 g = gx.permute(0, 2, 3, 1)
             elif dgrad == "K27":   # (the stride-2 32 -> 64 conv): the previous block's g, not dz
                 g = self._dgrad(conv, g, x_in.shape)
-            elif dgrad == "K28":   # with the previous block's activation backward + bias gradient
+            elif dgrad in ("K28", "K28R"):   # with the previous block's activation backward + bias gradient
                 pconv, pcode, pslope = self.convs[i - 1]
-                g = self._conv_dgrad(conv, g, tuple(x_in.shape), (pcode, pslope, hs[i], pconv.bias.grad))
+                g = self._conv_dgrad(conv, g, tuple(x_in.shape), (pcode, pslope, hs[i], pconv.bias.grad),
+                                     planes=self._conv_planes_t(i) if dgrad == "K28R" else None)
             elif dgrad != "none" or i > 0:
                 _no_form("conv block %d's data gradient" % i, dgrad)
         self.stale = True   # the optimizer step that follows changes the fc weight

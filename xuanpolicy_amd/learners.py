@@ -36,7 +36,14 @@ class Learner:
         self.grad_sync = None  # set by xuanpolicy_amd.distributed for data-parallel training
         self.fused_cnn_enabled = True
         self.conv_small_rows = False   # config key conv_small_rows: K28R on the trunks this learner builds (small_conv)
+        self.conv_small_rows_bwd = False   # config key conv_small_rows_bwd: K28R-D on their backward (small_conv_bwd)
         self._fc = None        # fused_cnn.FusedCNNActorCritic once built (False: the policy does not take it)
+
+    def _trunk_switches(self, trunk, backward=True):
+        """The config keys this learner carries, onto a CNN trunk it has built (backward False: a trunk that only runs
+        forwards, the Q-learner's target)."""
+        trunk.small_conv = bool(self.conv_small_rows)
+        trunk.small_conv_bwd = bool(backward and self.conv_small_rows_bwd)
 
     def save_model(self, model_path):
         torch.save(self.policy.state_dict(), model_path)
@@ -123,7 +130,7 @@ class _FusedPolicyGradient(Learner):
                 from .fused_cnn import FusedCNNActorCritic
                 try:
                     fc = FusedCNNActorCritic(self.policy)
-                    fc.trunk_.small_conv = bool(self.conv_small_rows)
+                    self._trunk_switches(fc.trunk_)
                 except ValueError:
                     fc = False
             self._fc = fc
@@ -631,7 +638,8 @@ class PerDQN_Learner(Learner):
                 from .fused_cnn import FusedQNetwork
                 try:
                     fq = FusedQNetwork(self.policy)
-                    fq.eval_trunk.small_conv = fq.target_trunk.small_conv = bool(self.conv_small_rows)
+                    self._trunk_switches(fq.eval_trunk)
+                    self._trunk_switches(fq.target_trunk, backward=False)
                 except ValueError:
                     fq = False
             self._fq = fq
