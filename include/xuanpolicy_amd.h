@@ -1311,6 +1311,28 @@ int xpa_conv_dgrad_small(const float *dz, int64_t batch, int64_t out_h, int64_t 
                          const void *planes, int64_t in_c, int64_t kernel, int64_t stride, int64_t pad, int64_t in_h,
                          int64_t in_w, int act_prev, const float *y_prev, float slope, float *dx, float *bias_partial,
                          xpa_stream_t stream);
+/* K28R-W — xpa_conv_wgrad for the same small row counts: per-block partials of dW = sum over the output pixels of
+ * dz x, in the weight's [out_c][in_c][kernel][kernel] order (xpa_colsum_finalize -> the weight gradient), both operands
+ * in the exact three-way bf16 split.  dz [batch, out_h, out_w, out_c] is the block's pre-activation gradient (no
+ * activation is folded in), x [batch, in_h, in_w, in_c] its input, both NHWC f32, 16-B aligned, under 2 GiB each;
+ * out_h / out_w the forward's output size.  in_c and out_c 16, 32 or 64, stride 1 or 2, any padding,
+ * kernel^2 in_c out_c <= 36 864 (xpa_conv_small_wgrad_ok; host only).  A persistent grid of at most one block per CU
+ * over slabs of output rows; partial [xpa_conv_wgrad_small_num_partials(...)][out_c in_c kernel^2], every partial
+ * written whole.  The map's own rule is xpa_conv_wgrad_small_fits (host only, no runtime call; what the launch itself
+ * checks and what a planner asks with the block's input size): 1 iff the shape is inside the envelope and a slab of one
+ * output row fits, i.e. its padded input rows ((out_w - 1) stride + kernel pixels wide, kernel rows) and its dz row in
+ * two LDS stages of three bf16 planes each (160 KiB in all) and in 6 + 3 float4 staging units per thread: e.g. square
+ * inputs up to 32 wide at 64 -> 64 3 x 3 stride 1, 53 at 32 -> 64 4 x 4 stride 2.  num_partials is 0 for arguments the
+ * launch rejects.  Bit-identical between launches; nothing but the partials is written.  hipErrorInvalidValue before
+ * any launch for anything outside these. */
+int xpa_conv_small_wgrad_ok(int64_t in_c, int64_t out_c, int64_t kernel, int64_t stride);
+int xpa_conv_wgrad_small_fits(int64_t in_h, int64_t in_w, int64_t in_c, int64_t out_c, int64_t kernel, int64_t stride,
+                              int64_t pad);
+int64_t xpa_conv_wgrad_small_num_partials(int64_t batch, int64_t in_h, int64_t in_w, int64_t in_c, int64_t out_c,
+                                          int64_t kernel, int64_t stride, int64_t pad);
+int xpa_conv_wgrad_small(const float *dz, const float *x, int64_t batch, int64_t in_h, int64_t in_w, int64_t in_c,
+                         int64_t out_c, int64_t kernel, int64_t stride, int64_t pad, int64_t out_h, int64_t out_w,
+                         float *partial, xpa_stream_t stream);
 
 /* r06, K14F — one device env step's last launch: xpa_rollout_policy_head_synthbox (policy heads, sample, store, SynthBox
  * env step) and K8's deferred + normalised post step (xpa_rollout_post_deferred_norm; with obs_count non-NULL also the

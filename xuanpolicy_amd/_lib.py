@@ -18,7 +18,8 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 LIB_PATH = os.path.join(PKG_DIR, "libxuanpolicy_amd.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["gae.hip", "loss.hip", "rollout.hip", "optim.hip", "mlp.hip", "head.hip", "thin.hip", "per.hip", "atari.hip",
-           "classic.hip", "dqn.hip", "conv.hip", "igemm.hip", "igemm_small.hip", "smallmlp.hip", "sgemm3.hip"]
+           "classic.hip", "dqn.hip", "conv.hip", "igemm.hip", "igemm_small.hip", "igemm_small_wgrad.hip", "smallmlp.hip",
+           "sgemm3.hip"]
 HEADER = os.path.join(REPO_DIR, "include", "xuanpolicy_amd.h")
 
 
@@ -84,8 +85,9 @@ ABI_VERSION, COLSUM_TICKET_INTS = _constants["XPA_ABI_VERSION"], _constants["XPA
 ENV_CODES = {n: v for n, v in _constants.items() if n.startswith("XPA_ENV_")}   # xpa_small_rollout_batch's `env`
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall"]
-# per-source additions: K28R is generated without the packed-f32 VALU forms (v_pk_add / mul / fma_f32)
-EXTRA_FLAGS = {"igemm_small.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-source additions: K28R (and K28R-W) are generated without the packed-f32 VALU forms (v_pk_add / mul / fma_f32)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"igemm_small.hip": _NO_PK_F32, "igemm_small_wgrad.hip": _NO_PK_F32}
 OBJ_DIR = os.path.join(PKG_DIR, "_obj")
 
 _lib = None

@@ -129,6 +129,8 @@ class _OnPolicyAgent:
         self.learner.conv_small_rows = bool(_cfg(config, "conv_small_rows", False))
         # conv_small_rows_bwd: K28R-D for the update's conv data gradients below igemm_min_rows (small minibatches)
         self.learner.conv_small_rows_bwd = bool(_cfg(config, "conv_small_rows_bwd", False))
+        # conv_small_rows_wgrad: K28R-W for the same backward's conv weight gradients
+        self.learner.conv_small_rows_wgrad = bool(_cfg(config, "conv_small_rows_wgrad", False))
         # A2C bootstraps a mid-rollout truncation with V(norm(reset_obs)): a2c_agent.py:88-95 writes obs[i] =
         # reset_obs into next_obs before its critic call (PPO calls the critic first, ppoclip_agent.py:95-101, and
         # both use the final observations for the full-buffer closures).  False: the final observation for A2C too.
@@ -1207,6 +1209,8 @@ class PerDQN_Agent:
         self.learner.conv_small_rows = bool(_cfg(config, "conv_small_rows", False))
         # conv_small_rows_bwd: K28R-D for the learner step's conv data gradients (the eval trunk's backward)
         self.learner.conv_small_rows_bwd = bool(_cfg(config, "conv_small_rows_bwd", False))
+        # conv_small_rows_wgrad: K28R-W for the same backward's conv weight gradients
+        self.learner.conv_small_rows_wgrad = bool(_cfg(config, "conv_small_rows_wgrad", False))
         self.device_env = hasattr(envs, "step_device")
         self.current_step = 0
         self.current_episode = np.zeros(self.n_envs, np.int32)

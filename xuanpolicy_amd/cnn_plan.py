@@ -32,16 +32,19 @@ class ConvFacts(NamedTuple):
     small: bool = False  # K28R takes the forward (xpa_conv_small_ok: 16 / 32 / 64 input channels, <= 64 outputs)
     small_dgrad: bool = False  # K28R-D takes the data gradient (xpa_conv_small_dgrad_ok: 16 / 32 / 64 output channels,
                                # <= 64 inputs, stride 1 or 2)
+    small_wgrad: bool = False  # K28R-W takes the weight gradient (xpa_conv_small_wgrad_ok: 16 / 32 / 64 channels on
+                               # both sides, stride 1 or 2, kernel^2 in out <= 36 864; a trunk asks it together with
+                               # xpa_conv_wgrad_small_fits for the block's input map)
 
 
 def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_ok=None, wgrad_ok=None, small_ok=None,
-               small_dgrad_ok=None):
+               small_dgrad_ok=None, small_wgrad_ok=None):
     """The ConvFacts of one Conv2d: the static shape rules of K27 / K28 / K29.  igemm_ok(in, out, k) and
     wgrad_ok(in, out, k) are the library's xpa_conv_igemm_ok (K28's weight image) and xpa_conv_wgrad_ok (K29's tiling),
     asked by the caller's hand (the planner never asks; None: not asked, no K28 / K29).  A block is on the K28 / K29
     path only when both take it: one that K29 cannot take plans the library route in all three directions.
     small_ok(in, out, k) is xpa_conv_small_ok (K28R's envelope; None: not asked, no K28R); small_dgrad_ok(in, out, k, s)
-    is xpa_conv_small_dgrad_ok (K28R-D's, likewise)."""
+    is xpa_conv_small_dgrad_ok (K28R-D's, likewise), small_wgrad_ok(in, out, k, s) xpa_conv_small_wgrad_ok (K28R-W's)."""
     k, s, p = kernel[0], stride[0], padding[0]
     square = kernel[0] == kernel[1] and stride[0] == stride[1] and padding[0] == padding[1]
     plain = square and zeros and w_contig
@@ -51,7 +54,9 @@ def conv_facts(cin, cout, kernel, stride, padding, zeros, w_contig, act, igemm_o
     k27 = plain and cin == 32 and cout == 64 and s in (1, 2) and k == 2 * s and p < k
     small = bool(plain and small_ok is not None and small_ok(cin, cout, k))
     small_dgrad = bool(plain and small_dgrad_ok is not None and small_dgrad_ok(cin, cout, k, s))
-    return ConvFacts(cin, cout, k, s, p, square, zeros, w_contig, act, igemm, dgrad, k27, small, small_dgrad)
+    small_wgrad = bool(plain and small_wgrad_ok is not None and small_wgrad_ok(cin, cout, k, s))
+    return ConvFacts(cin, cout, k, s, p, square, zeros, w_contig, act, igemm, dgrad, k27, small, small_dgrad,
+                     small_wgrad)
 
 
 class CnnFacts(NamedTuple):
@@ -76,6 +81,7 @@ class CnnFacts(NamedTuple):
     s3_gemms: bool            # ops.S3_GEMMS
     small_conv: bool = False  # K28R for the forwards below igemm_min_rows
     small_conv_bwd: bool = False  # K28R-D for the data gradients below igemm_min_rows
+    small_conv_wgrad: bool = False  # K28R-W for the weight gradients below igemm_min_rows
 
 
 class ConvForm(NamedTuple):
@@ -83,7 +89,7 @@ class ConvForm(NamedTuple):
     act_bwd: str   # who forms this block's dz and bias gradient: "K22" | "K24" (the max pool's) | "K26" | "K29" |
                    # "K40G-act" (the fc data gradient's epilogue) | "K28-dgrad" (the next block's data gradient's) |
                    # "K28R-dgrad" (the same from K28R-D)
-    wgrad: str     # "K26" | "K29" | "miopen"
+    wgrad: str     # "K26" | "K29" | "K28R" (below igemm_min_rows, opt-in) | "miopen"
     dgrad: str     # "none" (the first block) | "K27" | "K28" | "K28R" (below igemm_min_rows, opt-in) | "miopen"
 
 
@@ -93,7 +99,7 @@ _ACT_BWD = {"K22": ("xpa_act_bwd_bias", "xpa_colsum_finalize"), "K10": ("xpa_act
             "K24": ("xpa_maxpool_act_bwd_bias", "xpa_colsum_finalize")}
 # (the weight gradient's finalize, + the bias gradient's where the kernel also forms the activation backward)
 _WGRAD = {"K26": ("xpa_conv1_u8_wgrad_act", "xpa_colsum_finalize"), "K29": ("xpa_conv_wgrad", "xpa_colsum_finalize"),
-          "miopen": ()}
+          "K28R": ("xpa_conv_wgrad_small", "xpa_colsum_finalize"), "miopen": ()}
 _DGRAD = {"none": (), "K27": ("xpa_conv_dgrad_s2k",), "K28": ("xpa_conv_dgrad", "xpa_colsum_finalize"),
           "K28R": ("xpa_conv_dgrad_small", "xpa_colsum_finalize"), "miopen": ()}
 _FC0_FWD = {"K40G": ("xpa_s3_gemm_group",), "linear": ()}
@@ -215,7 +221,11 @@ def plan_cnn(f):
         if f.small_conv_bwd and dgrad == "miopen" and c.small_dgrad and max(numel[i], numel[i + 1]) * 4 < 2 ** 31:
             dgrad = "K28R"
         # the data gradient and the library's weight gradient read dz (K22); K29 alone folds the activation in
-        forms[i] = ConvForm(fwd[i], up or ("K22" if i > 0 or not ig else "K29"), "K29" if ig else "miopen", dgrad)
+        wgrad = "K29" if ig else "miopen"
+        # K28R-W (opt-in): the weight gradient the library route would take, from dz, both operands under 2 GiB
+        if f.small_conv_wgrad and wgrad == "miopen" and c.small_wgrad and max(numel[i], numel[i + 1]) * 4 < 2 ** 31:
+            wgrad = "K28R"
+        forms[i] = ConvForm(fwd[i], up or ("K22" if i > 0 or not ig else "K29"), wgrad, dgrad)
         up = "K28-dgrad" if dgrad == "K28" else "K28R-dgrad" if dgrad == "K28R" else None
     # MIOpen is refused for convs with fewer than 16 input or output channels.  The r02 intermittent
     # hipErrorIllegalAddress of the PER-DQN agent loop (2 of 9 runs, 8-channel test net) surfaced at the

@@ -29,7 +29,8 @@ decided"):
   act_bwd   who forms a conv block's dz and bias gradient: "K22" xpa_act_bwd_bias, "K24" (the pooled gradient routed
             to the argmax), "K26" / "K29" (folded into the weight gradient), "K40G-act", "K28-dgrad" / "K28R-dgrad" (the
             epilogue of the following block's data gradient)
-  wgrad     "K26" xpa_conv1_u8_wgrad_act (from the uint8 frames), "K29" xpa_conv_wgrad, "miopen"
+  wgrad     "K26" xpa_conv1_u8_wgrad_act (from the uint8 frames), "K29" xpa_conv_wgrad, "K28R" xpa_conv_wgrad_small
+            (from dz and the block's input, both split in LDS: the opt-in form below igemm_min_rows), "miopen"
   dgrad     "K27" xpa_conv_dgrad_s2k (the 4 x 4 stride-2 32 -> 64 conv), "K28" xpa_conv_dgrad, "K28R"
             xpa_conv_dgrad_small (K28's result from the conv's transposed split planes: the opt-in form below
             igemm_min_rows), "miopen", "none"
@@ -52,10 +53,11 @@ def _out_hw(conv, H, W):
     return out_hw(H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
 
 
-def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None, small_ok=None, small_dgrad_ok=None):
+def _conv_facts(conv, code, igemm_ok=None, wgrad_ok=None, small_ok=None, small_dgrad_ok=None,
+                small_wgrad_ok=None):
     return conv_facts(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
                       conv.padding_mode == "zeros", conv.weight.is_contiguous(), code, igemm_ok, wgrad_ok, small_ok,
-                      small_dgrad_ok)
+                      small_dgrad_ok, small_wgrad_ok)
 
 
 class _Ctx(NamedTuple):
@@ -218,8 +220,16 @@ class _Trunk:
         # the static shape rules of K27 / K28 / K29 / K28R, asked once (the library's xpa_conv_igemm_ok,
         # xpa_conv_wgrad_ok and xpa_conv_small_ok included)
         L = ops.lib()
-        self.conv_facts = tuple(_conv_facts(conv, code, L.xpa_conv_igemm_ok, L.xpa_conv_wgrad_ok, L.xpa_conv_small_ok,
-                                            L.xpa_conv_small_dgrad_ok) for conv, code, _ in self.convs)
+        # K28R-W's fact is asked with the block's input map (a trunk's maps are fixed): its envelope AND a one-row slab
+        # of this map fitting (xpa_conv_wgrad_small_fits, the launch's own rule), so a too-wide map keeps the library
+        facts, (h, w) = [], (H, W)
+        for conv, code, _ in self.convs:
+            def wgrad_small_ok(ci, co, k, s, h=h, w=w, p=conv.padding[0]):
+                return L.xpa_conv_small_wgrad_ok(ci, co, k, s) and L.xpa_conv_wgrad_small_fits(h, w, ci, co, k, s, p)
+            facts.append(_conv_facts(conv, code, L.xpa_conv_igemm_ok, L.xpa_conv_wgrad_ok, L.xpa_conv_small_ok,
+                                     L.xpa_conv_small_dgrad_ok, wgrad_small_ok))
+            h, w = _out_hw(conv, h, w)
+        self.conv_facts = tuple(facts)
         # K25: the first conv block straight from the uint8 frames (4 channels, 8 x 8 kernel, 32 outputs: the Nature
         # CNN's first layer); the f32 frame copy (K20) is then only made in the backward, for MIOpen's weight gradient
         c0 = self.conv_facts[0]
@@ -256,6 +266,12 @@ class _Trunk:
     # once per weight version (_conv_planes_t).  Independent of small_conv; off by default; the config key
     # conv_small_rows_bwd sets it (tools/conv_small_bwd_ab.py measures it).
     small_conv_bwd = False
+    # small_conv_wgrad: K28R-W (xpa_conv_wgrad_small) for the weight gradients K29 leaves to the library for their row
+    # count: dz and the block's input split once per slab in LDS, a persistent grid's partials into the weight gradient
+    # by the f64 finalize.  With all three switches on, a C5 learner step's backward makes no library convolution call.
+    # Independent of the other two; off by default; the config key conv_small_rows_wgrad sets it
+    # (tools/conv_small_wgrad_ab.py measures it).
+    small_conv_wgrad = False
     # r05, fc_split: the first fc layer of the update's minibatches (C3: [16384, 6400] x [6400, 512]) on the bf16 matrix
     # cores by the three-way split (K40G: one launch per GEMM; forward in 2 k halves x 256-column blocks, summed in a
     # fixed order; the data gradient in 256-column blocks, the last one aligned to the end so no block is padded — the
@@ -284,7 +300,7 @@ class _Trunk:
         reader of the switches above and of ops.S3_GEMMS."""
         return (B, x_u8, self._grads0_contig(), self.use_igemm, self.igemm_min_rows, self.fc_split,
                 self.fc_split_min_rows, self.fc_fuse_act, self.fc_wsplit, ops.S3_GEMMS, self.small_conv,
-                self.small_conv_bwd)
+                self.small_conv_bwd, self.small_conv_wgrad)
 
     def facts(self, B, x_u8=True):
         """The CnnFacts of a pass over B frames (x_u8: a contiguous uint8 device tensor, what the agents feed)."""
@@ -554,6 +570,23 @@ class _Trunk:
         if act >= 0:
             _lib.call(L.xpa_colsum_finalize, ops._p(bpart), G, cout, ops._p(conv.bias.grad), st)
 
+    def _conv_wgrad_small(self, conv, dz, x):
+        """K28R-W: conv.weight.grad from dz NHWC [B, OH, OW, out] (the pre-activation gradient: the bias gradient is
+        written where dz was formed) and the block's input x NHWC f32 [B, H, W, in]."""
+        L, st = ops.lib(), ops._stream(dz.device)
+        B, H, W, C = x.shape
+        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        cols = conv.out_channels * C * k * k
+        G = int(L.xpa_conv_wgrad_small_num_partials(B, H, W, C, conv.out_channels, k, s, p))
+        if G < 1:   # (not from a plan: ConvFacts.small_wgrad holds only where the map fits)
+            _no_form("a conv weight gradient outside xpa_conv_wgrad_small_fits", "K28R")
+        part = self.parts.buf(("wgs", G, cols), (G, cols), dz.device)
+        dz = dz if dz.is_contiguous() else dz.contiguous()
+        x = x if x.is_contiguous() else x.contiguous()
+        _lib.call(L.xpa_conv_wgrad_small, ops._p(dz), ops._p(x), B, H, W, C, conv.out_channels, k, s, p, dz.shape[1],
+                  dz.shape[2], ops._p(part), st)
+        _lib.call(L.xpa_colsum_finalize, ops._p(part), G, cols, ops._p(conv.weight.grad), st)
+
     def _conv_dgrad(self, conv, dz, x_shape, prev, planes=None):
         """K28 data gradient from dz (the block's pre-activation gradient, NHWC) into the block's input; prev = (code,
         slope, y_prev, bias_grad_prev) of the previous block: its activation backward and bias gradient fused in (the
@@ -646,6 +679,8 @@ class _Trunk:
                 self._conv1_wgrad(conv, g, x_in, act=(code, slope, y) if act_bwd == "K26" else None)
             elif wgrad == "K29":
                 self._conv_wgrad(conv, g, code if act_bwd == "K29" else -1, slope, y, x_in)
+            elif wgrad == "K28R":   # from dz: K22, K24, K40G-act or the downstream data gradient's epilogue formed it
+                self._conv_wgrad_small(conv, g, x_in)
             elif wgrad != "miopen":
                 _no_form("conv block %d's weight gradient" % i, wgrad)
             if "miopen" in (wgrad, dgrad):

@@ -37,6 +37,7 @@ class Learner:
         self.fused_cnn_enabled = True
         self.conv_small_rows = False   # config key conv_small_rows: K28R on the trunks this learner builds (small_conv)
         self.conv_small_rows_bwd = False   # config key conv_small_rows_bwd: K28R-D on their backward (small_conv_bwd)
+        self.conv_small_rows_wgrad = False   # config key conv_small_rows_wgrad: K28R-W likewise (small_conv_wgrad)
         self._fc = None        # fused_cnn.FusedCNNActorCritic once built (False: the policy does not take it)
 
     def _trunk_switches(self, trunk, backward=True):
@@ -44,6 +45,7 @@ class Learner:
         forwards, the Q-learner's target)."""
         trunk.small_conv = bool(self.conv_small_rows)
         trunk.small_conv_bwd = bool(backward and self.conv_small_rows_bwd)
+        trunk.small_conv_wgrad = bool(backward and self.conv_small_rows_wgrad)
 
     def save_model(self, model_path):
         torch.save(self.policy.state_dict(), model_path)
