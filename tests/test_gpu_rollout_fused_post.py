@@ -70,7 +70,8 @@ def _compare(f, u):
         assert torch.allclose(f[k], u[k], rtol=1e-4, atol=1e-5), (k, (f[k] - u[k]).abs().max().item())
 
 
-@pytest.mark.parametrize("n_envs,steps", [(1000, 16 + 7), (1002, 13), (4096, 16 + 16), (5, 9)])
+@pytest.mark.parametrize("n_envs,steps", [(1000, 16 + 7), (1002, 13), (4096, 16 + 16), (5, 9),
+                                           (4101, 9)])   # 1026 blocks: 17 ticket groups, the last ragged
 def test_k14f_matches_k14e_k8_rms(monkeypatch, n_envs, steps):
     f = _run(monkeypatch, True, n_envs, steps)
     u = _run(monkeypatch, False, n_envs, steps)
