@@ -625,6 +625,53 @@ int xpa_small_mlp_update_batch(int64_t n_agents, const XpaSmallMlpArgs *host_blo
                                const XpaSmallMlpGauss *host_heads, const XpaSmallMlpGauss *dev_heads,
                                xpa_stream_t stream);
 
+/* K34 — one PER-DQN learner step (perdqn_learner.py:17-48) of a small MLP Q-network in two launches, no eager op
+ * between them: eval and target networks Linear(d_in, h0) + act -> Linear(h0, h1) + act -> Linear(h1, k) (BasicQnetwork
+ * over a one-layer Basic_MLP with one hidden Q-head layer).  The main launch runs n_groups = ceil(batch / 32)
+ * workgroups; workgroup g takes batch rows [32 g, 32 g + 32): it reads them from obs / next [n_rows, obs_ld] and the
+ * flat act / rew / term [n_rows] through idx (the flat indices of PerOffPolicyBuffer.sample_indices; NULL: rows in
+ * order), runs the target network on the next rows first (y = rew + gamma (1 - term) max_a Qt), then the eval network
+ * in the same LDS regions, td = y - Qe[row][act], |td| into td_abs [batch], K19's one-hot d loss / d Qe, and the
+ * backward into grad_part[g * n ...] at the flat gradient's offsets (g* must point inside grad; grad_part is
+ * zero-initialised once and 16-B aligned) with its (sum td^2, sum Qe[act]) into loss_part[2 g ...].  An index outside
+ * [0, n_rows) or an action outside [0, k) is clamped and counted in *err (nullable).  The finalize launch sums the
+ * partials in g order into grad, steps Adam without clipping over the flat buffers [0, n) (K9's arithmetic, (lr, step)
+ * from the device schedule at cursor, xpa_clip_adam_step_sched's convention; the launch advances cursor[0]), writes
+ * scalars[0] = Qloss = sum td^2 / batch and scalars[1] = predictQ = sum Qe[act] / batch and, when sync_target is set,
+ * copies the updated eval parameters over the target ones (tW0 ... tbq: the hard update of perdqn_learner.py:38-39).
+ * The flat buffers may hold more than the eval network (the target copies: their gradient stays zero, and Adam with
+ * zero moments leaves them bit for bit).  Limits (xpa_small_q_ok): d_in <= 32, h0, h1 in {32, 64, 128}, 2 <= k <= 16,
+ * 1 <= batch <= 512, xpa_small_q_lds_floats(32, ...) <= 40704; flat buffers 16-B aligned, n % 4 == 0. */
+typedef struct XpaSmallQArgs {
+    int batch, d_in, h0, h1, k, act_code, sync_target, n_sched, n_groups;
+    float slope, gamma, beta1, beta2, eps;
+    const float *obs, *next;
+    int64_t obs_ld;
+    const int64_t *idx;
+    int64_t n_rows;
+    const float *act, *rew, *term;
+    const float *W0, *b0, *W1, *b1, *Wq, *bq;
+    float *tW0, *tb0, *tW1, *tb1, *tWq, *tbq;
+    float *gW0, *gb0, *gW1, *gb1, *gWq, *gbq;
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    int64_t n;
+    const float *sched;
+    int32_t *cursor;
+    float *td_abs, *scalars;
+    int32_t *err;
+    float *grad_part;
+    double *loss_part;
+} XpaSmallQArgs;
+/* LDS floats of one K34 workgroup of `rows` rows (rounded up to 32; the launches use 32), and the admission
+ * predicate (1: the shape is taken) that xpa_small_q_update checks before any launch. */
+int64_t xpa_small_q_lds_floats(int64_t rows, int64_t d_in, int64_t h0, int64_t h1, int64_t k);
+int xpa_small_q_ok(int64_t batch, int64_t d_in, int64_t h0, int64_t h1, int64_t k);
+int xpa_small_q_update(const XpaSmallQArgs *args, xpa_stream_t stream);
+/* K34's forward alone: the eval network of args (its dimensions, activation and W0 ... bq; nothing else is read) on
+ * rows [n, ld], Q values into q_out [n, k]; one workgroup per 32 rows, K34's tile arithmetic. */
+int xpa_small_q_values(const XpaSmallQArgs *args, const float *rows, int64_t ld, int64_t n, float *q_out,
+                       xpa_stream_t stream);
+
 /* K10 — activation backward fused with bias-gradient column sums for one MLP layer (row-major
  * [rows, cols]).  Replaces the activation backward and the bias-gradient reduction torch autograd runs
  * per mlp_block (xuance/torch/utils/layers.py:8-24) inside loss.backward() (ppoclip_learner.py:46).

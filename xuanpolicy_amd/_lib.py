@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libxuanpolicy_amd.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["gae.hip", "loss.hip", "rollout.hip", "optim.hip", "mlp.hip", "head.hip", "thin.hip", "per.hip", "atari.hip",
            "classic.hip", "dqn.hip", "conv.hip", "igemm.hip", "igemm_small.hip", "igemm_small_wgrad.hip", "smallmlp.hip",
-           "sgemm3.hip"]
+           "sgemm3.hip", "smallq.hip"]
 HEADER = os.path.join(REPO_DIR, "include", "xuanpolicy_amd.h")
 
 
@@ -81,6 +81,7 @@ with open(HEADER) as _f:
 XpaSmallMlpArgs, XpaSmallRolloutArgs = _structs["XpaSmallMlpArgs"], _structs["XpaSmallRolloutArgs"]
 XpaSmallRolloutHead, XpaSmallMlpGauss = _structs["XpaSmallRolloutHead"], _structs["XpaSmallMlpGauss"]
 XpaSmallCloseArgs, XpaSmallEval = _structs["XpaSmallCloseArgs"], _structs["XpaSmallEval"]
+XpaSmallQArgs = _structs["XpaSmallQArgs"]
 ABI_VERSION, COLSUM_TICKET_INTS = _constants["XPA_ABI_VERSION"], _constants["XPA_COLSUM_TICKET_INTS"]
 ENV_CODES = {n: v for n, v in _constants.items() if n.startswith("XPA_ENV_")}   # xpa_small_rollout_batch's `env`
 

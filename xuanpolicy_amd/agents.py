@@ -1211,6 +1211,9 @@ class PerDQN_Agent:
         self.learner.conv_small_rows_bwd = bool(_cfg(config, "conv_small_rows_bwd", False))
         # conv_small_rows_wgrad: K28R-W for the same backward's conv weight gradients
         self.learner.conv_small_rows_wgrad = bool(_cfg(config, "conv_small_rows_wgrad", False))
+        # small_q: K34, the learner step (and the action selection's forward) of a small MLP Q-network in HIP; the
+        # kernel gathers the batch from the replay arrays through the sampled flat index
+        self.learner.small_q = bool(_cfg(config, "small_q", False))
         self.device_env = hasattr(envs, "step_device")
         self.current_step = 0
         self.current_episode = np.zeros(self.n_envs, np.int32)
@@ -1270,8 +1273,16 @@ class PerDQN_Agent:
             self.memory.store(first, acts, rew, term, nxt)
             if self.current_step > self.start_training and self.current_step % self.train_frequency == 0:
                 u = self.uniform_source() if self.uniform_source is not None else None
-                o, a, r, d, n, w, idxes = self.memory.sample(self.PER_beta, uniforms=u)
-                td_abs, info = self.learner.update(o, a, r, n, d, sync_info=sync_info)
+                mem = self.memory
+                rows = mem.observations.reshape(mem.n_envs * mem.n_size, -1) if self.learner.small_q else None
+                if rows is not None and self.learner.small_q_ok(rows, mem.batch_size):
+                    idxes, flat, w = mem.sample_indices(self.PER_beta, uniforms=u)   # K34 gathers: no gathered copy
+                    td_abs, info = self.learner.update(rows, mem.actions.reshape(-1), mem.rewards.reshape(-1),
+                                                       mem.next_observations.reshape(rows.shape), mem.terminals.reshape(-1),
+                                                       sync_info=sync_info, idx=flat)
+                else:
+                    o, a, r, d, n, w, idxes = mem.sample(self.PER_beta, uniforms=u)
+                    td_abs, info = self.learner.update(o, a, r, n, d, sync_info=sync_info)
                 self.memory.update_priorities(idxes, td_abs, check=False)
                 info["epsilon-greedy"] = self.egreedy
                 self.infos.append(info)

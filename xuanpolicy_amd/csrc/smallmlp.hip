@@ -18,61 +18,13 @@
 // 95 us per update at C1, 222 k cycles of which 41 k in the output layers alone).  In-place reuse: h1 / h2 become
 // dh1 / dh2 once the output layers' weight gradients are formed, h0 becomes dh0 once the hidden ones' are.
 // Arithmetic of the loss and of the clip + Adam step: exactly K2's per-row formulas (loss.hip) and K9's (optim.hip).
-#include "xpa_common.h"
+#include "small_tile.h"
 
 namespace {
 
 constexpr int kSmThreads = 512;
 constexpr int kSmWaves = kSmThreads / 64;
 constexpr int kSmLds = 40704;   // floats (159 KiB: the rest of the 160 KiB holds the reduction scratch)
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <int ACT>
-__device__ __forceinline__ float sm_act(float z, float slope) {
-    if (ACT == 1) return z > 0.f ? z : z * slope;
-    if (ACT == 2) return tanhf(z);
-    return z;
-}
-template <int ACT>
-__device__ __forceinline__ float sm_grad(float y, float slope) {   // d act / d z from the output y
-    if (ACT == 1) return y > 0.f ? 1.f : slope;
-    if (ACT == 2) return 1.f - y * y;
-    return 1.f;
-}
-
-// One 32 x 32 tile D[m][n] = sum_{k < kred} A(m, k) B(k, n) with A(m, k) = pa[k ak + m am], B(k, n) = pb[k bk + n bn]
-// (LDS), rows m >= mvalid / columns n >= nvalid of the operands read as 0.  Lane (i, h) feeds A(i, k + h) and
-// B(k + h, i); D element r of lane (i, h) is D[(r & 3) + 8 (r >> 2) + 4 h][i].
-__device__ __forceinline__ f32x16 sm_tile(const float *pa, int am, int ak, int mvalid, const float *pb, int bk, int bn,
-                                          int nvalid, int kred) {
-    const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
-    const bool av = i < mvalid, bv = i < nvalid;
-    const float *qa = pa + (av ? i : 0) * am + h * ak, *qb = pb + (bv ? i : 0) * bn + h * bk;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    // 8 k-steps per group: the 16 operand reads issued before the group's MFMAs (a plain loop ran load, wait,
-    // MFMA per k-step: one LDS round trip per MFMA)
-    int k = 0;
-    for (; k + 16 <= kred; k += 16) {
-        float x[8], y[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            x[u] = qa[(k + 2 * u) * ak];
-            y[u] = qb[(k + 2 * u) * bk];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av ? x[u] : 0.f, bv ? y[u] : 0.f, acc, 0, 0, 0);
-    }
-    for (; k < kred; k += 2) {
-        const float x = qa[k * ak], y = qb[k * bk];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av ? x : 0.f, bv ? y : 0.f, acc, 0, 0, 0);
-    }
-    return acc;
-}
-__device__ __forceinline__ int sm_row(int r) { return (r & 3) + 8 * (r >> 2) + 4 * ((threadIdx.x & 63) >> 5); }
-
 #define XPA_SM_STAMP(i_)                                                                                  \
     do {                                                                                                  \
         if (a.stamps && t == 0 && blockIdx.x == 0) a.stamps[i_] = (int64_t)__builtin_amdgcn_s_memtime(); \

@@ -624,6 +624,62 @@ class PerDQN_Learner(Learner):
         super().__init__(policy, optimizer, scheduler, device, model_dir)
         self._err = None
         self._fq = None        # fused_cnn.FusedQNetwork once built (False: the policy does not take it)
+        self.small_q = False   # config key small_q: K34, the whole step of a small MLP Q-network in HIP (opt-in)
+        self._sq = None        # small_path.SmallQ once built (False: the policy or the optimizer does not take it)
+
+    # ---- K34: the learner step of a small MLP Q-network (the reference's perdqn/classic_control nets) ----------------
+    def _small_q_state(self):
+        sq = self._sq
+        if sq is None:
+            sq = False
+            if next(self.policy.parameters()).is_cuda and hasattr(self.policy, "eval_Qhead"):
+                try:
+                    sq = small_path.SmallQ(self.policy, self.optimizer)
+                except ValueError:
+                    sq = False
+            self._sq = sq
+        return sq or None
+
+    def small_q_ok(self, obs, batch):
+        """True when `batch` rows of obs [n_rows, d] can take K34 (xpa_small_q_update; any row count takes
+        xpa_small_q_values): the flag, f32 device rows, a small_path.SmallQ network under a plain Adam, and the
+        kernel's own admission predicate."""
+        if not self.small_q or self.grad_sync is not None:
+            return False
+        if not (isinstance(obs, torch.Tensor) and obs.is_cuda and obs.dim() == 2 and obs.dtype == torch.float32
+                and obs.stride(1) == 1):
+            return False
+        sq = self._small_q_state()
+        return sq is not None and obs.shape[1] == sq.dims[0] and ops.small_q_ok(batch, *sq.dims)
+
+    def _rows(self, x, dev):
+        """Observations as f32 device rows [n, d]."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(x)
+        x = x.to(device=dev, dtype=torch.float32)
+        return x.reshape(x.shape[0], -1) if x.dim() != 2 else x
+
+    def _small_q_update(self, obs, act, rew, nxt, term, idx, sync_info):
+        """One update through K34: the device part (two launches), then the host bookkeeping of the step."""
+        sq, dev = self._small_q_state(), obs.device
+        batch = obs.shape[0] if idx is None else idx.shape[0]
+        sq.fused.ensure_window(self.scheduler)
+        if self._err is None:
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        td_abs = torch.empty(batch, dtype=torch.float32, device=dev)
+        sc = torch.empty(2, dtype=torch.float32, device=dev)
+        a = sq.args(obs, nxt, self._f32(act, dev), self._f32(rew, dev), self._f32(term, dev), idx, batch, self.gamma,
+                    (self.iterations + 1) % self.sync_frequency == 0, td_abs, sc, err=self._err)
+        ops.small_q_update(a, dev)
+        self.iterations += 1
+        sq.fused.host_step()
+        if self.scheduler is not None:
+            self.scheduler.step()
+        lr = self.optimizer.param_groups[0]["lr"]
+        if not sync_info:
+            return td_abs, {"Qloss": sc[0], "learning_rate": lr, "predictQ": sc[1]}
+        q = sc.cpu().tolist()
+        return td_abs, {"Qloss": q[0], "learning_rate": lr, "predictQ": q[1]}
 
     def _f32(self, x, dev):
         if isinstance(x, torch.Tensor):
@@ -652,12 +708,24 @@ class PerDQN_Learner(Learner):
         fq = self._fused_q()
         if fq is not None and isinstance(obs, torch.Tensor) and obs.dtype == torch.uint8 and obs.is_cuda:
             return fq.forward(obs.contiguous())[0]
+        if self.small_q and self.small_q_ok(obs, 1):   # K34's forward form
+            return ops.small_q_values(self._small_q_state().forward_block(), obs)
         with torch.no_grad():
             return self.policy(obs)[2]
 
-    def update(self, obs_batch, act_batch, rew_batch, next_batch, terminal_batch, sync_info=True):
+    def update(self, obs_batch, act_batch, rew_batch, next_batch, terminal_batch, sync_info=True, idx=None):
+        """idx (K34 only): int64 device indices of the batch's rows in obs / act / rew / next / terminal, which are then
+        the whole replay arrays (PerOffPolicyBuffer.sample_indices' flat index): the kernel gathers."""
+        if self.small_q and self._small_q_state() is not None:
+            dev = next(self.policy.parameters()).device
+            obs, nxt = self._rows(obs_batch, dev), self._rows(next_batch, dev)
+            if self.small_q_ok(obs, obs.shape[0] if idx is None else idx.shape[0]):
+                return self._small_q_update(obs, act_batch, rew_batch, nxt, terminal_batch, idx, sync_info)
+        if idx is not None:
+            raise ValueError("a row index needs the K34 path (small_q and a shape small_q_ok admits)")
         self.iterations += 1
         fq = self._fused_q()
+        sq = self._sq or None   # built by an earlier small_q call: the parameters and Adam's state live in its flat buffers
         fused = (fq is not None and isinstance(obs_batch, torch.Tensor) and obs_batch.dtype == torch.uint8
                  and obs_batch.is_cuda and isinstance(next_batch, torch.Tensor) and next_batch.dtype == torch.uint8)
         if fused:   # K20 frames, MIOpen convs + K21, K23 max pool, Q head GEMMs; backward K24 / K22 + MIOpen
@@ -675,9 +743,22 @@ class PerDQN_Learner(Learner):
         if fused:
             fq.backward(ctx, dQ)           # overwrites every eval-network gradient
         else:
-            self.optimizer.zero_grad()
+            if sq is not None:
+                sq.fs.ensure_views()       # autograd accumulates into the flat gradient's views
+                sq.fs.zero_()
+            else:
+                self.optimizer.zero_grad()
             evalQ.backward(dQ)
-        self.optimizer.step()
+        if sq is not None:
+            # K34's flat state exists but this batch is outside its admission (more than 512 rows): the step still goes
+            # through the flat state's Adam (K9 without clipping, from the device schedule), which owns the moments,
+            # the one step count and the schedule cursor — optimizer.step() would advance the shared step once per
+            # parameter
+            sq.fused.ensure_window(self.scheduler)
+            sq.fused.launch_sched(None)
+            sq.fused.host_step()
+        else:
+            self.optimizer.step()
         if self.scheduler is not None:
             self.scheduler.step()
         if self.iterations % self.sync_frequency == 0:

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from .small_path import small_close, small_close_args, small_close_batch, small_eval, small_eval_batch  # noqa: F401
+from .small_path import small_q_ok, small_q_update, small_q_values  # noqa: F401  (K34)
 
 ALGO = {"ppo": 0, "a2c": 1}
 DIST = {"gaussian": 0, "categorical": 1}

@@ -248,6 +248,33 @@ def build_perdqn(n_envs=8, n_size=131072, batch_size=2048, seed=1, device="cuda:
     return PerDQN_Agent(cfg, envs, policy, opt, sch, device)
 
 
+def build_perdqn_classic(env_id, small_q=False, device="cuda:0", **overrides):
+    """PER-DQN on a device classic-control env (perdqn/classic_control/<env_id>.yaml keys): Basic_MLP [128] +
+    BasicQnetwork with one hidden Q-head layer [128], Adam(eps=1e-5) + LinearLR as build_perdqn builds them.
+    small_q: the learner step and the action selection's forward through K34 (config key small_q).  The device replay
+    samples batch_size / parallels rows per env, as the reference does (its 128 over 10 envs are 12 each): a batch size
+    that is no multiple of the env count is rounded down to one."""
+    from .agents import PerDQN_Agent
+    from .policies import BasicQnetwork
+    cfg = get_arguments("perdqn", "classic_control", env_id)
+    if getattr(cfg, "env_name", None) != "Classic Control" or getattr(cfg, "env_id", None) != env_id:
+        raise ValueError("no PerDQN config for the classic-control env %r" % (env_id,))
+    cfg.small_q = bool(small_q)
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    cfg.batch_size -= cfg.batch_size % cfg.parallels
+    cfg.device = str(device)
+    torch.manual_seed(cfg.seed)
+    envs = make_envs(cfg, device=device)
+    act = ActivationFunctions[cfg.activation]
+    rep = Basic_MLP(envs.observation_space.shape, cfg.representation_hidden_size, None, torch.nn.init.orthogonal_, act,
+                    device)
+    policy = BasicQnetwork(envs.action_space, rep, cfg.q_hidden_size, None, torch.nn.init.orthogonal_, act, device)
+    opt = torch.optim.Adam(policy.parameters(), cfg.learning_rate, eps=1e-5)
+    sch = torch.optim.lr_scheduler.LinearLR(opt, start_factor=1.0, end_factor=0.0, total_iters=cfg.running_steps)
+    return PerDQN_Agent(cfg, envs, policy, opt, sch, device)
+
+
 def build_atari_a2c(n_envs=1024, n_steps=128, seed=1, device="cuda:0", **overrides):
     """The BASELINE.json C3 configuration: A2C, AC_CNN_Atari, SynthAtari 4x84x84 uint8 frames, 6 actions."""
     cfg = get_arguments("a2c", "atari", "SynthAtari-v0")

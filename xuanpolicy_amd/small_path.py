@@ -206,6 +206,144 @@ def update(block, logstd, device):
               _stream(device))
 
 
+# ---- K34: the PER-DQN learner step of a small MLP Q-network ------------------------------------------------------------
+def small_q_ok(batch, d_in, h0, h1, k):
+    """K34's admission predicate (xpa_small_q_ok, the one the launch checks): host arithmetic, no device."""
+    return bool(_lib.load().xpa_small_q_ok(int(batch), int(d_in), int(h0), int(h1), int(k)))
+
+
+def small_q_update(block, device):
+    """K34 (xpa_small_q_update): the main launch and the finalize of one learner step; block: SmallQ.args'."""
+    _lib.call(_lib.load().xpa_small_q_update, ctypes.byref(block), _stream(device))
+
+
+def small_q_values(block, rows, out=None):
+    """K34's forward alone (xpa_small_q_values): Q [n, A] of the block's eval network on rows [n, d_in] (f32, unit
+    column stride)."""
+    from .ops import _req, _row_stride
+    _req(rows, "rows", torch.float32, contiguous=False)
+    ld = _row_stride(rows, "rows", block.d_in)
+    n = rows.shape[0]
+    if out is None:
+        out = torch.empty((n, block.k), dtype=torch.float32, device=rows.device)
+    _req(out, "out", torch.float32, (n, block.k))
+    _lib.call(_lib.load().xpa_small_q_values, ctypes.byref(block), _p(rows), ld, n, _p(out), _stream(rows.device))
+    return out
+
+
+class SmallQ:
+    """The host side of K34 for a BasicQnetwork whose representation is one mlp_block and whose Q head is one hidden
+    mlp_block plus the output Linear, both hidden layers with one activation (else ValueError): every parameter the
+    optimizer holds as a view of one flat buffer (flat.FlatState) with the fused Adam's moments and device schedule
+    (flat.FusedClipAdam).  torch.optim.Adam(policy.parameters()) holds the target copies too: their span of the flat
+    gradient stays zero, which Adam's step with zero moments leaves bit for bit, and the kernel steps the whole buffer
+    (no span bookkeeping in the kernel; optimizer.state_dict() still loads into an eager learner, which skips them)."""
+
+    def __init__(self, policy, optimizer):
+        from .flat import FlatState, FusedClipAdam, fused_adam_compatible
+        from .fused_mlp import _act_code
+        nets = []
+        for rep, head in ((policy.representation, policy.eval_Qhead), (policy.target_representation, policy.target_Qhead)):
+            rep, head = list(getattr(rep, "model", ())), list(head.model)
+            lin = torch.nn.Linear
+            if not (len(rep) == 2 and len(head) == 3 and isinstance(rep[0], lin) and isinstance(head[0], lin)
+                    and isinstance(head[2], lin) and _act_code(rep[1]) == _act_code(head[1])):
+                raise ValueError("K34 takes Linear + act -> Linear + act -> Linear Q-networks")
+            if any(l.bias is None or l.weight.dtype != torch.float32 or not l.weight.is_cuda
+                   for l in (rep[0], head[0], head[2])):
+                raise ValueError("K34 takes float32 device layers with biases")
+            nets.append((rep[0], head[0], head[2]))
+            self.code, self.slope = _act_code(rep[1])
+        self.layers, self.target = nets
+        if [tuple(l.weight.shape) for l in self.layers] != [tuple(l.weight.shape) for l in self.target] \
+                or self.layers[1].in_features != self.layers[0].out_features \
+                or self.layers[2].in_features != self.layers[1].out_features:
+            raise ValueError("eval and target networks differ in shape")
+        if not fused_adam_compatible(optimizer):   # before the parameters are re-homed into the flat buffer
+            raise ValueError("K34 steps a plain torch.optim.Adam with one param group")
+        self.fs = FlatState(optimizer.param_groups[0]["params"])
+        self.fused = FusedClipAdam(optimizer, self.fs).enable_sched()
+        # the flat Adam keeps ONE step tensor for all parameters; an eager torch.optim.Adam that loaded it as it is would
+        # advance it once per parameter and step: state_dict() hands every parameter a step of its own
+        optimizer.register_state_dict_post_hook(self._own_steps)
+        self._off = {id(p): o for p, o in zip(self.fs.params, self.fs.offsets)}
+        if any(id(p) not in self._off for l in self.layers + self.target for p in (l.weight, l.bias)):
+            raise ValueError("the optimizer does not hold the Q-network's parameters")
+        self._ws = {}   # workgroup count -> (gradient partials, loss partials), zero-filled once
+
+    @staticmethod
+    def _own_steps(optimizer, state_dict):
+        state_dict["state"] = {k: dict(st, step=st["step"].clone()) if "step" in st else st
+                               for k, st in state_dict["state"].items()}
+        return state_dict
+
+    @property
+    def dims(self):
+        """(d_in, h0, h1, A)"""
+        l0, l1, lq = self.layers
+        return l0.in_features, l0.out_features, l1.out_features, lq.out_features
+
+    def _grad_ptr(self, p):
+        return self.fs.flat.data_ptr() + 4 * self._off[id(p)]
+
+    def forward_block(self):
+        """The block xpa_small_q_values reads: the dimensions, the activation and the eval layers."""
+        a = _lib.XpaSmallQArgs()
+        a.d_in, a.h0, a.h1, a.k = self.dims
+        a.act_code, a.slope = int(self.code), float(self.slope)
+        l0, l1, lq = self.layers
+        a.W0, a.b0, a.W1, a.b1, a.Wq, a.bq = (_p(l0.weight), _p(l0.bias), _p(l1.weight), _p(l1.bias), _p(lq.weight),
+                                              _p(lq.bias))
+        return a
+
+    def args(self, obs, nxt, act, rew, term, idx, batch, gamma, sync_target, td_abs, scalars, err=None):
+        """The block of one learner step.  obs / nxt f32 [n_rows, d_in] (one row stride), act / rew / term f32
+        [n_rows]; idx int64 [batch] or None (rows 0 .. batch - 1); td_abs f32 [batch], scalars f32 [2], err int32 [1]
+        or None.  The block holds addresses and, as a Python object, references that keep the tensors alive."""
+        from .ops import _req, _row_stride
+        d_in = self.dims[0]
+        for name, t in (("obs", obs), ("next", nxt)):
+            _req(t, name, torch.float32, contiguous=False)
+            _row_stride(t, name, d_in)
+        n_rows = obs.shape[0]
+        if nxt.shape[0] != n_rows or nxt.stride(0) != obs.stride(0):
+            raise ValueError("obs and next must have the same rows and row stride")
+        for name, t in (("act", act), ("rew", rew), ("term", term)):
+            _req(t, name, torch.float32, (n_rows,))
+        if idx is not None:
+            _req(idx, "idx", torch.int64, (batch,))
+        elif batch > n_rows:
+            raise ValueError("batch exceeds the rows given")
+        _req(td_abs, "td_abs", torch.float32, (batch,))
+        _req(scalars, "scalars", torch.float32, (2,))
+        if err is not None:
+            _req(err, "err", torch.int32, (1,))
+        fused, fs = self.fused, self.fs
+        g = fused.optimizer.param_groups[0]
+        a = self.forward_block()
+        a.batch, a.sync_target, a.n_sched, a.n_groups = int(batch), int(bool(sync_target)), fused.SCHED_WINDOW, \
+            (int(batch) + 31) // 32
+        a.gamma, a.beta1, a.beta2, a.eps = float(gamma), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+        a.obs, a.next, a.obs_ld, a.idx, a.n_rows = _p(obs), _p(nxt), obs.stride(0), None if idx is None else _p(idx), n_rows
+        a.act, a.rew, a.term = _p(act), _p(rew), _p(term)
+        (l0, l1, lq), (t0, t1, tq) = self.layers, self.target
+        a.tW0, a.tb0, a.tW1, a.tb1, a.tWq, a.tbq = (_p(t0.weight), _p(t0.bias), _p(t1.weight), _p(t1.bias), _p(tq.weight),
+                                                    _p(tq.bias))
+        a.gW0, a.gb0, a.gW1, a.gb1, a.gWq, a.gbq = (self._grad_ptr(p) for p in (l0.weight, l0.bias, l1.weight, l1.bias,
+                                                                               lq.weight, lq.bias))
+        a.param, a.grad, a.exp_avg, a.exp_avg_sq, a.n = _p(fs.param), _p(fs.flat), _p(fused.exp_avg), \
+            _p(fused.exp_avg_sq), fs.numel
+        a.sched, a.cursor = _p(fused._sched), _p(fused._cursor)
+        a.td_abs, a.scalars, a.err = _p(td_abs), _p(scalars), None if err is None else _p(err)
+        G = a.n_groups
+        if G not in self._ws:
+            self._ws[G] = (torch.zeros((G, fs.numel), dtype=torch.float32, device=fs.param.device),
+                           torch.zeros((G, 2), dtype=torch.float64, device=fs.param.device))
+        a.grad_part, a.loss_part = _p(self._ws[G][0]), _p(self._ws[G][1])
+        a._keep = (obs, nxt, act, rew, term, idx, td_abs, scalars, err)
+        return a
+
+
 def update_batch(n_agents, blocks, heads, device):
     """xpa_small_mlp_update_batch: one minibatch update of every agent in one launch (capturable); blocks / heads as
     rollout_batch's, the heads XpaSmallMlpGauss."""
